@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: batched RNNoise (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One step = one pass of the hot path (high-pass -> frame kernel -> history roll, i.e. one
 `crispy_rn_process_device` call) over one batch of synthetic 48 kHz audio that is already
@@ -9,12 +9,23 @@ resident in HBM: `--streams` concurrent streams (default 4096) x `--frames` cons
 frames (default 100 = 1 s of audio per stream).  Metric: concurrent real-time 48 kHz streams per
 GPU = frames/s / 100, summed over ranks (streams shard with no data-path collective).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step), nothing more.
+
+--dump-outputs DIR  after the timed steps, rank 0 writes what its last timed step computed:
+                    DIR/denoised.npy, float32 [frames, streams, 480] -- the denoised samples of a fixed
+                    seeded sample of the streams (every stream when they fit) over the last frames of the
+                    step, at most 48 MiB (dump_selection); with --host-fed also DIR/vad.npy, float32
+                    [frames, streams], the VAD probabilities of the same sample.  Inputs are seeded: the same
+                    arguments give the same inputs on every run.
+--full              everything else, after the headline has been timed.  The JSON line then also carries
   roofline      HBM roofline of the dominant kernel (rn_frame_kernel): algorithmic bytes per launch
                 (3840 B per stream-frame) / its average duration measured with hipEvents on the
                 launch stream, against the 8 TB/s HBM3E peak.
   cpu_baseline  the C oracle (CPU restatement of the reference algorithm; the reference's Rust crates
                 cannot be built here) timed on this box's host cores on a bounded sample, rank 0, N=1.
+  sustained, host_fed, latency_us, asr, asr_rtfx, cfg4, cfg5
+                the legs each `--no-...` option names (see --help); each is skipped by its option.
 """
 from __future__ import annotations
 
@@ -901,17 +912,23 @@ def main():
                     help="cfg5: 1 = f16 operands / f32 accumulation, the arithmetic of the reference's whisper.cpp engine (default); "
                          "0 = exact f32 products (the mode the oracle parity is stated in)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-fed", action="store_true", help="cfg2: skip the PCIe-inclusive leg (f32 and int16 transport) of the default run")
+    ap.add_argument("--no-host-fed", action="store_true", help="cfg2: skip the PCIe-inclusive leg (f32 and int16 transport) of a --full run")
     ap.add_argument("--no-asr", action="store_true", help="skip the Whisper-tiny leg of the metric")
     ap.add_argument("--no-latency", action="store_true", help="skip the single-stream process_frame latency leg")
     ap.add_argument("--no-cfg45", action="store_true", help="cfg2: skip the in-process cfg4 / cfg5 legs")
     ap.add_argument("--sustain-seconds", type=float, default=5.0,
-                    help="cfg2: length of the sustained-rate loop behind the timed steps (0 = off)")
+                    help="cfg2 --full: length of the sustained-rate loop behind the timed steps (0 = off)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not run the two rocprofv3 --pmc passes; roofline.traffic then comes from profiles/")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher self-test on CPU (gloo, no GPU work, no value); used by tests/test_sharding_gloo.py")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="cfg2: write what the last timed step computed as DIR/denoised.npy (float32, a fixed seeded "
+                         "sample of at most 48 MiB; see dump_selection)")
+    ap.add_argument("--full", action="store_true",
+                    help="cfg2: after the headline, also the roofline, sustained, cpu_baseline, host_fed, latency_us, asr "
+                         "and cfg4 / cfg5 legs (each still skipped by its --no-... option); off: the headline alone")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = {"cfg5": 4, "cfg4": 2}.get(args.workload, 10)
@@ -919,6 +936,8 @@ def main():
         args.new_tokens = 64 if args.workload == "cfg4" else 32
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.dump_outputs and args.workload != "cfg2":
+        ap.error("--dump-outputs: cfg2 only")
 
     # One process per GPU.  Under a launcher (torch.distributed.run sets WORLD_SIZE) this process IS a rank; without
     # one, --gpus N > 1 starts its own N ranks as fresh children BEFORE anything here has imported torch or touched
@@ -993,6 +1012,93 @@ def host_fed_leg(ds, d_in, B, T, steps=20, warmup=2):
             "entry_points": "crispy_rn_process / crispy_rn_process_s16 (pieces of frames on three streams; DESIGN section 6)"}
 
 
+DUMP_BYTES = 48 << 20        # --dump-outputs: the sample's size cap (64 MB allowed)
+
+
+def dump_selection(B: int, T: int, cap: int = DUMP_BYTES):
+    """What --dump-outputs keeps of a [T, B, 480] f32 step output: (first frame, sorted stream indices).  As many whole
+    frame rows of streams as `cap` holds -- every stream when they fit, else a sample drawn with a fixed seed -- over the
+    last frames of the step.  Depends on (B, T) alone, so two runs with the same arguments keep the same samples."""
+    import numpy as np
+    row = 480 * 4
+    n_s = max(1, min(B, cap // (row * T)))
+    n_f = max(1, min(T, cap // (row * n_s)))
+    idx = np.arange(B) if n_s == B else np.sort(np.random.default_rng(0).choice(B, size=n_s, replace=False))
+    return T - n_f, idx
+
+
+def dump_outputs(dirpath: str, out, B: int, T: int, vad=None):
+    """--dump-outputs: the dump_selection sample of the step output `out` ([T, B, 480] f32, torch on the device or numpy
+    on the host) as dirpath/denoised.npy, and of the VAD probabilities `vad` ([T, B] f32 on the host, what the host-fed
+    call returns beside it) as dirpath/vad.npy."""
+    import numpy as np
+    f0, idx = dump_selection(B, T)
+    if isinstance(out, np.ndarray):
+        sample = out[f0:, idx]
+    else:
+        import torch
+        sample = out[f0:].index_select(1, torch.from_numpy(idx).to(out.device)).cpu().numpy()
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, "denoised.npy"), np.ascontiguousarray(sample, dtype=np.float32))
+    if vad is not None:
+        np.save(os.path.join(dirpath, "vad.npy"), np.ascontiguousarray(vad[f0:, idx], dtype=np.float32))
+
+
+def cfg2_roofline(args, B: int, T: int, world: int, k_ms):
+    """--full: rn_frame_kernel against the VALU and HBM roofs, from `k_ms` -- crispy_rn_last_kernel_ms of three steps
+    timed with hipEvents after the headline -- and the kernel's HBM traffic (live rocprofv3 passes or profiles/)."""
+    from crispy_amd import _native as N
+    # rn_frame_kernel launches per step (a call starts with short launches of 3 and 8 frames, then 12 per launch);
+    # per-launch figures below are averages over them: algorithmic bytes of a step / launches, kernel time / launches
+    launches = N.lib().crispy_rn_n_launches(T)
+    frame_ms = sum(k[0] for k in k_ms) / len(k_ms) / launches
+    total_ms = sum(k[1] for k in k_ms) / len(k_ms)
+    alg_bytes = BYTES_PER_STREAM_FRAME * B * T / launches
+    # HBM traffic per launch: measured live on this box by two rocprofv3 --pmc child passes (measure_traffic);
+    # if that is not possible the committed passes of the same launch shape are quoted and labelled as such.
+    traffic = None
+    traffic_src = None
+    valu = None
+    if world == 1 and not args.no_live_traffic:
+        try:
+            tr = measure_traffic(B, T)
+            traffic = int((tr["fetch_bytes"] + tr["write_bytes"]) * B * T / launches)
+            traffic_src = {"how": "live: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) over "
+                                  "`bench.py --pmc-child` on this box; FETCH_SIZE x2 (gfx950), KiB -> bytes",
+                           "fetch_bytes_per_stream_frame": tr["fetch_bytes"],
+                           "write_bytes_per_stream_frame": tr["write_bytes"]}
+        except Exception as e:
+            traffic_src = {"how": "committed profile (live measurement failed)", "error": str(e)[:200]}
+    try:
+        pm_file, streams, psf = committed_pmc()
+        if streams == B:
+            sf = B * T / launches                        # stream-frames per (average) launch
+            if traffic is None:
+                traffic = int((2 * psf["FETCH_SIZE"] + psf["WRITE_SIZE"]) * 1024 * sf)
+                traffic_src = dict(traffic_src or {}, file=pm_file)
+            # what actually bounds this kernel: VALU issue slots.  SQ_ACTIVE_INST_VALU counts 4-cycle issue
+            # slots; 1024 SIMDs; priced against the live kernel time at the 2.4 GHz peak clock.
+            valu = {"insts_per_stream_frame": round(psf["SQ_INSTS_VALU"]),
+                    "issue_frac": psf["SQ_ACTIVE_INST_VALU"] * sf * 4 / (1024 * frame_ms * 1e-3 * 2.4e9),
+                    "source": f"{pm_file} (rocprofv3 --pmc SQ_ACTIVE_INST_VALU), live kernel time"}
+    except Exception:
+        pass
+    achieved = alg_bytes / (frame_ms * 1e-3) / 1e9
+    flops = FLOPS_PER_STREAM_FRAME * B * T / launches / (frame_ms * 1e-3) / 1e12
+    # SURVEY.md 8d: with the per-stream state on chip this kernel is bound by the fp32 vector pipe (117 flop per
+    # algorithmic byte against a machine balance of 20), so that is the roof `frac` is taken against; the HBM
+    # figures (algorithmic bytes per launch against 8 TB/s, counter traffic) ride beside it.
+    return {"bound": "valu", "achieved": flops, "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": flops / VALU_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
+            "kernel": "rn_frame_kernel", "kernel_ms": frame_ms, "launches_per_step": launches,
+            "enqueue_ms": total_ms,
+            "alg_flops_per_launch": FLOPS_PER_STREAM_FRAME * B * T / launches,
+            "alg_bytes_per_launch": alg_bytes, "valu": valu,
+            "hbm": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                    "traffic_over_algorithmic": (traffic / alg_bytes) if traffic else None}}
+
+
 def cfg2(args):
     rank, local_rank, world = _dist_env()
     numa = _bind_numa(local_rank, world)
@@ -1056,77 +1162,47 @@ def cfg2(args):
     per_rank_ms = _gather_ms(dist, dt * 1e3, dev)
     # max time over ranks, frames summed over ranks (two tiny RCCL all-reduces)
     dt, frames_total = reduce_job_stats(dt, B * T * args.steps, device=dev)
+    if args.dump_outputs and rank == 0:
+        if args.host_fed:
+            dump_outputs(args.dump_outputs, h_out, B, T, vad=h_vad)
+        else:
+            dump_outputs(args.dump_outputs, d_out, B, T)
 
-    # dominant-kernel duration, measured live with hipEvents on the launch stream
-    ds.set_timing(True)
-    k_ms = []
-    for _ in range(3):
-        step()
-        ds.synchronize()
-        k_ms.append(ds.last_kernel_ms())
-    ds.set_timing(False)
-    # A sustained figure beside the driver-timed burst (20 steps = 0.12 s): the same step for `--sustain-seconds` of wall
-    # time (default 5), clock sampled by a side thread.  Synchronised every 50 steps so that the host cannot run ahead.
-    sustained = None
-    if args.sustain_seconds > 0 and not args.host_fed:
-        with _ClockSampler(local_rank) as clk:
-            n_sus = 0
-            t0s = time.perf_counter()
-            while time.perf_counter() - t0s < args.sustain_seconds:
-                for _ in range(50):
-                    step()
-                ds.synchronize()
-                n_sus += 50
-            dts = time.perf_counter() - t0s
-        sustained = {"seconds": dts, "steps": n_sus, "ms_per_step": dts / n_sus * 1e3,
-                     "value": B * T * n_sus / dts / 100.0, "unit": "concurrent real-time 48 kHz streams (this rank)",
-                     "sclk_mhz_mean": clk.mean(), "sclk_samples": len(clk.samples),
-                     "sclk_source": (clk.path + " (matched by PCI address)") if clk.by_pci else
-                                    ("highest of " + str(len(clk.paths)) + " pp_dpm_sclk files" if clk.paths else "no pp_dpm_sclk in sysfs")}
-    from crispy_amd import _native as N
-    # rn_frame_kernel launches per step (a call starts with short launches of 3 and 8 frames, then 12 per launch);
-    # per-launch figures below are averages over them: algorithmic bytes of a step / launches, kernel time / launches
-    launches = N.lib().crispy_rn_n_launches(T)
-    frame_ms = sum(k[0] for k in k_ms) / len(k_ms) / launches
-    total_ms = sum(k[1] for k in k_ms) / len(k_ms)
+    k_ms, sustained = None, None
+    if args.full:
+        # dominant-kernel duration, measured live with hipEvents on the launch stream
+        ds.set_timing(True)
+        k_ms = []
+        for _ in range(3):
+            step()
+            ds.synchronize()
+            k_ms.append(ds.last_kernel_ms())
+        ds.set_timing(False)
+        # A sustained figure beside the driver-timed burst (20 steps = 0.12 s): the same step for `--sustain-seconds` of
+        # wall time (default 5), clock sampled by a side thread.  Synchronised every 50 steps so that the host cannot run
+        # ahead.
+        if args.sustain_seconds > 0 and not args.host_fed:
+            with _ClockSampler(local_rank) as clk:
+                n_sus = 0
+                t0s = time.perf_counter()
+                while time.perf_counter() - t0s < args.sustain_seconds:
+                    for _ in range(50):
+                        step()
+                    ds.synchronize()
+                    n_sus += 50
+                dts = time.perf_counter() - t0s
+            sustained = {"seconds": dts, "steps": n_sus, "ms_per_step": dts / n_sus * 1e3,
+                         "value": B * T * n_sus / dts / 100.0, "unit": "concurrent real-time 48 kHz streams (this rank)",
+                         "sclk_mhz_mean": clk.mean(), "sclk_samples": len(clk.samples),
+                         "sclk_source": (clk.path + " (matched by PCI address)") if clk.by_pci else
+                                        ("highest of " + str(len(clk.paths)) + " pp_dpm_sclk files" if clk.paths
+                                         else "no pp_dpm_sclk in sysfs")}
     if args.host_fed:
         d_out.copy_(torch.from_numpy(h_out))
     finite = bool(torch.isfinite(d_out).all().item())
 
     fps = frames_total / dt
     if rank == 0:
-        alg_bytes = BYTES_PER_STREAM_FRAME * B * T / launches
-        # HBM traffic per launch: measured live on this box by two rocprofv3 --pmc child passes (measure_traffic);
-        # if that is not possible the committed passes of the same launch shape are quoted and labelled as such.
-        traffic = None
-        traffic_src = None
-        valu = None
-        if world == 1 and not args.no_live_traffic:
-            try:
-                tr = measure_traffic(B, T)
-                traffic = int((tr["fetch_bytes"] + tr["write_bytes"]) * B * T / launches)
-                traffic_src = {"how": "live: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) over "
-                                      "`bench.py --pmc-child` on this box; FETCH_SIZE x2 (gfx950), KiB -> bytes",
-                               "fetch_bytes_per_stream_frame": tr["fetch_bytes"],
-                               "write_bytes_per_stream_frame": tr["write_bytes"]}
-            except Exception as e:
-                traffic_src = {"how": "committed profile (live measurement failed)", "error": str(e)[:200]}
-        try:
-            pm_file, streams, psf = committed_pmc()
-            if streams == B:
-                sf = B * T / launches                        # stream-frames per (average) launch
-                if traffic is None:
-                    traffic = int((2 * psf["FETCH_SIZE"] + psf["WRITE_SIZE"]) * 1024 * sf)
-                    traffic_src = dict(traffic_src or {}, file=pm_file)
-                # what actually bounds this kernel: VALU issue slots.  SQ_ACTIVE_INST_VALU counts 4-cycle issue
-                # slots; 1024 SIMDs; priced against the live kernel time at the 2.4 GHz peak clock.
-                valu = {"insts_per_stream_frame": round(psf["SQ_INSTS_VALU"]),
-                        "issue_frac": psf["SQ_ACTIVE_INST_VALU"] * sf * 4 / (1024 * frame_ms * 1e-3 * 2.4e9),
-                        "source": f"{pm_file} (rocprofv3 --pmc SQ_ACTIVE_INST_VALU), live kernel time"}
-        except Exception:
-            pass
-        achieved = alg_bytes / (frame_ms * 1e-3) / 1e9
-        flops = FLOPS_PER_STREAM_FRAME * B * T / launches / (frame_ms * 1e-3) / 1e12
         line = {
             "metric": "concurrent real-time 48 kHz streams/GPU (RNNoise)"
                       + (" -- HOST-FED flavour: PCIe copies inside the timed region, not the headline" if args.host_fed else ""),
@@ -1143,28 +1219,18 @@ def cfg2(args):
                                    + (", fed from page-locked host memory through crispy_rn_process" if args.host_fed else ""),
                        "streams_per_gpu": B, "frames_per_step": T, "sharding": f"streams x{world_reported}, no collective",
                        "frames_per_s": fps, "output_finite": finite},
-            # with the per-stream state on chip this kernel is bound by the fp32 vector pipe (117 flop per
-            # algorithmic byte against a machine balance of 20), so that is the roof `frac` is taken against; the HBM
-            # figures (algorithmic bytes per launch against 8 TB/s, counter traffic) ride beside it.
-            "roofline": {"bound": "valu", "achieved": flops, "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": flops / VALU_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": "rn_frame_kernel", "kernel_ms": frame_ms, "launches_per_step": launches,
-                         "enqueue_ms": total_ms,
-                         "alg_flops_per_launch": FLOPS_PER_STREAM_FRAME * B * T / launches,
-                         "alg_bytes_per_launch": alg_bytes, "valu": valu,
-                         "hbm": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                 "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                                 "traffic_over_algorithmic": (traffic / alg_bytes) if traffic else None}},
-            "sustained": sustained,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            line["roofline"] = cfg2_roofline(args, B, T, world, k_ms)
+            line["sustained"] = sustained
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
-        if world == 1 and not args.host_fed and not args.no_host_fed:
+        if args.full and world == 1 and not args.host_fed and not args.no_host_fed:
             try:
                 line["host_fed"] = host_fed_leg(ds, d_in, B, T)
             except Exception as e:     # a reported extra, never a reason to lose the headline
                 line["host_fed"] = {"error": str(e)[:300]}
-        if world == 1 and not args.no_latency:
+        if args.full and world == 1 and not args.no_latency:
             # the literal drop-in: ONE stream, ONE frame per call, host slices (audio.rs:260-268), from a C program
             # compiled against include/crispy_hip.h; a child process, timed call by call
             try:
@@ -1174,7 +1240,7 @@ def cfg2(args):
                 line["latency_us"] = c_dropin.run(lat_w, x1, timed_calls=10000)[2]
             except Exception as e:     # a reported extra, never a reason to lose the headline
                 line["latency_us"] = {"error": str(e)[:300]}
-        if world == 1 and not args.no_asr:
+        if args.full and world == 1 and not args.no_asr:
             del d_in, d_out
             torch.cuda.empty_cache()
             line["asr"] = asr_leg(local_rank, ggml_path=args.ggml)
@@ -1188,7 +1254,7 @@ def cfg2(args):
                                 "value_precision_mode_0": a["rtfx_end_to_end"],
                                 "single_30s_chunk_from_host_ms": a["single_clip"]["f16_operand_mode_ms"],
                                 "model": a["model"]}
-        if world == 1 and not args.no_cfg45:
+        if args.full and world == 1 and not args.no_cfg45:
             # BASELINE configs[3] and configs[4] inside the same run (and so inside the driver's clock around it): one
             # 1024-stream end-to-end step pair and 256-clip Whisper-base steps, each through its own workload function
             import copy

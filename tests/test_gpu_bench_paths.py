@@ -3,12 +3,14 @@
     all-reduces of the job statistics, the per-rank all-gather, and -- cfg 5 -- the all_gather_into_tensor of the token
     ids), which the driver's N = 1 run never enters;
   * the host-fed flavour of cfg 2 (page-locked host buffers through crispy_rn_process);
-  * the cfg 4 workload with two pipelines in flight, against its serial form (same token checksum)."""
+  * the cfg 4 workload with two pipelines in flight, against its serial form (same token checksum);
+  * a plain run: the headline alone, and --dump-outputs writing the same output sample run after run."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +28,8 @@ def _bench(args, env_extra=None, timeout=600):
     return json.loads(last)
 
 
-QUICK = ["--no-asr", "--no-latency", "--no-live-traffic", "--no-cpu-baseline", "--no-cfg45", "--no-host-fed", "--sustain-seconds", "0"]
+# --full: the roofline and host_fed legs these tests read; the --no-... options keep every other leg out
+QUICK = ["--full", "--no-asr", "--no-latency", "--no-live-traffic", "--no-cpu-baseline", "--no-cfg45", "--no-host-fed", "--sustain-seconds", "0"]
 
 
 def test_cfg2_through_rccl_with_one_rank():
@@ -53,11 +56,18 @@ def test_cfg5_gathers_the_token_ids_over_rccl():
     assert t["checksum"] == solo["transcript_ids"]["checksum"] and t["rank0_first_clip"] == solo["transcript_ids"]["rank0_first_clip"]
 
 
-def test_cfg2_host_fed_flavour():
-    line = _bench(["--steps", "2", "--warmup", "1", "--host-fed", "--streams", "1024", "--frames", "50", *QUICK])
+def test_cfg2_host_fed_flavour(tmp_path):
+    import bench
+    line = _bench(["--steps", "2", "--warmup", "1", "--host-fed", "--streams", "1024", "--frames", "50",
+                   "--dump-outputs", str(tmp_path), *QUICK])
     assert "HOST-FED" in line["metric"] and "host-resident" in line["data"]
     assert line["config"]["output_finite"] and line["value"] > 8000
-    # ... and as a leg of the default line: f32 and int16 sample transport beside the HBM-resident value
+    # what the host-fed call hands back: samples and VAD probabilities of the dump_selection sample
+    f0, idx = bench.dump_selection(1024, 50)
+    out, vad = np.load(tmp_path / "denoised.npy"), np.load(tmp_path / "vad.npy")
+    assert out.shape == (50 - f0, idx.size, 480) and vad.shape == (50 - f0, idx.size)
+    assert out.dtype == vad.dtype == np.float32 and np.isfinite(out).all() and 0 <= vad.min() and vad.max() <= 1
+    # ... and as a leg of the --full line: f32 and int16 sample transport beside the HBM-resident value
     quick = [a for a in QUICK if a != "--no-host-fed"]
     line = _bench(["--steps", "2", "--warmup", "1", *quick])
     hf = line["host_fed"]
@@ -77,3 +87,18 @@ def test_cfg4_two_pipelines_in_flight_equal_the_serial_form():
         assert line["config"]["new_tokens"] == 8 and line["config"]["precision_mode"] == 1 and line["value"] > 500
     assert piped["config"]["tokens_checksum"] == serial["config"]["tokens_checksum"]
     assert set(piped["config"]["serial_stage_ms"]) == {"denoise", "resample", "logmel", "encoder", "decode"}
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_the_same_outputs(tmp_path):
+    import bench
+    args = ["--steps", "3", "--warmup", "1", "--streams", "1024", "--frames", "50"]
+    lines = [_bench([*args, "--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    for line in lines:
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 8000
+        assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["config"]["output_finite"]
+        assert not {"roofline", "sustained", "cpu_baseline", "host_fed", "latency_us", "asr", "cfg4", "cfg5"} & set(line)
+    f0, idx = bench.dump_selection(1024, 50)
+    a, b = (np.load(tmp_path / d / "denoised.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (50 - f0, idx.size, 480) and a.nbytes <= 64e6
+    assert np.isfinite(a).all() and np.abs(a).max() > 1.0
+    assert np.array_equal(a, b)              # seeded inputs, same arguments: the same outputs

@@ -16,5 +16,5 @@ for b in 1 64; do
 done
 B=64 PREC=1 rocprofv3 --kernel-trace --output-format csv -d $out/r05_enc -- python3 tools/prof_encode.py > /dev/null 2>&1
 python3 tools/enc_timeline.py $out/r05_enc > $out/r05_asr_encoder_timeline.txt 2>&1
-python3 bench.py > $out/r05_bench_line.json 2> $out/r05_bench.err
+python3 bench.py --full > $out/r05_bench_line.json 2> $out/r05_bench.err
 tail -c 1500 $out/r05_bench_line.json

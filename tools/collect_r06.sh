@@ -8,7 +8,7 @@ part=${1:-a}
 if [ "$part" = a ]; then
   step 900 r06_collect.log tools/collect_profiles.sh r06
   BS=1024,2048,4096,8192,16384 T=100 step 300 r06_sweep.txt python3 tools/sweep_streams.py
-  step 600 r06_bench.err python3 bench.py
+  step 600 r06_bench.err python3 bench.py --full
   grep '^{"metric"' $GO/r06_bench.err | tail -n 1 > $GO/r06_bench_line.json
   tail -c 600 $GO/r06_bench_line.json
 else

@@ -3,7 +3,7 @@
 source "$(dirname "$0")/gpu_steps.sh"
 rm -f $GO/c13_*.log
 echo skip tests
-step 400 c13_bench.log python bench.py --no-cpu-baseline --no-host-fed --no-latency --no-cfg45 --no-live-traffic --sustain-seconds 0
+step 400 c13_bench.log python bench.py --full --no-cpu-baseline --no-host-fed --no-latency --no-cfg45 --no-live-traffic --sustain-seconds 0
 
 python - <<'P'
 import json

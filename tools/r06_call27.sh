@@ -1,6 +1,6 @@
 #!/bin/bash
 source "$(dirname "$0")/gpu_steps.sh"
-step 600 r06_bench.err python3 bench.py
+step 600 r06_bench.err python3 bench.py --full
 grep '^{"metric"' $GO/r06_bench.err | tail -n 1 > $GO/r06_bench_line.json
 python3 - <<'P'
 import json

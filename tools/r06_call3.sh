@@ -5,7 +5,7 @@ rm -f gpurun_out/c3_*.log
 step 600 c3_tests_a.log python -m pytest tests/test_gpu_recording.py tests/test_gpu_fused_decode.py -x -q -m gpu -s
 step 600 c3_tests_b.log python -m pytest tests/test_gpu_resident.py tests/test_gpu_decision.py -x -q -m gpu -s
 step 600 c3_tests_c.log python -m pytest tests/test_gpu_rnnoise.py -x -q -m gpu -s -k "mixed_batch or sampled_oracle or int16"
-step 300 c3_hostfed.log python bench.py --steps 5 --no-asr --no-latency --no-live-traffic --no-cpu-baseline --no-cfg45 --sustain-seconds 0
+step 300 c3_hostfed.log python bench.py --full --steps 5 --no-asr --no-latency --no-live-traffic --no-cpu-baseline --no-cfg45 --sustain-seconds 0
 cd /tmp
 for cfg in "tiny 512" "base 256" "tiny 64"; do set -- $cfg
   MODEL=$1 B=$2 PREC=1 step 200 c3_prof.log rocprofv3 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/c3_dec_$1_$2 -- python3 $GRAFT_REPO_ROOT/tools/prof_decode.py

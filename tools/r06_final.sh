@@ -10,6 +10,6 @@ f=$(find $GO/r06_trace3 -name "*kernel_stats.csv" | head -n 1)
 [ -n "$f" ] && cp "$f" $GO/r06_bench_kernel_stats.csv
 python3 tools/dec_breakdown.py $GO/r06_ladder2 < /dev/null > $GO/r06_asr_batch_ladder_breakdown.txt 2>&1
 find $GO/r06_trace3 $GO/r06_ladder2 -name "*.csv" -size +512k -delete
-step 600 r06_bench.err python3 bench.py
+step 600 r06_bench.err python3 bench.py --full
 grep '^{"metric"' $GO/r06_bench.err | tail -n 1 > $GO/r06_bench_line.json
 head -n 6 $GO/r06_bench_kernel_stats.csv | cut -c1-200; head -n 5 $GO/r06_asr_batch_ladder_breakdown.txt | cut -c1-160; tail -c 300 $GO/r06_bench_line.json
