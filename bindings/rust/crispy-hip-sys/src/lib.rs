@@ -33,7 +33,7 @@ pub const CRISPY_RN_FRAME_SIZE: usize = 480;
 pub const CRISPY_RN_WEIGHT_BYTES: usize = 87503;
 pub const CRISPY_RN_TAPS: usize = 72;
 /// The ABI this file was written against (crispy_hip.h: CRISPY_ABI_VERSION); every constructor checks it.
-pub const CRISPY_ABI_VERSION: c_int = 4;
+pub const CRISPY_ABI_VERSION: c_int = 5;
 pub const CRISPY_MEL_FRAMES: usize = 3000;
 pub const CRISPY_MEL_BINS: usize = 201;
 
@@ -114,6 +114,11 @@ pub struct crispy_asr_opts {
     pub n_initial_prompt: c_int,
     pub carry_context: c_int,
     pub beam_size: c_int,
+    /// ABI 5: word-level timestamps from cross-attention alignment (openai-whisper's word_timestamps, whisper.cpp's
+    /// dtw_token_timestamps); `dtw_heads` = (layer, head) pairs, NULL = every head of the last half of the layers.
+    pub dtw_token_timestamps: c_int,
+    pub dtw_heads: *const c_int,
+    pub n_dtw_heads: c_int,
 }
 impl Default for crispy_asr_opts {
     /// All zero / NULL = `TranscribeOptions::default()` (a raw pointer has no derived Default).
@@ -156,6 +161,22 @@ pub struct crispy_asr_result {
     pub segments: *const crispy_asr_segment,
     pub n_windows: c_int,
     pub windows: *const crispy_asr_window,
+    /// ABI 5 (NULL / 0 unless `dtw_token_timestamps`): a start time per token (-1 for timestamp tokens) and the words,
+    /// `words` pointing at `n_words` `crispy_asr_word`s.
+    pub token_t_dtw: *const c_float,
+    pub n_words: c_int,
+    pub words: *const c_void,
+}
+
+/// One word of a result (`dtw_token_timestamps`): seconds from the start of the chunk, index of its first token.
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct crispy_asr_word {
+    pub t0: c_float,
+    pub t1: c_float,
+    pub text: *const c_char,
+    pub first_token: c_int,
+    pub n_tokens: c_int,
 }
 
 /// `crispy_asr_progress_fn`: called after every group of chunks with (samples done, samples total, user).
@@ -222,6 +243,8 @@ extern "C" {
     pub fn crispy_asr_transcribe(h: *mut crispy_asr, pcm16k: *const c_float, n: usize, opts: *const crispy_asr_opts, out: *mut *mut crispy_asr_result) -> c_int;
     pub fn crispy_asr_transcribe_batch(h: *mut crispy_asr, pcm: *const *const c_float, n: *const usize, batch: c_int, opts: *const crispy_asr_opts, results: *mut *mut crispy_asr_result) -> c_int;
     pub fn crispy_asr_free_result(r: *mut crispy_asr_result);
+    pub fn crispy_asr_align_device(h: *mut crispy_asr, d_enc: *const c_float, batch: c_int, tokens: *const c_int, n_tokens: *const c_int, ld_tokens: c_int, n_sot: c_int, n_frames: *const c_int, heads: *const c_int, n_heads: c_int, d_probs: *mut c_float, d_matrix: *mut c_float, jump_times: *mut c_float) -> c_int;
+    pub fn crispy_asr_dtw_device(h: *mut crispy_asr, d_x: *const c_float, n_rows: c_int, n_cols: c_int, ld: c_long, text_idx: *mut c_int, time_idx: *mut c_int, n_path: *mut c_int) -> c_int;
     pub fn crispy_asr_transcribe_recording(h: *mut crispy_asr, pcm16k: *const c_float, n: usize, opts: *const crispy_asr_opts, max_batch: c_int, cancel_flag: *const c_int, progress: crispy_asr_progress_fn, progress_user: *mut c_void, out: *mut *mut crispy_asr_result) -> c_int;
 
     pub fn crispy_resampler_create(device: c_int, out: *mut *mut crispy_resampler) -> c_int;
@@ -405,6 +428,19 @@ pub struct Transcript {
     pub language_token: i32,
     /// Per window of whisper_full's seek loop: temperature accepted, no_speech_prob, avg_logprob, entropy, dropped / failed.
     pub windows: Vec<crispy_asr_window>,
+    /// With `dtw_token_timestamps`: the start of every token in seconds (-1 for timestamp tokens), parallel to `tokens`.
+    pub token_times: Option<Vec<f32>>,
+    /// With `dtw_token_timestamps`: the words, seconds relative to the chunk.
+    pub words: Vec<Word>,
+}
+/// One word of a transcript (`dtw_token_timestamps`).
+#[derive(Debug, Clone, PartialEq)]
+pub struct Word {
+    pub start: f32,
+    pub end: f32,
+    pub text: String,
+    pub first_token: i32,
+    pub n_tokens: i32,
 }
 
 /// `transcribe_rs::whisper_cpp::WhisperEngine`: `load(&path)` + `transcribe(&audio, &TranscribeOptions::default())`.
@@ -453,6 +489,29 @@ impl GpuWhisperEngine {
         let p = if audio.is_empty() { std::ptr::null() } else { audio.as_ptr() };
         check(unsafe { crispy_asr_transcribe(self.h, p, audio.len(), o, &mut r) })?;
         Ok(unsafe { take_result(r) })
+    }
+    /// `TranscriptionManager::transcribe_with_timestamps` (managers/transcription.rs:200-249) with WORD times for the
+    /// diarization path (`format_diarized_text` gives each word to a speaker by its midpoint, managers/diarization.rs:656-700):
+    /// one `(offset + start, offset + end, word)` per word of the chunk, from cross-attention alignment over `heads`
+    /// ((layer, head) pairs of the model; empty = every head of the last half of the decoder layers).  Empty audio or
+    /// blank text gives no words.
+    pub fn transcribe_with_timestamps_words(&mut self, audio: &[f32], chunk_offset_seconds: f32, heads: &[(i32, i32)])
+                                            -> Result<Vec<(f32, f32, String)>, CrispyError> {
+        if audio.is_empty() {
+            return Ok(Vec::new());
+        }
+        let flat: Vec<c_int> = heads.iter().flat_map(|&(l, h)| [l as c_int, h as c_int]).collect();
+        let mut o = crispy_asr_opts::default();
+        o.dtw_token_timestamps = 1;
+        if !flat.is_empty() {
+            o.dtw_heads = flat.as_ptr();
+            o.n_dtw_heads = heads.len() as c_int;
+        }
+        let t = self.transcribe_chunk(audio, Some(&o))?;
+        if t.text.trim().is_empty() {
+            return Ok(Vec::new());
+        }
+        Ok(t.words.into_iter().map(|w| (chunk_offset_seconds + w.start, chunk_offset_seconds + w.end, w.text)).collect())
     }
     /// `run_transcription`'s chunk loop (commands/transcription.rs:249-302, 363-400, 468) over a whole 16 kHz recording in
     /// ONE call: 30 s chunks decoded `max_batch` at a time (0 = 128), chunk texts trimmed and joined with a space.
@@ -515,7 +574,23 @@ unsafe fn take_result(r: *mut crispy_asr_result) -> Transcript {
         None
     };
     let windows = if res.n_windows > 0 { std::slice::from_raw_parts(res.windows, res.n_windows as usize).to_vec() } else { Vec::new() };
-    let out = Transcript { text, segments, tokens, language_token: res.language_token, windows };
+    let token_times = if res.token_t_dtw.is_null() { None } else if res.n_tokens > 0 {
+        Some(std::slice::from_raw_parts(res.token_t_dtw, res.n_tokens as usize).to_vec())
+    } else {
+        Some(Vec::new())
+    };
+    let words = if res.n_words > 0 && !res.words.is_null() {
+        std::slice::from_raw_parts(res.words as *const crispy_asr_word, res.n_words as usize).iter().map(|w| Word {
+            start: w.t0,
+            end: w.t1,
+            text: if w.text.is_null() { String::new() } else { CStr::from_ptr(w.text).to_string_lossy().into_owned() },
+            first_token: w.first_token,
+            n_tokens: w.n_tokens,
+        }).collect()
+    } else {
+        Vec::new()
+    };
+    let out = Transcript { text, segments, tokens, language_token: res.language_token, windows, token_times, words };
     crispy_asr_free_result(r);
     out
 }

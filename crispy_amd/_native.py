@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CRISPY_HIP_LIB") or os.path.join(_HERE, "libcrispy_hip.so")
 
 RN_FRAME = 480
-ABI_VERSION = 4
+ABI_VERSION = 5
 RN_WEIGHT_BYTES = 87503
 RN_TAPS = 72
 RN_DBG_FLOATS = 4304
@@ -41,7 +41,8 @@ ASR_SYMBOLS = ("crispy_asr_create", "crispy_asr_set_tensor", "crispy_asr_finaliz
                "crispy_asr_decode_greedy_lang_device", "crispy_asr_detect_language_device",
                "crispy_asr_transcribe_batch", "crispy_asr_decode_timestamps_device", "crispy_asr_set_precision",
                "crispy_asr_vocab_specials", "crispy_asr_stage_logits_device", "crispy_asr_language_token",
-               "crispy_asr_decode_window_device", "crispy_asr_transcribe_recording")
+               "crispy_asr_decode_window_device", "crispy_asr_transcribe_recording",
+               "crispy_asr_align_device", "crispy_asr_dtw_device")
 RS_SYMBOLS = ("crispy_resampler_create", "crispy_resampler_destroy", "crispy_resampler_out_len",
               "crispy_resampler_process_device", "crispy_resampler_synchronize")
 ALL_SYMBOLS = RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS
@@ -59,7 +60,8 @@ class AsrOpts(C.Structure):
                 ("temperature", C.c_float), ("temperature_inc", C.c_float), ("entropy_thold", C.c_float),
                 ("logprob_thold", C.c_float), ("no_speech_thold", C.c_float), ("best_of", C.c_int),
                 ("suppress_nst", C.c_int), ("initial_prompt", C.POINTER(C.c_int)), ("n_initial_prompt", C.c_int),
-                ("carry_context", C.c_int), ("beam_size", C.c_int)]
+                ("carry_context", C.c_int), ("beam_size", C.c_int),
+                ("dtw_token_timestamps", C.c_int), ("dtw_heads", C.POINTER(C.c_int)), ("n_dtw_heads", C.c_int)]
 
 
 class AsrSegment(C.Structure):
@@ -74,11 +76,17 @@ class AsrWindow(C.Structure):
                 ("avg_logprob", C.c_float), ("entropy", C.c_float)]
 
 
+class AsrWord(C.Structure):
+    """crispy_asr_word"""
+    _fields_ = [("t0", C.c_float), ("t1", C.c_float), ("text", C.c_char_p), ("first_token", C.c_int), ("n_tokens", C.c_int)]
+
+
 class AsrResult(C.Structure):
     """crispy_asr_result"""
     _fields_ = [("text", C.c_char_p), ("tokens", C.POINTER(C.c_int)), ("n_tokens", C.c_int),
                 ("language_token", C.c_int), ("n_segments", C.c_int), ("segments", C.POINTER(AsrSegment)),
-                ("n_windows", C.c_int), ("windows", C.POINTER(AsrWindow))]
+                ("n_windows", C.c_int), ("windows", C.POINTER(AsrWindow)),
+                ("token_t_dtw", C.POINTER(C.c_float)), ("n_words", C.c_int), ("words", C.c_void_p)]
 
 
 ERR_CANCELLED = -7
@@ -196,6 +204,9 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_asr_detect_language_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.crispy_asr_transcribe_tokens.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p,
                                                C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.crispy_asr_align_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.crispy_asr_dtw_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]
     L.crispy_resampler_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.crispy_resampler_destroy.argtypes = [C.c_void_p]
     L.crispy_resampler_destroy.restype = None

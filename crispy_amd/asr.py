@@ -234,6 +234,36 @@ class WhisperModel:
                                                         n.ctypes.data))
         return toks, tids, plog, nosp, n
 
+    def align_device(self, d_enc: int, rows, n_sot: int, n_frames, heads=None, d_probs: int = 0, d_matrix: int = 0,
+                     ld_tokens: int = 0):
+        """`crispy_asr_align_device`: rows = one token list per clip (sot sequence, <|notimestamps|>, text, <|endoftext|>),
+        d_enc = their encoder outputs; heads = [(layer, head)] or None.  Optional device outputs d_probs [batch][n_heads]
+        [ld_tokens][n_audio_ctx] and d_matrix [batch][ld_tokens][n_audio_ctx] (f32).  Returns jump_times [batch][ld_tokens]
+        (seconds; entries 0 .. len(row) - n_sot - 2 are set)."""
+        b = len(rows)
+        ld = int(ld_tokens) or max(len(r) for r in rows)
+        tok = np.zeros((b, ld), np.int32)
+        for i, r in enumerate(rows):
+            tok[i, :len(r)] = r
+        n_tok = np.array([len(r) for r in rows], np.int32)
+        nf = np.ascontiguousarray(n_frames, dtype=np.int32)
+        hv = np.array([v for lh in heads for v in lh], np.int32) if heads else None
+        jt = np.full((b, ld), np.nan, np.float32)
+        self._ck(self._L.crispy_asr_align_device(self._h, C.c_void_p(d_enc), b, tok.ctypes.data, n_tok.ctypes.data, ld, int(n_sot),
+                                                 nf.ctypes.data, hv.ctypes.data if hv is not None else None,
+                                                 len(heads) if heads else 0, C.c_void_p(d_probs or None),
+                                                 C.c_void_p(d_matrix or None), jt.ctypes.data))
+        return jt
+
+    def dtw_device(self, d_x: int, n_rows: int, n_cols: int, ld: int):
+        """`crispy_asr_dtw_device` on a device f32 cost matrix -> (text_indices, time_indices) of the warping path."""
+        ti = np.zeros(n_rows + n_cols, np.int32)
+        tj = np.zeros(n_rows + n_cols, np.int32)
+        n = C.c_int()
+        self._ck(self._L.crispy_asr_dtw_device(self._h, C.c_void_p(d_x), int(n_rows), int(n_cols), int(ld), ti.ctypes.data,
+                                               tj.ctypes.data, C.byref(n)))
+        return ti[:n.value].copy(), tj[:n.value].copy()
+
     def transcribe_tokens(self, clips, prompt, max_new: int):
         """`SpeechModel::transcribe` up to token ids for a batch of <= 30 s clips."""
         if len(clips) == 0:
@@ -276,7 +306,8 @@ class WhisperEngine(WhisperModel):
         language_token = 0 auto-detects, as `TranscribeOptions::default()` does.  timestamps = True is whisper.cpp's
         default decoding mode (timestamp tokens, seek loop); its segments are kept in `self.last_segments` as
         (t0 seconds, t1 seconds, text), what whisper_full decided per window in `self.last_windows` (dicts of the
-        `crispy_asr_window` fields).  prev_text = True: from the second window of the seek loop on, the decoder is
+        `crispy_asr_window` fields); with dtw=True the token start times and words of the alignment in
+        `self.last_token_times` / `self.last_words` (_read_alignment).  prev_text = True: from the second window of the seek loop on, the decoder is
         conditioned on the text so far (whisper.cpp's prompt_past).  decision: temperature, temperature_inc,
         entropy_thold, logprob_thold, no_speech_thold, best_of (0 / absent = whisper.cpp's default; fallback=False is
         shorthand for temperature_inc = -1: one greedy pass per window)."""
@@ -287,6 +318,7 @@ class WhisperEngine(WhisperModel):
                                               C.byref(res)))
         try:
             text, tokens, self.last_language_token, self.last_segments, self.last_windows = _read_result(res)
+            self.last_token_times, self.last_words = _read_alignment(res)
         finally:
             self._L.crispy_asr_free_result(res)
         return text, tokens
@@ -301,9 +333,10 @@ class WhisperEngine(WhisperModel):
 
 def make_opts(language_token=0, translate=False, max_new_tokens=0, timestamps=False, prev_text=True, fallback=True,
               temperature=0.0, temperature_inc=0.0, entropy_thold=0.0, logprob_thold=0.0, no_speech_thold=0.0, best_of=0,
-              suppress_nst=False, initial_prompt=None, carry_context=False, beam_size=0):
+              suppress_nst=False, initial_prompt=None, carry_context=False, beam_size=0, dtw=False, dtw_heads=None):
     """`crispy_asr_opts`; the decision fields read "0 = whisper.cpp's default" (include/crispy_hip.h).  The struct keeps a
-    reference to the initial-prompt array (`_keep`) for as long as it lives."""
+    reference to the initial-prompt and alignment-head arrays (`_keep`, `_keep_heads`) for as long as it lives.
+    dtw: word-level timestamps (`dtw_token_timestamps`); dtw_heads: [(layer, head), ...], None = the default set."""
     if not fallback and temperature_inc == 0.0:
         temperature_inc = -1.0
     o = N.AsrOpts(int(language_token), int(translate), int(max_new_tokens), 0 if timestamps else 1, 0 if prev_text else 1,
@@ -317,6 +350,13 @@ def make_opts(language_token=0, translate=False, max_new_tokens=0, timestamps=Fa
         o.n_initial_prompt = len(initial_prompt)
     o.carry_context = 1 if carry_context else 0
     o.beam_size = int(beam_size)
+    o.dtw_token_timestamps = 1 if dtw else 0
+    if dtw_heads is not None and len(dtw_heads):
+        flat = [int(v) for lh in dtw_heads for v in lh]
+        arr = (C.c_int * len(flat))(*flat)
+        o._keep_heads = arr
+        o.dtw_heads = C.cast(arr, C.POINTER(C.c_int))
+        o.n_dtw_heads = len(dtw_heads)
     return o
 
 
@@ -330,10 +370,24 @@ def _read_result(res) -> tuple:
     return text, tokens, int(r.language_token), segs, wins
 
 
+def _read_alignment(res) -> tuple:
+    """The ABI-5 fields of a result: (token start times or None, [(t0, t1, word, first_token, n_tokens)])."""
+    r = C.cast(res, C.POINTER(N.AsrResult)).contents
+    times = [float(r.token_t_dtw[i]) for i in range(r.n_tokens)] if r.token_t_dtw else None
+    words = []
+    if r.n_words:
+        w = C.cast(r.words, C.POINTER(N.AsrWord))
+        words = [(float(w[i].t0), float(w[i].t1), (w[i].text or b"").decode("utf-8", "replace"), int(w[i].first_token),
+                  int(w[i].n_tokens)) for i in range(r.n_words)]
+    return times, words
+
+
 def transcribe_batch(engine: "WhisperEngine", clips, max_new_tokens: int = 0, language_token: int = 0,
-                     timestamps: bool = False, with_segments: bool = False, prev_text: bool = True, **decision):
+                     timestamps: bool = False, with_segments: bool = False, prev_text: bool = True, with_words: bool = False,
+                     **decision):
     """`crispy_asr_transcribe_batch`: a list of chunks (each <= 30 s, empty allowed) -> [(text, tokens, language)]
-    (+ segments and window decisions with with_segments)."""
+    (+ segments and window decisions with with_segments; + token times and words, `_read_alignment`, with with_words --
+    pass dtw=True for them)."""
     arrs = [np.ascontiguousarray(c, dtype=np.float32).ravel() for c in clips]
     nb = len(arrs)
     ptrs = (C.c_void_p * max(nb, 1))(*[a.ctypes.data if a.size else None for a in arrs])
@@ -346,7 +400,8 @@ def transcribe_batch(engine: "WhisperEngine", clips, max_new_tokens: int = 0, la
         r = C.c_void_p(res[i])
         try:
             full = _read_result(r)
-            out.append(full if with_segments else full[:3])
+            full = full if with_segments else full[:3]
+            out.append(full + _read_alignment(r) if with_words else full)
         finally:
             engine._L.crispy_asr_free_result(r)
     return out
@@ -372,12 +427,14 @@ class Cancelled(Exception):
 
 
 def transcribe_recording(engine: "WhisperEngine", pcm16k: np.ndarray, max_new_tokens: int = 0, timestamps: bool = False,
-                         max_batch: int = 0, cancel=None, progress=None, with_result: bool = False, **decision):
+                         max_batch: int = 0, cancel=None, progress=None, with_result: bool = False, with_words: bool = False,
+                         **decision):
     """`crispy_asr_transcribe_recording`: the same chunk loop with the chunks decoded side by side, `max_batch` (0 = 128) per
     engine call -- an hour of audio is one call instead of 120 -- and the reference's two hooks:
     cancel: a `ctypes.c_int` another thread (or the progress callback) sets non-zero -> raises `Cancelled`;
     progress: callable (samples_done, samples_total), called after every group of chunks (transcription.rs:285-299).
-    Returns the text; with_result also (text, tokens, language, segments, windows) of the whole recording."""
+    Returns the text; with_result also (text, tokens, language, segments, windows) of the whole recording (with_words:
+    + token times and words, `_read_alignment`; pass dtw=True for them)."""
     x = np.ascontiguousarray(pcm16k, dtype=np.float32).ravel()
     opts = make_opts(0, False, max_new_tokens, timestamps, True, **decision)
     res = C.c_void_p()
@@ -389,20 +446,31 @@ def transcribe_recording(engine: "WhisperEngine", pcm16k: np.ndarray, max_new_to
     engine._ck(rc)
     try:
         full = _read_result(res)
+        if with_words:
+            full = full + _read_alignment(res)
     finally:
         engine._L.crispy_asr_free_result(res)
     return full if with_result else full[0]
 
 
 def transcribe_with_timestamps(engine: "WhisperEngine", audio: np.ndarray, chunk_offset_seconds: float,
-                               max_new_tokens: int = 0, use_segments: bool = False):
+                               max_new_tokens: int = 0, use_segments: bool = False, words: bool = False, dtw_heads=None):
     """`TranscriptionManager::transcribe_with_timestamps` (managers/transcription.rs:200-249): empty audio or empty
     trimmed text -> []; with segments from the engine (use_segments, :223-240) every non-blank segment shifted by
     the chunk offset, text untrimmed; otherwise (:242-248, what the reference reports for Whisper) one segment
-    spanning the chunk, (offset, offset + len/16000, trimmed text)."""
+    spanning the chunk, (offset, offset + len/16000, trimmed text).
+    words=True: the engine's word-level timestamps (dtw_token_timestamps, alignment heads `dtw_heads`) -- one
+    (offset + t0, offset + t1, word) per word, what `format_diarized_text` (managers/diarization.rs:656-700) gives to a
+    speaker by its midpoint."""
     a = np.ascontiguousarray(audio, dtype=np.float32).ravel()
     if a.size == 0:
         return []
+    if words:
+        text, _ = engine.transcribe(a, max_new_tokens, timestamps=True, dtw=True, dtw_heads=dtw_heads)
+        if not text.strip():
+            return []
+        off = float(chunk_offset_seconds)
+        return [(off + t0, off + t1, w) for t0, t1, w, _f, _n in engine.last_words]
     text, _ = engine.transcribe(a, max_new_tokens, timestamps=use_segments)
     text = text.strip()
     if not text:

@@ -438,6 +438,15 @@ int layer_cross_and_mlp(StepCtx& c, size_t l) {
     if (qrc != CRISPY_OK) return qrc;
     HIP_TRY(gemm_f32_nt(gemm(h->d_dxn, dt, xq_w, dt, h->d_dq, dt, L.xq_b, batch, dt, dt), 1, s));
   }
+  if (h->align.on && l < h->align.slot.size() && h->align.slot[l] >= 0) {
+    // word alignment pass (whisper_align.hip): keep the cross q of rows (clip, pos .. pos + P - 1) -- what the attention
+    // below reads -- at [slot][clip][pos + j]
+    AlignWs& A = h->align;
+    if (c.dev_pos || c.pos + c.P > A.rows) return fail(CRISPY_ERR_INVALID_ARG, "alignment pass: rows out of range");
+    float* dst = A.q + (((size_t)A.slot[l] * c.clips) * A.rows + c.pos) * dt;
+    HIP_TRY(hipMemcpy2DAsync(dst, (size_t)A.rows * dt * sizeof(float), h->d_dq, (size_t)c.P * dt * sizeof(float),
+                             (size_t)c.P * dt * sizeof(float), (size_t)c.clips, hipMemcpyDeviceToDevice, s));
+  }
   if (h->enc_precision == 1)
     HIP_TRY(attn_decoder_kv16(h->d_dq, dt, reinterpret_cast<const char*>(h->d_xkv_h) + l * c.xclips * Tn * 2 * dt * 2,
                               (long)Tn * 2 * dt, 64, 64L * Tn, 0, (long)Tn * dt, Tn, nullptr, h->d_datt, dt, batch, c.H, s, 0,

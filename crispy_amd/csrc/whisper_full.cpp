@@ -24,9 +24,16 @@ struct crispy_asr_result_impl {
   std::vector<float> seg_t0, seg_t1;
   std::vector<crispy_asr_segment> segs;
   std::vector<crispy_asr_window> wins;
+  // opts.dtw_token_timestamps: a time per token (-1 for timestamp tokens), the words
+  bool dtw = false;
+  std::vector<float> tok_t;
+  std::vector<std::string> word_text;
+  std::vector<crispy_asr_word> words;      // text pointers filled in by publish
 };
 
 }  // namespace
+
+AlignRoundFn g_align_round = nullptr;
 
 // whisper.cpp's always-suppressed specials (whisper_process_logits [UPSTREAM-RECALL]): sot, nosp, translate,
 // transcribe, prev, solm, every language token; suppress_blank adds " " and EOT at the first position.
@@ -176,6 +183,145 @@ void publish(crispy_asr_result_impl* r) {
   r->pub.segments = r->segs.empty() ? nullptr : r->segs.data();
   r->pub.n_windows = (int)r->wins.size();
   r->pub.windows = r->wins.empty() ? nullptr : r->wins.data();
+  for (size_t i = 0; i < r->words.size(); ++i) r->words[i].text = r->word_text[i].c_str();
+  r->pub.token_t_dtw = r->dtw ? r->tok_t.data() : nullptr;
+  r->pub.n_words = (int)r->words.size();
+  r->pub.words = r->words.empty() ? nullptr : r->words.data();
+}
+
+// ---- words of one aligned window: openai-whisper's tokenizer.split_to_word_tokens and timing.merge_punctuations ----
+// [UPSTREAM-RECALL: whisper/tokenizer.py, whisper/timing.py; oracle: tests/align_oracle.py]
+struct WordSpan {
+  std::string text;
+  int first = 0, n = 0;          // the window's text tokens [first, first + n)
+  float t0 = 0.f, t1 = 0.f;
+};
+
+// Python's str.isspace for the code points a token can hold (str.strip() in the reference)
+bool py_space(unsigned cp) {
+  return (cp >= 9 && cp <= 13) || (cp >= 0x1C && cp <= 0x20) || cp == 0x85 || cp == 0xA0 || cp == 0x1680 ||
+         (cp >= 0x2000 && cp <= 0x200A) || cp == 0x2028 || cp == 0x2029 || cp == 0x202F || cp == 0x205F || cp == 0x3000;
+}
+
+// length of the UTF-8 sequence at s[i] as Python's decoder accepts it; 0 = not a valid sequence there
+size_t utf8_len(const std::string& s, size_t i) {
+  const unsigned char c = (unsigned char)s[i];
+  auto cont = [&](size_t k, unsigned lo, unsigned hi) {
+    return i + k < s.size() && (unsigned char)s[i + k] >= lo && (unsigned char)s[i + k] <= hi;
+  };
+  if (c < 0x80) return 1;
+  if (c >= 0xC2 && c <= 0xDF) return cont(1, 0x80, 0xBF) ? 2 : 0;
+  if (c >= 0xE0 && c <= 0xEF) {
+    const unsigned lo = c == 0xE0 ? 0xA0 : 0x80, hi = c == 0xED ? 0x9F : 0xBF;
+    return cont(1, lo, hi) && cont(2, 0x80, 0xBF) ? 3 : 0;
+  }
+  if (c >= 0xF0 && c <= 0xF4) {
+    const unsigned lo = c == 0xF0 ? 0x90 : 0x80, hi = c == 0xF4 ? 0x8F : 0xBF;
+    return cont(1, lo, hi) && cont(2, 0x80, 0xBF) && cont(3, 0x80, 0xBF) ? 4 : 0;
+  }
+  return 0;
+}
+
+unsigned utf8_cp(const std::string& s, size_t i, size_t len) {
+  const unsigned char c = (unsigned char)s[i];
+  if (len == 1) return c;
+  unsigned cp = c & (len == 2 ? 0x1Fu : len == 3 ? 0x0Fu : 0x07u);
+  for (size_t k = 1; k < len; ++k) cp = (cp << 6) | ((unsigned char)s[i + k] & 0x3Fu);
+  return cp;
+}
+
+std::string py_strip(const std::string& s) {
+  std::vector<std::pair<size_t, size_t>> cps;           // (offset, length); an invalid byte stands for itself
+  for (size_t i = 0; i < s.size();) {
+    size_t len = utf8_len(s, i);
+    if (len == 0) len = 1;
+    cps.emplace_back(i, len);
+    i += len;
+  }
+  size_t a = 0, b = cps.size();
+  auto sp = [&](size_t k) { return utf8_len(s, cps[k].first) == cps[k].second && py_space(utf8_cp(s, cps[k].first, cps[k].second)); };
+  while (a < b && sp(a)) ++a;
+  while (b > a && sp(b - 1)) --b;
+  if (a == b) return std::string();
+  return s.substr(cps[a].first, cps[b - 1].first + cps[b - 1].second - cps[a].first);
+}
+
+// Python's `x in y` for two strings: a substring test (the empty string is in every string)
+bool py_in(const std::string& x, const char* y) { return std::string(y).find(x) != std::string::npos; }
+
+// split_tokens_on_unicode: tokens are gathered until their bytes end on a character boundary of the window's whole text
+// (a token that ends inside a multi-byte character waits for the rest); then split_tokens_on_spaces: a unit starts a new
+// word when it begins with a space, is punctuation once stripped, or is the first (unicode_only: every unit is a word)
+std::vector<WordSpan> split_words(const std::vector<std::string>& pieces, bool unicode_only) {
+  std::string all;
+  std::vector<size_t> end_at(pieces.size());
+  for (size_t k = 0; k < pieces.size(); ++k) { all += pieces[k]; end_at[k] = all.size(); }
+  std::vector<unsigned char> boundary(all.size() + 1, 0);
+  boundary[0] = 1;
+  for (size_t i = 0; i < all.size();) {
+    size_t len = utf8_len(all, i);
+    if (len == 0) {                  // Python replaces a maximal invalid subpart by one U+FFFD: a truncated sequence is one unit
+      len = 1;
+      const unsigned char c = (unsigned char)all[i];
+      const size_t want = c >= 0xF0 ? 4 : c >= 0xE0 ? 3 : c >= 0xC2 ? 2 : 1;
+      while (len < want && i + len < all.size() && ((unsigned char)all[i + len] & 0xC0) == 0x80 && utf8_len(all, i + len) == 0) ++len;
+    }
+    i += len;
+    boundary[i] = 1;
+  }
+  static const char* const kPunct = "!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~";       // string.punctuation
+  std::vector<WordSpan> words;
+  size_t u0 = 0;
+  std::string unit;
+  for (size_t k = 0; k < pieces.size(); ++k) {
+    unit += pieces[k];
+    if (!boundary[end_at[k]] && k + 1 < pieces.size()) continue;
+    const bool with_space = !unit.empty() && unit[0] == ' ';
+    const bool punct = py_in(py_strip(unit), kPunct);
+    if (unicode_only || with_space || punct || words.empty()) {
+      WordSpan w;
+      w.text = unit; w.first = (int)u0; w.n = (int)(k + 1 - u0);
+      words.push_back(w);
+    } else {
+      words.back().text += unit;
+      words.back().n += (int)(k + 1 - u0);
+    }
+    unit.clear();
+    u0 = k + 1;
+  }
+  return words;
+}
+
+// timing.merge_punctuations with openai's default sets; emptied words are dropped (add_word_timestamps keeps a word only
+// when its text is not empty).  Times stay those of the word they were computed for.
+void merge_punctuations(std::vector<WordSpan>& w) {
+  static const char* const kPrepend = "\"'\xe2\x80\x9c\xc2\xbf([{-";
+  static const char* const kAppend = "\"'.\xe3\x80\x82,\xef\xbc\x8c!\xef\xbc\x81?\xef\xbc\x9f:\xef\xbc\x9a\xe2\x80\x9d)]}\xe3\x80\x81";
+  const int n = (int)w.size();
+  for (int i = n - 2, j = n - 1; i >= 0; --i) {
+    WordSpan &prev = w[i], &next = w[j];
+    if (!prev.text.empty() && prev.text[0] == ' ' && py_in(py_strip(prev.text), kPrepend)) {
+      next.text = prev.text + next.text;
+      if (prev.n > 0) { next.n += prev.n; next.first = prev.first; }
+      prev.text.clear(); prev.n = 0;
+    } else {
+      j = i;
+    }
+  }
+  for (int i = 0, j = 1; j < n; ++j) {
+    WordSpan &prev = w[i], &next = w[j];
+    if (!(!prev.text.empty() && prev.text.back() == ' ') && py_in(next.text, kAppend)) {
+      prev.text += next.text;
+      if (next.n > 0) { if (prev.n == 0) prev.first = next.first; prev.n += next.n; }
+      next.text.clear(); next.n = 0;
+    } else {
+      i = j;
+    }
+  }
+  std::vector<WordSpan> kept;
+  for (auto& x : w)
+    if (!x.text.empty()) kept.push_back(std::move(x));
+  w.swap(kept);
 }
 
 
@@ -223,6 +369,8 @@ struct Accepted {
   float nosp = 0.f, temperature = 0.f;
   int decoder = 0;
   bool have = false;
+  std::vector<int> align;             // dtw_token_timestamps: entry column of <|notimestamps|> and of every text token's row
+  bool aligned = false;
 };
 
 // what one decode of a group of clips (n_dec rows each) returned
@@ -261,6 +409,9 @@ class BatchCall {
   int decode_group(const std::vector<int>& act, const std::vector<int>& grp, float t_cur, int n_dec, GroupPicks& out);
   bool evaluate_clip(int a, int k, int c, float t_cur, bool last_temp, int n_dec, const GroupPicks& g, Accepted& A);
   void finish_window(int k, const Accepted& A);
+  int kept_tokens(const Accepted& A, bool* no_speech) const;
+  void add_words(int k, const Accepted& A, const std::vector<int>& text_at, crispy_asr_result_impl* r) const;
+  int align_round(const std::vector<int>& act, std::vector<Accepted>& acc);
   std::vector<int> build_prompt(int k, int lang_tok, float t_cur) const;
   int reserve_enc_rep(int n_clips);
 
@@ -276,6 +427,8 @@ class BatchCall {
   size_t stride = 1;
   int nb = 0, max_new = 0, n_init = 0;
   bool timestamps = true, detect = false;
+  bool dtw = false;                    // opts.dtw_token_timestamps
+  std::vector<int> dtw_heads;          // (layer, head) pairs; empty = the default set
   // whisper_full's parameters (0 in crispy_asr_opts = whisper.cpp's default)
   float entropy_thold = 2.4f, logprob_thold = -1.0f, no_speech_thold = 0.6f;
   int best_of = 5, beam = 0;
@@ -307,6 +460,18 @@ int BatchCall::check_options() const {
   for (int i = 0; i < opts->n_initial_prompt; ++i)
     if (opts->initial_prompt[i] < 0 || opts->initial_prompt[i] >= h->hp.n_vocab)
       return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_transcribe_batch: initial prompt token %d out of range", opts->initial_prompt[i]);
+  if (opts->dtw_token_timestamps) {
+    if (!timestamps) return fail(CRISPY_ERR_UNSUPPORTED, "crispy_asr_transcribe_batch: dtw_token_timestamps aligns the windows of the seek loop (timestamps on)");
+    if (!g_align_round) return fail(CRISPY_ERR_UNSUPPORTED, "crispy_asr_transcribe_batch: this build has no alignment kernels");
+    if (opts->n_dtw_heads < 0 || (opts->n_dtw_heads > 0 && !opts->dtw_heads) || (opts->dtw_heads && opts->n_dtw_heads == 0))
+      return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_transcribe_batch: dtw_heads is NULL or its count %d wrong", opts->n_dtw_heads);
+    for (int i = 0; i < opts->n_dtw_heads; ++i) {
+      const int l = opts->dtw_heads[2 * i], hd = opts->dtw_heads[2 * i + 1];
+      if (l < 0 || l >= h->hp.n_text_layer || hd < 0 || hd >= h->hp.n_text_head)
+        return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_transcribe_batch: alignment head (%d, %d) outside %d layers x %d heads", l, hd,
+                    h->hp.n_text_layer, h->hp.n_text_head);
+    }
+  }
   return CRISPY_OK;
 }
 
@@ -335,6 +500,9 @@ int BatchCall::prepare() {
   timestamps = !(opts && opts->no_timestamps) && sp.beg + 1501 <= h->hp.n_vocab;
   const int rc = check_options();
   if (rc != CRISPY_OK) return rc;
+  dtw = opts && opts->dtw_token_timestamps;
+  if (dtw && opts->n_dtw_heads > 0) dtw_heads.assign(opts->dtw_heads, opts->dtw_heads + 2 * opts->n_dtw_heads);
+  for (int i = 0; i < batch; ++i) impl[i]->dtw = dtw;
   prompt = {sp.sot};
   if (sp.multilingual) {
     prompt.push_back(opts && opts->language_token > 0 ? opts->language_token : sp.lang0);   // <|en|>
@@ -528,8 +696,9 @@ int BatchCall::seek_loop() {
       if (seek[k] > 0 && seek[k] + 500 >= seek_end[k]) past[k].clear();
     }
     std::vector<Accepted> acc((size_t)na);
-    const int rc = decode_round(act, acc);
+    int rc = decode_round(act, acc);
     if (rc != CRISPY_OK) return rc;
+    if (dtw && (rc = align_round(act, acc)) != CRISPY_OK) return rc;
     for (int a = 0; a < na; ++a) finish_window(act[a], acc[a]);
   }
 }
@@ -659,13 +828,90 @@ bool BatchCall::evaluate_clip(int a, int k, int c, float t_cur, bool last_temp, 
   return success;
 }
 
+// the words of an aligned window (times: the window start + the alignment entry times of its first token and of the
+// token after its last; the <|endoftext|> row closes the last word)
+void BatchCall::add_words(int k, const Accepted& A, const std::vector<int>& text_at, crispy_asr_result_impl* r) const {
+  std::vector<std::string> pieces;
+  for (int i = 0; i < (int)A.toks.size() && pieces.size() < text_at.size(); ++i)
+    if (A.toks[i] < h->eot) pieces.push_back(A.toks[i] < (int)h->vocab.size() ? h->vocab[A.toks[i]] : std::string());
+  // languages written without spaces between words: zh, ja, th, lo, my, yue (their places in Whisper's language list)
+  bool unicode_only = false;
+  for (int i : {1, 7, 30, 77, 87, 99})
+    if (i < sp.n_lang && lang[k] == sp.lang0 + i) unicode_only = true;
+  std::vector<WordSpan> w = split_words(pieces, unicode_only);
+  for (auto& x : w) {
+    x.t0 = (float)(seek[k] * 0.01 + A.align[x.first] * 0.02);
+    x.t1 = (float)(seek[k] * 0.01 + A.align[x.first + x.n] * 0.02);
+  }
+  merge_punctuations(w);
+  for (const auto& x : w) {
+    r->word_text.push_back(x.text);
+    r->words.push_back(crispy_asr_word{x.t0, x.t1, nullptr, text_at[x.first], x.n});
+  }
+}
+
+// tokens of the accepted pass that the window keeps (a decoder that failed before the ranking keeps all its tokens: only
+// ranked sequences are cut to result_len); *no_speech: dropped by the no-speech rule
+int BatchCall::kept_tokens(const Accepted& A, bool* no_speech) const {
+  *no_speech = A.nosp > no_speech_thold && A.d.avg_logprobs < logprob_thold;
+  return A.d.scored ? A.d.result_len : A.d.n;
+}
+
+// dtw_token_timestamps: ONE alignment pass over every clip of the round whose window keeps text -- its tokens as the
+// accepted pass left them (greedy, best-of winner or beam winner), without the conditioning text
+int BatchCall::align_round(const std::vector<int>& act, std::vector<Accepted>& acc) {
+  const int na = (int)act.size();
+  std::vector<int> who, n_frames;
+  std::vector<std::vector<int>> rows;
+  for (int a = 0; a < na; ++a) {
+    const int k = act[a];
+    bool nos = false;
+    const int n_cur = kept_tokens(acc[a], &nos);
+    if (n_cur <= 0 || nos) continue;
+    std::vector<int> row(prompt.begin(), prompt.end());            // the sot sequence (timestamps on: no <|notimestamps|> in it)
+    if (sp.multilingual) row[1] = lang[k];
+    row.push_back(sp.not_);
+    const size_t n0 = row.size();
+    for (int i = 0; i < n_cur; ++i)
+      if (acc[a].toks[i] < h->eot) row.push_back(acc[a].toks[i]);
+    if (row.size() == n0) continue;                                 // no text in the window
+    row.push_back(h->eot);
+    const int nf = std::min(3000, seek_end[k] - seek[k]);
+    // a window the DTW kernel cannot hold (more than ~370 tokens: a caller's max_new_tokens) keeps its transcript and
+    // gets no alignment -- times -1, no words -- rather than failing the call
+    if (!align_dtw_fits((int)(row.size() - n0), nf / 2)) continue;       // rows: <|notimestamps|> + the text
+    who.push_back(a);
+    rows.push_back(std::move(row));
+    n_frames.push_back(nf);
+  }
+  if (who.empty()) return CRISPY_OK;
+  const float* d_enc = h->w_enc;
+  bool contiguous = true;
+  for (size_t c = 0; c < who.size(); ++c) contiguous = contiguous && who[c] == (int)c;
+  if (!contiguous) {
+    const int rc = reserve_enc_rep((int)who.size());
+    if (rc != CRISPY_OK) return rc;
+    for (size_t c = 0; c < who.size(); ++c)
+      HIP_TRY(hipMemcpyAsync(d_enc_rep + c * enc_clip, h->w_enc + (size_t)who[c] * enc_clip, enc_clip * sizeof(float),
+                             hipMemcpyDeviceToDevice, h->stream));
+    d_enc = d_enc_rep;
+  }
+  std::vector<std::vector<int>> idx;
+  const int rc = g_align_round(h, d_enc, rows, n_init, n_frames, dtw_heads, idx);
+  if (rc != CRISPY_OK) return rc;
+  for (size_t c = 0; c < who.size(); ++c) {
+    acc[who[c]].align = std::move(idx[c]);
+    acc[who[c]].aligned = true;
+  }
+  return CRISPY_OK;
+}
+
 // the accepted pass of clip k's window into its result: conditioning text, segments, tokens, the window record, the seek advance
 void BatchCall::finish_window(int k, const Accepted& A) {
   crispy_asr_result_impl* r = impl[live[k]];
   const DecoderPass& d = A.d;
-  // a decoder that failed before the ranking keeps all its tokens (only ranked sequences are cut to result_len)
-  const int n_cur = d.scored ? d.result_len : d.n;
-  const bool is_no_speech = A.nosp > no_speech_thold && d.avg_logprobs < logprob_thold;
+  bool is_no_speech = false;
+  const int n_cur = kept_tokens(A, &is_no_speech);
   {
     std::vector<int> np;
     if (A.prompt.front() == sp.prev) np.assign(A.prompt.begin() + 1, A.prompt.end() - n_init);
@@ -675,8 +921,17 @@ void BatchCall::finish_window(int k, const Accepted& A) {
   int seek_delta = d.seek_delta;
   if (n_cur > 0 && !is_no_speech) {
     window_segments(h, A.toks.data(), A.tids.data(), n_cur, sp.beg, seek[k], seek_delta, r);
+    std::vector<int> text_at;                       // result index of every text token of the window
     for (int i = 0; i < n_cur; ++i)
-      if (A.toks[i] != h->eot) r->tokens.push_back(A.toks[i]);
+      if (A.toks[i] != h->eot) {
+        if (dtw) {
+          const bool text = A.toks[i] < h->eot && A.aligned && text_at.size() < A.align.size();
+          r->tok_t.push_back(text ? (float)(seek[k] * 0.01 + A.align[text_at.size()] * 0.02) : -1.f);
+          if (A.toks[i] < h->eot) text_at.push_back((int)r->tokens.size());
+        }
+        r->tokens.push_back(A.toks[i]);
+      }
+    if (dtw && A.aligned && !text_at.empty() && A.align.size() == text_at.size() + 1) add_words(k, A, text_at, r);
   }
   // a single closing timestamp: nothing is left to say in this chunk [UPSTREAM-RECALL: whisper.cpp PR 2629]
   if (n_cur > 1 && A.toks[n_cur - 2] < sp.beg && A.toks[n_cur - 1] > sp.beg)
@@ -781,6 +1036,7 @@ int crispy_asr_transcribe_recording(crispy_asr* h, const float* pcm16k, size_t n
   const size_t group = max_batch > 0 ? (size_t)max_batch : 128;       // (more than SKINNY_MAX_M are taken in turns by the batch call)
   crispy_asr_result_impl* R = new (std::nothrow) crispy_asr_result_impl();
   if (!R) return fail(CRISPY_ERR_OOM, "crispy_asr_transcribe_recording: host allocation failed");
+  R->dtw = opts && opts->dtw_token_timestamps;
   struct Own { crispy_asr_result_impl* r; ~Own() { delete r; } } own{R};
   bool first_text = true;
   for (size_t g0 = 0; g0 < n_chunks; g0 += group) {
@@ -805,9 +1061,19 @@ int crispy_asr_transcribe_recording(crispy_asr* h, const float* pcm16k, size_t n
         R->text += t;
         first_text = false;
       }
+      const float t_off = (float)(ci * 30.0);              // chunk_start_seconds (transcription.rs:262)
+      const int tok0 = (int)R->tokens.size();
       R->tokens.insert(R->tokens.end(), r.tokens, r.tokens + r.n_tokens);
       if (ci == 0) R->language_token = r.language_token;
-      const float t_off = (float)(ci * 30.0);              // chunk_start_seconds (transcription.rs:262)
+      if (r.token_t_dtw) {
+        R->dtw = true;
+        for (int k = 0; k < r.n_tokens; ++k) R->tok_t.push_back(r.token_t_dtw[k] < 0.f ? r.token_t_dtw[k] : t_off + r.token_t_dtw[k]);
+      }
+      const crispy_asr_word* ws = static_cast<const crispy_asr_word*>(r.words);
+      for (int k = 0; k < r.n_words; ++k) {
+        R->word_text.emplace_back(ws[k].text ? ws[k].text : "");
+        R->words.push_back(crispy_asr_word{t_off + ws[k].t0, t_off + ws[k].t1, nullptr, tok0 + ws[k].first_token, ws[k].n_tokens});
+      }
       for (int k = 0; k < r.n_segments; ++k) {
         R->seg_t0.push_back(t_off + r.segments[k].t0);
         R->seg_t1.push_back(t_off + r.segments[k].t1);

@@ -4,6 +4,8 @@
 //   decode_steps.cpp   the decoder: workspaces, the step forms (fused / matrix-vector / skinny), prompts, captured steps,
 //                      the greedy / timestamp-rule / beam passes over one window
 //   whisper_full.cpp   whisper_full on top of them: seek loop, temperature ladder, segments, results, the recording chunker
+//   whisper_align.hip  word-level timestamps: the alignment pass, its kernels, crispy_asr_{align,dtw}_device (reached from
+//                      whisper_full.cpp through a hook that file installs: not linked, a dtw request is unsupported)
 // Reference surface: transcribe_rs::whisper_cpp::WhisperEngine::{load, transcribe} (src-tauri/src/managers/transcription.rs:138-141,
 // 183-185).
 #pragma once
@@ -67,6 +69,23 @@ struct DecLayer {
   const float *qkv_lw, *qkv_ls, *qkv_lc, *xq_lw, *xq_ls, *xq_lc, *fc1_lw, *fc1_ls, *fc1_lc;
 };
 
+// Word alignment (whisper_align.hip): while an alignment prefill runs (`on`), layer_cross_and_mlp copies the cross-q rows
+// of every layer that holds an alignment head into q [slot][clip][row][n_text_state] -- the rows that layer's own
+// cross-attention reads.  Buffers grow on demand and live as long as the handle.
+struct AlignWs {
+  float* q = nullptr; size_t q_bytes = 0;
+  void* ws = nullptr; size_t ws_bytes = 0;     // row statistics, matrix, DTW outputs, per-clip arguments
+  std::vector<int> slot;                       // [n_text_layer]: the layer's slot in q, -1 = none
+  int rows = 0;                                // token rows per clip of the running pass
+  bool on = false;
+  AlignWs() = default;
+  AlignWs(const AlignWs&) = delete;
+  AlignWs& operator=(const AlignWs&) = delete;
+  ~AlignWs() {
+    if (q) (void)hipFree(q);
+    if (ws) (void)hipFree(ws);
+  }
+};
 
 }  // namespace asr
 }  // namespace crispy
@@ -187,6 +206,7 @@ struct crispy_asr {
   int eot = 50257;
   std::vector<unsigned char> sup_all, sup_first;   // host copies of the two suppression lists
   std::vector<std::string> vocab;                  // token byte strings of a loaded model file
+  crispy::asr::AlignWs align;                      // word alignment (opts.dtw_token_timestamps)
 };
 
 namespace crispy {
@@ -224,8 +244,24 @@ int decode_beam(crispy_asr* h, const float* d_enc, int n_clips, int n_dec, int n
                 float temperature, const std::vector<std::mt19937*>& rng, int* tokens_out, int* tids_out, float* plog_out,
                 float* nosp_out, int* n_out);
 
+void choose_decode_path(crispy_asr* h);
+int prefill(crispy_asr* h, const float* d_enc, int batch, const int* tok_mat, int n_rows, hipStream_t s, int* pos_out);
+
 // ---- whisper_full.cpp ----
 int build_ts_masks(crispy_asr* h);
+// Word alignment of one round of the seek loop: rows[c] = clip c's token rows (sot sequence of n_sot ids, <|notimestamps|>,
+// text tokens, <|endoftext|>), d_enc = the clips' encoder outputs in order, n_frames[c] = mel frames of its window;
+// time_idx[c] receives the warping path's entry column of every row after the sot sequence but the last (10 ms x 2 each).
+// Installed by whisper_align.hip at static initialisation; null where that file is not part of the build.
+using AlignRoundFn = int (*)(crispy_asr* h, const float* d_enc, const std::vector<std::vector<int>>& rows, int n_sot,
+                             const std::vector<int>& n_frames, const std::vector<int>& heads, std::vector<std::vector<int>>& time_idx);
+extern AlignRoundFn g_align_round;
+// what the DTW kernel takes: its trace at 2 bits per cell, the last two anti-diagonals and the row entries share the LDS
+constexpr int kAlignDtwMaxRows = 512, kAlignDtwMaxCols = 4096, kAlignDtwMaxTraceWords = 35000;
+inline bool align_dtw_fits(int rows, int cols) {
+  return rows >= 1 && rows <= kAlignDtwMaxRows && cols >= 1 && cols <= kAlignDtwMaxCols &&
+         (long)rows * ((cols + 15) / 16) <= kAlignDtwMaxTraceWords;
+}
 
 }  // namespace asr
 }  // namespace crispy

@@ -77,8 +77,10 @@ const char *crispy_version(void);
 /* The ABI this header describes; crispy_abi_version() returns the one the library was built with.
  *   1: rounds 1 - 3.   2: round 4 (crispy_asr_opts 20 -> 44 bytes, crispy_asr_result gained windows, the staged RNNoise
  *   pipeline entry points removed).   3: round 5.   4: round 6 (this header: crispy_asr_transcribe_recording and its
- *   CRISPY_ERR_CANCELLED, the int16 sample transport crispy_rn_process_s16*). */
-#define CRISPY_ABI_VERSION 4
+ *   CRISPY_ERR_CANCELLED, the int16 sample transport crispy_rn_process_s16*).   5: word-level timestamps
+ *   (crispy_asr_opts::dtw_token_timestamps / dtw_heads / n_dtw_heads, crispy_asr_result::token_t_dtw / n_words / words,
+ *   crispy_asr_word, crispy_asr_align_device, crispy_asr_dtw_device). */
+#define CRISPY_ABI_VERSION 5
 int crispy_abi_version(void);
 /* Number of usable gfx950 devices (0 when there is none; never fails). */
 int crispy_device_count(void);
@@ -455,6 +457,23 @@ typedef struct crispy_asr_opts {
                             the sum of their log-probabilities and dealt to the decoders without repeating a sequence.  One
                             host round trip per token.  0 | 1: the GREEDY strategy.  At most 8 (WHISPER_MAX_DECODERS); needs
                             timestamps (no_timestamps = 1 with beam_size > 1: CRISPY_ERR_UNSUPPORTED). */
+  /* ---- appended with ABI 5 (zero / NULL = the behaviour before): word-level timestamps ---- */
+  int dtw_token_timestamps;  /* 1 = token and word start times from cross-attention alignment: openai-whisper's
+                                word_timestamps=True (timing.py: find_alignment, add_word_timestamps), whisper.cpp's
+                                dtw_token_timestamps [UPSTREAM-RECALL].  Per kept window one teacher-forced decoder pass over
+                                sot sequence + <|notimestamps|> + the window's text tokens + <|endoftext|> (the previous-text
+                                prompt is not part of it), the soft-maxed cross-attention of the alignment heads over the
+                                window's n_frames / 2 keys, standardised per frame over the tokens, a width-7 median filter
+                                along the frames, the mean over the heads, dynamic time warping on minus that matrix; each
+                                token starts where the warping path enters its row (crispy_asr_result::token_t_dtw, words).
+                                The diarization path gives each word to a speaker by its midpoint (managers/diarization.rs:
+                                656-700, format_diarized_text) from transcribe_with_timestamps (managers/transcription.rs:
+                                200-249).  Segments, tokens, text and windows are the same with or without it.  Needs
+                                timestamps (no_timestamps = 1: CRISPY_ERR_UNSUPPORTED). */
+  const int *dtw_heads;      /* the alignment heads as (layer, head) pairs, n_dtw_heads of them (a model's own
+                                `alignment_heads`; the host passes them, the library has no per-model table).  NULL: every
+                                head of the last n_text_layer - n_text_layer / 2 decoder layers (openai's default mask). */
+  int n_dtw_heads;
 } crispy_asr_opts;
 
 /* One segment of the result (managers/transcription.rs:223-233: `seg.start`, `seg.end`, `seg.text`),
@@ -479,6 +498,18 @@ typedef struct crispy_asr_window {
   float entropy;         /* entropy of the token histogram of the last 32 kept tokens */
 } crispy_asr_window;
 
+/* One word of the result (opts.dtw_token_timestamps): openai's split_tokens_on_spaces (split_tokens_on_unicode only for
+ * zh / ja / th / lo / my / yue) and merge_punctuations with its default sets.  t0 = the alignment entry time of its first
+ * token, t1 = that of the token after its last (the window's <|endoftext|> closes the last word); a punctuation mark
+ * merged into a neighbour leaves the neighbour's times as they were (openai's order).  Seconds from the start of the
+ * chunk, as segments are. */
+typedef struct crispy_asr_word {
+  float t0, t1;
+  const char *text;    /* UTF-8, NUL-terminated, with its leading space */
+  int first_token;     /* index into crispy_asr_result::tokens */
+  int n_tokens;        /* tokens of the word (timestamp tokens never are) */
+} crispy_asr_word;
+
 /* Library-owned result of one transcribe call; release with crispy_asr_free_result. */
 typedef struct crispy_asr_result {
   const char *text;    /* UTF-8, NUL-terminated, untrimmed (the caller trims: transcription.rs:187) */
@@ -489,6 +520,12 @@ typedef struct crispy_asr_result {
   const crispy_asr_segment *segments;
   int n_windows;       /* windows of the seek loop, in order (0 with no_timestamps) */
   const crispy_asr_window *windows;
+  /* ---- appended with ABI 5: word-level timestamps (NULL / 0 unless opts.dtw_token_timestamps) ---- */
+  const float *token_t_dtw;  /* [n_tokens], parallel to tokens: start time of a text token in seconds from the start of the
+                                chunk (window seek x 0.01 + its alignment entry time); -1 for timestamp tokens */
+  int n_words;
+  const void *words;         /* crispy_asr_word[n_words], in order (typed `const void *` so that the struct stays within the
+                                scalar / pointer field types every binding of this header mirrors) */
 } crispy_asr_result;
 
 /* engine.transcribe(&audio, &TranscribeOptions::default()) for ONE chunk of <= 480000 samples
@@ -522,10 +559,40 @@ void crispy_asr_free_result(crispy_asr_result *r);
  *   progress (nullable): called on the calling thread after every group with (samples done, n, progress_user) -- what the
  *     reference turns into its "transcription-progress" event (:285-299).  It must not call into this handle.
  * n == 0: an empty result (:190-194).  opts->carry_context is refused (a single-chunk option). */
+/* With opts.dtw_token_timestamps the words and token times of every chunk are shifted by its start like the segments. */
 typedef void (*crispy_asr_progress_fn)(size_t samples_done, size_t samples_total, void *user);
 int crispy_asr_transcribe_recording(crispy_asr *h, const float *pcm16k, size_t n, const crispy_asr_opts *opts,
                                     int max_batch, const volatile int *cancel_flag, crispy_asr_progress_fn progress,
                                     void *progress_user, crispy_asr_result **out);
+
+/* Stage entry points of the word-level alignment (crispy_asr_opts::dtw_token_timestamps), for tests and profiling.
+ *   crispy_asr_align_device: one teacher-forced decoder pass and the alignment matrix of `batch` clips.
+ *     d_enc       device, the encoder output of the clips [batch][n_audio_ctx][n_audio_state] (crispy_asr_encode_device)
+ *     tokens      host [batch][ld_tokens]: clip b's first n_tokens[b] ids are its token rows -- the sot sequence (n_sot ids:
+ *                 1, or 3 with a multilingual vocabulary), <|notimestamps|>, the text tokens, <|endoftext|>; at most
+ *                 n_text_ctx, and n_tokens[b] >= n_sot + 2
+ *     n_frames    host [batch]: mel frames of each clip's window, 8 ... 2 * n_audio_ctx; F = n_frames / 2 keys are used
+ *     heads       host (layer, head) pairs, n_heads of them; NULL = the default of crispy_asr_opts::dtw_heads
+ *     d_probs     (nullable) device f32 [batch][n_heads][ld_tokens][n_audio_ctx]: softmax(q.K^T / 8) over the first F keys
+ *                 of every head, columns >= F and rows >= n_tokens[b] left as they were
+ *     d_matrix    (nullable) device f32 [batch][ld_tokens][n_audio_ctx]: the standardised, median-filtered, head-averaged
+ *                 matrix of ALL token rows (the DTW takes rows n_sot ... n_tokens[b] - 2)
+ *     jump_times  (nullable) host f32 [batch][ld_tokens]: entries 0 ... n_tokens[b] - n_sot - 2 -- seconds into the window at
+ *                 which the warping path enters each row of the cropped matrix (<|notimestamps|>, then the text tokens)
+ *   Operands as the decoder's own cross-attention in the current precision mode (mode 0: f32 q and K; 1: f32 q, f16 K;
+ *   2: q rounded to f16 too).  A clip's outputs do not depend on the other clips of the batch.
+ *   crispy_asr_dtw_device: dynamic time warping (openai's dtw_cpu, ties: diagonal only when strictly below both, up only
+ *     when strictly below both, else left) of a caller's device cost matrix d_x [n_rows][ld] (n_cols <= ld used), f32
+ *     costs.  The path from (0, 0) to (n_rows - 1, n_cols - 1): text_idx / time_idx host [n_rows + n_cols], *n_path of
+ *     them.  n_rows <= 512, n_cols <= 4096 and n_rows x ceil(n_cols / 16) <= 35 000 (the trace lives in LDS at 2 bits
+ *     per cell, beside the last two anti-diagonals and the path's row entries: 226 rows x 1500 columns take 83 KB).
+ *     In the seek loop a window beyond these limits (possible only with max_new_tokens above ~370) gets no alignment:
+ *     its token times are -1 and it has no words. */
+int crispy_asr_align_device(crispy_asr *h, const float *d_enc, int batch, const int *tokens, const int *n_tokens, int ld_tokens,
+                            int n_sot, const int *n_frames, const int *heads, int n_heads, float *d_probs, float *d_matrix,
+                            float *jump_times);
+int crispy_asr_dtw_device(crispy_asr *h, const float *d_x, int n_rows, int n_cols, long ld, int *text_idx, int *time_idx,
+                          int *n_path);
 
 /* ------------------------------------------------------------------------------------------
  * 48 kHz -> 16 kHz resampler between the denoiser and the ASR front end:
