@@ -1,6 +1,7 @@
-// decode_steps.cpp -- the Whisper decoder of a crispy_asr handle: workspaces, the three forms of a step (the fused kernels of
-// whisper_dec_fused.hip for tiny / base, the matrix-vector products of whisper_dec_gemv.hip for the catalog widths, the skinny
-// GEMMs for everything else and for the multi-position prompt), cross K | V, captured steps replayed four tokens at a time,
+// decode_steps.cpp -- the Whisper decoder of a crispy_asr handle: its workspace, the start of a pass (begin_pass: the
+// DecodePass every step function takes), the three forms of a step (the fused kernels of whisper_dec_fused.hip for tiny /
+// base, the matrix-vector products of whisper_dec_gemv.hip for the catalog widths, the skinny GEMMs for everything else
+// and for the multi-position prompt), cross K | V, captured steps replayed four tokens at a time,
 // and the passes over one window: plain greedy, greedy / sampling under the timestamp rules, beam search.  The decoder half of
 // transcribe_rs::SpeechModel::transcribe (src-tauri/src/managers/transcription.rs:183-185); whisper.cpp's decoder graph and
 // sampling [UPSTREAM-RECALL].
@@ -12,7 +13,7 @@ using namespace crispy::asr;
 namespace crispy {
 namespace asr {
 
-// Row stride of h->d_logits: the vocabulary padded to a multiple of four floats.  n_vocab is odd (51865): with rows V
+// Row stride of h->dw.logits: the vocabulary padded to a multiple of four floats.  n_vocab is odd (51865): with rows V
 // apart every clip's row has another 16-byte alignment, the pick kernels split it over their threads differently, and a
 // sum over the row (the log-probability of a pick) comes out with other last bits for the same logits -- enough to
 // reorder two best-of decoders that sampled the same tokens.
@@ -22,71 +23,76 @@ long logits_ld(const crispy_asr* h) { return ((long)h->hp.n_vocab + 3) & ~3L; }
 // 0: one clip per row).  Grows only; growing frees everything and drops the captured steps.
 int reserve_dec(crispy_asr* h, int batch, int xclips) {
   if (xclips <= 0) xclips = batch;
-  if (batch <= h->dcap_batch && xclips <= h->dcap_xclips) return CRISPY_OK;
-  batch = std::max(batch, h->dcap_batch);
-  xclips = std::max(xclips, h->dcap_xclips);
+  DecWs& w = h->dw;
+  if (batch <= w.cap_rows && xclips <= w.cap_xclips) return CRISPY_OK;
+  batch = std::max(batch, w.cap_rows);
+  xclips = std::max(xclips, w.cap_xclips);
   free_dec_ws(h);
   const size_t B = batch, X = xclips, dt = h->hp.n_text_state, L = h->hp.n_text_layer, Tn = h->hp.n_audio_ctx,
                C = h->hp.n_text_ctx;
   // activation rows: one per clip in a generation step, up to SKINNY_MAX_M in a batched prompt step (prefill)
   const size_t R = B > (size_t)SKINNY_MAX_M ? B : (size_t)SKINNY_MAX_M;
-  HIP_TRY(hipMalloc(&h->d_xkv, L * X * Tn * 2 * dt * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->d_selfkv, L * B * C * 2 * dt * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->d_dx, R * dt * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->d_dxn, R * dt * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->d_dq, R * dt * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->d_datt, R * dt * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->d_dh, R * 4 * dt * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->d_logits, B * (size_t)logits_ld(h) * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->d_best, B * C * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->d_tok, R * sizeof(int)));
-  HIP_TRY(hipMalloc(&h->d_tokens_all, B * C * sizeof(int)));
-  HIP_TRY(hipMalloc(&h->d_counters, 8 * sizeof(int)));      // position, pick index, ticket of the fused pick, spare; beam pass: first generated cache row, max_new
-  HIP_TRY(hipMalloc(&h->d_ts_state, B * sizeof(TsState)));
-  HIP_TRY(hipMalloc(&h->d_tids_all, B * C * sizeof(int)));
-  HIP_TRY(hipMalloc(&h->d_done_count, sizeof(int)));
-  HIP_TRY(hipMalloc(&h->d_finished, B * sizeof(int)));
-  HIP_TRY(hipMalloc(&h->d_xkv_h, L * X * Tn * 2 * dt * 2));
-  HIP_TRY(hipMalloc(&h->d_plog_all, B * C * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->d_nosp, B * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->d_u_all, B * C * sizeof(double)));
-  HIP_TRY(hipMalloc(&h->d_ts_x, B * (size_t)TS_SCRATCH_ROW * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->d_temperature, sizeof(float)));
-  HIP_TRY(hipMalloc(&h->d_row_off, B * sizeof(int)));
-  HIP_TRY(hipMalloc(&h->d_beam_parent, B * sizeof(int)));
-  HIP_TRY(hipMalloc(&h->d_beam_row, B * sizeof(BeamRow)));
-  HIP_TRY(hipMalloc(&h->d_beam_cand, B * 3 * TS_MAX_CAND * sizeof(int)));
-  HIP_TRY(hipMalloc(&h->d_beam_rec_parent, B * C * sizeof(int)));
+  HIP_TRY(w.xkv.alloc(L * X * Tn * 2 * dt * sizeof(float)));
+  HIP_TRY(w.selfkv.alloc(L * B * C * 2 * dt * sizeof(float)));
+  HIP_TRY(w.dx.alloc(R * dt * sizeof(float)));
+  HIP_TRY(w.dxn.alloc(R * dt * sizeof(float)));
+  HIP_TRY(w.dq.alloc(R * dt * sizeof(float)));
+  HIP_TRY(w.datt.alloc(R * dt * sizeof(float)));
+  HIP_TRY(w.dh.alloc(R * 4 * dt * sizeof(float)));
+  HIP_TRY(w.logits.alloc(B * (size_t)logits_ld(h) * sizeof(float)));
+  HIP_TRY(w.best.alloc(B * C * sizeof(float)));
+  HIP_TRY(w.tok.alloc(R * sizeof(int)));
+  HIP_TRY(w.tokens_all.alloc(B * C * sizeof(int)));
+  HIP_TRY(w.counters.alloc(8 * sizeof(int)));      // position, pick index, ticket of the fused pick, spare; beam pass: first generated cache row, max_new
+  HIP_TRY(w.ts_state.alloc(B * sizeof(TsState)));
+  HIP_TRY(w.tids_all.alloc(B * C * sizeof(int)));
+  HIP_TRY(w.done_count.alloc(sizeof(int)));
+  HIP_TRY(w.finished.alloc(B * sizeof(int)));
+  HIP_TRY(w.xkv_h.alloc(L * X * Tn * 2 * dt * 2));
+  HIP_TRY(w.plog_all.alloc(B * C * sizeof(float)));
+  HIP_TRY(w.nosp.alloc(B * sizeof(float)));
+  HIP_TRY(w.u_all.alloc(B * C * sizeof(double)));
+  HIP_TRY(w.ts_x.alloc(B * (size_t)TS_SCRATCH_ROW * sizeof(float)));
+  HIP_TRY(w.temperature.alloc(sizeof(float)));
+  HIP_TRY(w.row_off.alloc(B * sizeof(int)));
+  HIP_TRY(w.beam_parent.alloc(B * sizeof(int)));
+  HIP_TRY(w.beam_row.alloc(B * sizeof(BeamRow)));
+  HIP_TRY(w.beam_cand.alloc(B * 3 * TS_MAX_CAND * sizeof(int)));
+  HIP_TRY(w.beam_rec_parent.alloc(B * C * sizeof(int)));
   if (fused_decode_supported((int)dt, 1, (int)Tn)) {
     for (int i = 0; i < 3; ++i) {
-      HIP_TRY(hipMalloc(&h->d_fx[i], B * dt * sizeof(float)));
-      HIP_TRY(hipMalloc(&h->d_fpart[i], (i == 2 ? dt / 32 : dt / 64) * B * dt * sizeof(float)));
+      HIP_TRY(w.fx[i].alloc(B * dt * sizeof(float)));
+      HIP_TRY(w.fpart[i].alloc((i == 2 ? dt / 32 : dt / 64) * B * dt * sizeof(float)));
     }
   }
   if (gemv_dec_supported((int)dt, 1))
-    HIP_TRY(hipMalloc(&h->d_gvpart, (size_t)std::min<size_t>(B, GEMV_MAX_ROWS) * (dt / 64) * XA_PARTS * XA_PART_FLOATS * sizeof(float)));
-  h->dcap_batch = batch;
-  h->dcap_xclips = xclips;
+    HIP_TRY(w.gvpart.alloc((size_t)std::min<size_t>(B, GEMV_MAX_ROWS) * (dt / 64) * XA_PARTS * XA_PART_FLOATS * sizeof(float)));
+  w.cap_rows = batch;
+  w.cap_xclips = xclips;
   return CRISPY_OK;
 }
 
-// the last block of a decoder step: final LayerNorm and vocabulary projection of h->d_dx into h->d_logits
+// The folded path: up to SKINNY_MAX_M rows the projections run on the skinny kernel (row blocks of 32), which writes q and
+// k|v of the self-attention block from one launch and, in mode 0, folds the preceding LayerNorm in
+bool folded(const crispy_asr* h, int rows) { return rows <= SKINNY_MAX_M && h->hp.n_text_state % 128 == 0; }
+
+// the last block of a decoder step: final LayerNorm and vocabulary projection of h->dw.dx into h->dw.logits
 int decoder_logits(crispy_asr* h, int batch, hipStream_t s, const float* x = nullptr) {
   const int dt = h->hp.n_text_state, V = h->hp.n_vocab;
-  if (!x) x = h->d_dx;
-  const bool fold = batch <= SKINNY_MAX_M && dt % 128 == 0;
+  if (!x) x = h->dw.dx;
+  const bool fold = folded(h, batch);
   if (h->enc_precision == 1 && h->tok_emb_hp) {
     // the reference's arithmetic: final LayerNorm in f32, rounded to f16, against the f16 embedding, f32 accumulation
-    HIP_TRY(layernorm_f16out(x, h->dec_ln_w, h->dec_ln_b, h->d_dxn, batch, dt, s));
-    HIP_TRY(vocab_f16(h->d_dxn, dt, h->tok_emb_hp, h->d_logits, logits_ld(h), batch, V, dt, s));
+    HIP_TRY(layernorm_f16out(x, h->dec_ln_w, h->dec_ln_b, h->dw.dxn, batch, dt, s));
+    HIP_TRY(vocab_f16(h->dw.dxn, dt, h->tok_emb_hp, h->dw.logits, logits_ld(h), batch, V, dt, s));
   } else {
     // Vocabulary projection in f32: LayerNorm launch + the 128 x 128 tiled kernel for every batch size.  (Up to 64 clips a
     // persistent LayerNorm-folded kernel, gemm_vocab_f32_kernel, used to run instead -- ~7 us faster per step, but other
     // arithmetic than the tiled path of larger batches: a clip's logits then depended, in the last bits, on the size of
     // the batch it was decoded in.  Mode 0 is the mode the parity claims are made in; one path keeps "alone = in any
     // batch" exact there too.)
-    HIP_TRY(layernorm_f32(x, h->dec_ln_w, h->dec_ln_b, h->d_dxn, batch, dt, s));
-    GemmArgs g = gemm(h->d_dxn, dt, h->tok_emb, dt, h->d_logits, logits_ld(h), nullptr, batch, V, dt);
+    HIP_TRY(layernorm_f32(x, h->dec_ln_w, h->dec_ln_b, h->dw.dxn, batch, dt, s));
+    GemmArgs g = gemm(h->dw.dxn, dt, h->tok_emb, dt, h->dw.logits, logits_ld(h), nullptr, batch, V, dt);
     g.tiled = fold ? 1 : 0;
     HIP_TRY(gemm_f32_nt(g, 1, s));
   }
@@ -118,22 +124,22 @@ void choose_decode_path(crispy_asr* h) {
   }
 }
 
-bool fused_step_ok(const crispy_asr* h, int rows) {
-  return h->fused_path && h->enc_precision == 1 && !h->resident && h->ln16_ready && h->dec[0].qkv_p && h->tok_emb_hp && h->d_fx[0] &&
-         rows <= FUSED_MAX_ROWS && fused_decode_supported(h->hp.n_text_state, h->dec_max_keys, h->hp.n_audio_ctx);
+bool fused_step_ok(const crispy_asr* h, const DecodePass& p) {
+  return h->fused_path && h->enc_precision == 1 && !h->resident && h->ln16_ready && h->dec[0].qkv_p && h->tok_emb_hp && h->dw.fx[0] &&
+         p.rows <= FUSED_MAX_ROWS && fused_decode_supported(h->hp.n_text_state, p.max_keys, h->hp.n_audio_ctx);
 }
 
 // A generated token's decoder step through the fused kernels (whisper_dec_fused.hip): 3 launches per layer + the final
-// LayerNorm + the vocabulary projection.  The token's embedding is in h->d_dx (written by the pick that chose it), its
-// position in h->d_counters[0]; one row per decoder, `rows / xgroup` clips (rows of a clip share its cross K | V).
-int decoder_step_fused(crispy_asr* h, int rows, hipStream_t s) {
-  const int dt = h->hp.n_text_state, Tn = h->hp.n_audio_ctx, C = h->hp.n_text_ctx;
-  const size_t clips = (size_t)rows, xclips = (size_t)(rows / h->cur_xgroup);
+// LayerNorm + the vocabulary projection.  The token's embedding is in h->dw.dx (written by the pick that chose it), its
+// position in h->dw.counters[0]; one row per decoder, `rows / xgroup` clips (rows of a clip share its cross K | V).
+int decoder_step_fused(crispy_asr* h, const DecodePass& p, hipStream_t s) {
+  const int dt = h->hp.n_text_state, Tn = h->hp.n_audio_ctx, C = h->hp.n_text_ctx, rows = p.rows;
+  const size_t clips = (size_t)rows, xclips = (size_t)(rows / p.xgroup);
   const int attn16 = h->dec_attn16 ? 1 : 0;
-  const int stream_kv = xclips * h->dec.size() * Tn * 2 * dt * 2 > ((size_t)256 << 20) ? 1 : 0;      // see decoder_step
-  float *xa = h->d_fx[0], *xb = h->d_fx[1], *xc = h->d_fx[2];
-  float *pa = h->d_fpart[0], *pb = h->d_fpart[1], *pc = h->d_fpart[2];
-  const float* x_in = h->d_dx;
+  const int stream_kv = xclips * h->dec.size() * Tn * 2 * dt * 2 > ((size_t)256 << 20) ? 1 : 0;      // see step_ctx
+  float *xa = h->dw.fx[0], *xb = h->dw.fx[1], *xc = h->dw.fx[2];
+  float *pa = h->dw.fpart[0], *pb = h->dw.fpart[1], *pc = h->dw.fpart[2];
+  const float* x_in = h->dw.dx;
   const float* prev_bias = nullptr;
   for (size_t l = 0; l < h->dec.size(); ++l) {
     const DecLayer& L = h->dec[l];
@@ -141,18 +147,18 @@ int decoder_step_fused(crispy_asr* h, int rows, hipStream_t s) {
     a.in = FusedIn{x_in, prev_bias, pc, xa, L.ln1_w, L.ln1_b};
     a.wqkv = reinterpret_cast<const _Float16*>(L.qkv_p); a.bqkv = L.qkv_b;
     a.wo = reinterpret_cast<const _Float16*>(L.out_p);
-    a.kv = reinterpret_cast<_Float16*>(h->d_selfkv) + l * clips * C * 2 * dt; a.kv_row_stride = (long)C * 2 * dt;
-    a.pos_dev = h->d_counters; a.key_off = h->cur_row_off;
-    a.attn16 = attn16; a.max_keys = h->dec_max_keys;
+    a.kv = h->dw.selfkv.as<_Float16>() + l * clips * C * 2 * dt; a.kv_row_stride = (long)C * 2 * dt;
+    a.pos_dev = h->dw.counters; a.key_off = p.row_off;
+    a.attn16 = attn16; a.max_keys = p.max_keys;
     a.part_out = pa; a.rows = rows; a.D = dt;
     HIP_TRY(fused_self(a, l == 0, s));
     FusedCrossArgs b{};
     b.in = FusedIn{xa, L.out_b, pa, xb, L.lnx_w, L.lnx_b};
     b.wq = reinterpret_cast<const _Float16*>(L.xq_wh); b.bq = L.xq_b;
     b.wo = reinterpret_cast<const _Float16*>(L.xout_wh);
-    b.xkv = reinterpret_cast<const _Float16*>(h->d_xkv_h) + l * xclips * Tn * 2 * dt; b.clip_stride = (long)Tn * 2 * dt;
-    b.n_keys = Tn; b.group = h->cur_xgroup; b.attn16 = attn16;
-    b.stream_kv = h->cur_xgroup > 1 ? 0 : stream_kv;      // the rows of a clip share its K | V through the XCD's L2: plain loads
+    b.xkv = h->dw.xkv_h.as<const _Float16>() + l * xclips * Tn * 2 * dt; b.clip_stride = (long)Tn * 2 * dt;
+    b.n_keys = Tn; b.group = p.xgroup; b.attn16 = attn16;
+    b.stream_kv = p.xgroup > 1 ? 0 : stream_kv;      // the rows of a clip share its K | V through the XCD's L2: plain loads
     b.part_out = pb; b.rows = rows; b.D = dt;
     HIP_TRY(fused_cross(b, s));
     FusedMlpArgs m{};
@@ -167,18 +173,19 @@ int decoder_step_fused(crispy_asr* h, int rows, hipStream_t s) {
   FusedFinishArgs f{};
   f.in = FusedIn{xc, prev_bias, pc, xa, h->dec_ln_w, h->dec_ln_b};
   if (rows <= VOCAB_FUSE_ROWS) {       // a few rows: the vocabulary projection normalises them itself (one launch fewer in the chain)
-    HIP_TRY(vocab_f16_fused(f.in, h->tok_emb_hp, h->d_logits, logits_ld(h), rows, h->hp.n_vocab, dt, s));
+    HIP_TRY(vocab_f16_fused(f.in, h->tok_emb_hp, h->dw.logits, logits_ld(h), rows, h->hp.n_vocab, dt, s));
     return CRISPY_OK;
   }
-  f.y = reinterpret_cast<_Float16*>(h->d_dxn); f.rows = rows; f.D = dt;
+  f.y = h->dw.dxn.as<_Float16>(); f.rows = rows; f.D = dt;
   HIP_TRY(fused_finish(f, s));
-  HIP_TRY(vocab_f16(h->d_dxn, dt, h->tok_emb_hp, h->d_logits, logits_ld(h), rows, h->hp.n_vocab, dt, s));
+  HIP_TRY(vocab_f16(h->dw.dxn, dt, h->tok_emb_hp, h->dw.logits, logits_ld(h), rows, h->hp.n_vocab, dt, s));
   return CRISPY_OK;
 }
 
-// the self K | V cache of a decode call over `rows` rows holds halves (mode 1, folded path) or floats
-bool self_kv_half(const crispy_asr* h, int rows) {
-  return rows <= SKINNY_MAX_M && h->hp.n_text_state % 128 == 0 && h->enc_precision == 1 && h->dec_max_keys > 0 && h->dec_max_keys <= 512;
+// the self K | V cache of a pass holds halves (mode 1, folded path) or floats.  (By p.rows: a multi-position prompt step has
+// rows x P <= SKINNY_MAX_M rows only where the pass's own rows are on the folded path.)
+bool self_kv_half(const crispy_asr* h, const DecodePass& p) {
+  return folded(h, p.rows) && h->enc_precision == 1 && p.max_keys > 0 && p.max_keys <= 512;
 }
 
 // A generated-token step of a catalog-width model (768 / 1024 / 1280) in precision mode 1, at ANY row count: the projections as
@@ -197,10 +204,10 @@ bool gemv_ref_ok(const QRef& r) {
     if (r.t[i]->ttype != tt || r.t[i]->n != r.t[0]->n || r.t[i]->cols != r.t[0]->cols) return false;
   return true;
 }
-bool gemv_step_ok(const crispy_asr* h, int rows) {
+bool gemv_step_ok(const crispy_asr* h, const DecodePass& p) {
   const char* e = dev_env("CRISPY_ASR_GEMV");       // read per call: a test flips it inside one process (the captured steps are keyed by
   const bool off = e && e[0] == '0';                // the handle, and the two arms of the test use two handles)
-  if (off || h->enc_precision != 1 || !h->dec_ln16 || !gemv_dec_supported(h->hp.n_text_state, rows) || !self_kv_half(h, rows)) return false;
+  if (off || h->enc_precision != 1 || !h->dec_ln16 || !gemv_dec_supported(h->hp.n_text_state, p.rows) || !self_kv_half(h, p)) return false;
   for (const DecLayer& L : h->dec) {
     if (h->resident) {
       if (!(gemv_ref_ok(L.r_qkv) && L.r_qkv.n == 3 && gemv_ref_ok(L.r_out) && gemv_ref_ok(L.r_xq) && gemv_ref_ok(L.r_xout) &&
@@ -219,7 +226,9 @@ struct StepCtx {
   hipStream_t s;
   int clips, P, rows, pos;             // rows = clips x P
   bool dev_pos;
-  const int* pos_dev;                  // h->d_counters with a device position, else null
+  const int* pos_dev;                  // h->dw.counters with a device position, else null
+  int max_keys;                        // DecodePass::max_keys
+  bool kv16;                           // self_kv_half of the pass
   bool fold;                           // the skinny kernels (<= SKINNY_MAX_M rows): LayerNorm folded in (mode 0) or a launch of its own (modes 1 / 2)
   AttnRows self_rows, cross_rows;
   int xg;                              // sequences (rows with a self K|V cache of their own) per audio clip
@@ -235,6 +244,14 @@ const float* step_w32(const StepCtx& c, const float* dense, const QRef& r, const
   const int e = dq(c.h, r, false, gamma, c.s, &o);
   if (e != CRISPY_OK) *rc = e;
   return reinterpret_cast<const float*>(o);
+}
+
+// the ggml blocks of a resident projection as the kernels that de-quantise in registers take them (GemmArgs / GemvArgs)
+template <class Args>
+void weight_blocks(Args& a, const QRef& r) {
+  for (int i = 0; i < 3; ++i) a.wq[i] = r.t[i < r.n ? i : 0]->d;
+  a.wq_type = r.t[0]->ttype;
+  a.wq_rows = (int)(r.t[0]->n / (size_t)r.t[0]->cols);
 }
 
 // One projection of the folded path.  Dense model: W = the f32 (gamma-folded) tensor or its f16 copy.  Resident model:
@@ -253,9 +270,7 @@ int step_proj(const StepCtx& c, GemmArgs g, const float* dense32, const void* de
   for (int i = 1; i < r.n; ++i) blocks = blocks && r.t[i]->ttype == r.t[0]->ttype && r.t[i]->n == r.t[0]->n;
   if (blocks && skinny_q_supported(g, 1)) {
     g.W = nullptr;
-    for (int i = 0; i < 3; ++i) g.wq[i] = r.t[i < r.n ? i : 0]->d;
-    g.wq_type = r.t[0]->ttype;
-    g.wq_rows = (int)(r.t[0]->n / (size_t)r.t[0]->cols);
+    weight_blocks(g, r);
     g.wq_gamma = gamma;
     HIP_TRY(gemm_skinny_q(g, c.s));
     return CRISPY_OK;
@@ -274,18 +289,16 @@ int layer_gemv(StepCtx& c, size_t l) {
   hipStream_t s = c.s;
   const DecLayer& L = h->dec[l];
   const int dt = c.dt, batch = c.rows;
-  _Float16* kvh = reinterpret_cast<_Float16*>(h->d_selfkv) + l * (size_t)c.clips * c.C * 2 * dt;
-  _Float16* hid = reinterpret_cast<_Float16*>(h->d_dh);                  // GELU'd hidden units as the f16 fc2 multiplies
+  _Float16* kvh = h->dw.selfkv.as<_Float16>() + l * (size_t)c.clips * c.C * 2 * dt;
+  _Float16* hid = h->dw.dh.as<_Float16>();                  // GELU'd hidden units as the f16 fc2 multiplies
   auto weights = [&](GemvArgs& a, const void* dense16, const QRef& r) {
     if (!h->resident) { a.w16 = reinterpret_cast<const _Float16*>(dense16); return; }
-    for (int i = 0; i < 3; ++i) a.wq[i] = r.t[i < r.n ? i : 0]->d;
-    a.wq_type = r.t[0]->ttype;
-    a.wq_rows = (int)(r.t[0]->n / (size_t)r.t[0]->cols);
+    weight_blocks(a, r);
   };
   auto residual_proj = [&](const float* x32, const _Float16* x16, long ldx, const void* dense16, const QRef& r, const float* bias, int K) -> int {
     GemvArgs a{};
     a.x = x32; a.x16 = x16; a.ldx = ldx; weights(a, dense16, r); a.bias = bias;
-    a.out = h->d_dx; a.res = h->d_dx; a.ldo = dt; a.M = batch; a.N = dt; a.K = K;
+    a.out = h->dw.dx; a.res = h->dw.dx; a.ldo = dt; a.M = batch; a.N = dt; a.K = K;
     HIP_TRY(gemv_dec(a, GEMV_RES, s));
     return CRISPY_OK;
   };
@@ -296,10 +309,10 @@ int layer_gemv(StepCtx& c, size_t l) {
   // instructions gv_layernorm_wave mirrors; tests/test_gpu_gemv_decode.py: row 0 of 130 == the row alone, bytes) writes
   // them as f16 once and the products read those
   const bool ln_launch = batch > GEMV_MAX_M;
-  _Float16* xn16 = reinterpret_cast<_Float16*>(h->d_dxn);
+  _Float16* xn16 = h->dw.dxn.as<_Float16>();
   auto normalised = [&](GemvArgs& a, const float* g_, const float* b_) -> int {
-    if (!ln_launch) { a.x = h->d_dx; a.ldx = dt; a.ln_g = g_; a.ln_b = b_; return CRISPY_OK; }
-    HIP_TRY(layernorm_f16out(h->d_dx, g_, b_, xn16, batch, dt, s));
+    if (!ln_launch) { a.x = h->dw.dx; a.ldx = dt; a.ln_g = g_; a.ln_b = b_; return CRISPY_OK; }
+    HIP_TRY(layernorm_f16out(h->dw.dx, g_, b_, xn16, batch, dt, s));
     a.x16 = xn16; a.ldx = dt;
     return CRISPY_OK;
   };
@@ -307,14 +320,14 @@ int layer_gemv(StepCtx& c, size_t l) {
     GemvArgs a{};
     if ((rc = normalised(a, L.ln1_w, L.ln1_b)) != CRISPY_OK) return rc;
     weights(a, L.qkv_wh, L.r_qkv); a.bias = L.qkv_b;
-    a.out = h->d_dq; a.ldo = dt; a.kv = kvh; a.kv_row_stride = (long)c.C * 2 * dt; a.pos = c.pos; a.pos_dev = c.pos_dev;
+    a.out = h->dw.dq; a.ldo = dt; a.kv = kvh; a.kv_row_stride = (long)c.C * 2 * dt; a.pos = c.pos; a.pos_dev = c.pos_dev;
     a.M = batch; a.N = 3 * dt; a.K = dt;
     HIP_TRY(gemv_dec(a, GEMV_QKV, s));
   }
-  HIP_TRY(attn_decoder_kv16(h->d_dq, dt, kvh, (long)c.C * 2 * dt, 2L * dt, 64, 0, dt, c.dev_pos ? 1 : c.pos + 1, c.pos_dev, h->d_datt, dt,
-                            batch, c.H, s, h->dec_max_keys, c.self_rows));
-  if ((rc = residual_proj(h->d_datt, nullptr, dt, L.out_wh, L.r_out, L.out_b, dt)) != CRISPY_OK) return rc;
-  if (!c.cross_rows.attn16 && h->d_gvpart && c.Tn <= XA_PARTS * 16 * XA_SLOTS * 8) {
+  HIP_TRY(attn_decoder_kv16(h->dw.dq, dt, kvh, (long)c.C * 2 * dt, 2L * dt, 64, 0, dt, c.dev_pos ? 1 : c.pos + 1, c.pos_dev, h->dw.datt, dt,
+                            batch, c.H, s, c.max_keys, c.self_rows));
+  if ((rc = residual_proj(h->dw.datt, nullptr, dt, L.out_wh, L.r_out, L.out_b, dt)) != CRISPY_OK) return rc;
+  if (!c.cross_rows.attn16 && h->dw.gvpart && c.Tn <= XA_PARTS * 16 * XA_SLOTS * 8) {
     // cross q (one launch), attention over a quarter of the keys per workgroup (heads x XA_PARTS of them per row), the partial
     // soft-maxes merged by the output projection's prologue
     XattnArgs xa{};
@@ -324,28 +337,28 @@ int layer_gemv(StepCtx& c, size_t l) {
       GemvArgs a{};
       if ((rc = normalised(a, L.lnx_w, L.lnx_b)) != CRISPY_OK) return rc;
       if (L.xq_wh) a.w16 = reinterpret_cast<const _Float16*>(L.xq_wh); else weights(a, nullptr, L.r_xq);      // (a resident model keeps this one matrix as f16 too: finalize_resident)
-      a.bias = L.xq_b; a.out = h->d_dq; a.ldo = dt; a.M = batch; a.N = dt; a.K = dt;
+      a.bias = L.xq_b; a.out = h->dw.dq; a.ldo = dt; a.M = batch; a.N = dt; a.K = dt;
       HIP_TRY(gemv_dec(a, GEMV_F32, s));
-      xa.q = h->d_dq; xa.ldq = dt;
+      xa.q = h->dw.dq; xa.ldq = dt;
     }
-    xa.xkv = reinterpret_cast<const _Float16*>(h->d_xkv_h) + l * c.xclips * c.Tn * 2 * dt; xa.clip_stride = (long)c.Tn * 2 * dt;
-    xa.n_keys = c.Tn; xa.group = c.xg; xa.part = h->d_gvpart; xa.rows = batch; xa.D = dt;
+    xa.xkv = h->dw.xkv_h.as<const _Float16>() + l * c.xclips * c.Tn * 2 * dt; xa.clip_stride = (long)c.Tn * 2 * dt;
+    xa.n_keys = c.Tn; xa.group = c.xg; xa.part = h->dw.gvpart; xa.rows = batch; xa.D = dt;
     HIP_TRY(gemv_xattn(xa, s));
     GemvArgs a{};
-    a.xpart = h->d_gvpart; weights(a, L.xout_wh, L.r_xout); a.bias = L.xout_b;
-    a.out = h->d_dx; a.res = h->d_dx; a.ldo = dt; a.M = batch; a.N = dt; a.K = dt;
+    a.xpart = h->dw.gvpart; weights(a, L.xout_wh, L.r_xout); a.bias = L.xout_b;
+    a.out = h->dw.dx; a.res = h->dw.dx; a.ldo = dt; a.M = batch; a.N = dt; a.K = dt;
     HIP_TRY(gemv_dec(a, GEMV_RES_MERGE, s));
   } else {
     {
       GemvArgs a{};
-      a.x = h->d_dx; a.ldx = dt; a.ln_g = L.lnx_w; a.ln_b = L.lnx_b; weights(a, L.xq_wh, L.r_xq); a.bias = L.xq_b;
-      a.out = h->d_dq; a.ldo = dt; a.M = batch; a.N = dt; a.K = dt;
+      a.x = h->dw.dx; a.ldx = dt; a.ln_g = L.lnx_w; a.ln_b = L.lnx_b; weights(a, L.xq_wh, L.r_xq); a.bias = L.xq_b;
+      a.out = h->dw.dq; a.ldo = dt; a.M = batch; a.N = dt; a.K = dt;
       HIP_TRY(gemv_dec(a, GEMV_F32, s));
     }
-    HIP_TRY(attn_decoder_kv16(h->d_dq, dt, reinterpret_cast<const char*>(h->d_xkv_h) + l * c.xclips * c.Tn * 2 * dt * 2,
-                              (long)c.Tn * 2 * dt, 64, 64L * c.Tn, 0, (long)c.Tn * dt, c.Tn, nullptr, h->d_datt, dt, batch, c.H, s, 0,
+    HIP_TRY(attn_decoder_kv16(h->dw.dq, dt, h->dw.xkv_h.as<const char>() + l * c.xclips * c.Tn * 2 * dt * 2,
+                              (long)c.Tn * 2 * dt, 64, 64L * c.Tn, 0, (long)c.Tn * dt, c.Tn, nullptr, h->dw.datt, dt, batch, c.H, s, 0,
                               c.cross_rows));
-    if ((rc = residual_proj(h->d_datt, nullptr, dt, L.xout_wh, L.r_xout, L.xout_b, dt)) != CRISPY_OK) return rc;
+    if ((rc = residual_proj(h->dw.datt, nullptr, dt, L.xout_wh, L.r_xout, L.xout_b, dt)) != CRISPY_OK) return rc;
   }
   {
     GemvArgs a{};
@@ -364,56 +377,56 @@ int layer_self_block(StepCtx& c, size_t l) {
   const DecLayer& L = h->dec[l];
   const int dt = c.dt, C = c.C, batch = c.rows, pos = c.pos, P = c.P, clips = c.clips;
   const bool dev_pos = c.dev_pos;
-  float* selfkv = h->d_selfkv + l * (size_t)clips * C * 2 * dt;
+  float* selfkv = h->dw.selfkv + l * (size_t)clips * C * 2 * dt;
   float* kv_dst = selfkv + (dev_pos ? 0 : (size_t)pos * 2 * dt);
   // mode 1: the self K|V cache is f16, as whisper.cpp's kv_self is (it aliases the f32 cache: every decode call
   // starts with its own prefill); the projection stores halves, the attention requests all its keys up front
-  const bool kv16 = self_kv_half(h, batch);
-  _Float16* selfkv_h = reinterpret_cast<_Float16*>(h->d_selfkv) + l * (size_t)clips * C * 2 * dt;
+  const bool kv16 = c.kv16;
+  _Float16* selfkv_h = h->dw.selfkv.as<_Float16>() + l * (size_t)clips * C * 2 * dt;
   c.self_rows.attn16 = kv16 && h->dec_attn16 ? 1 : 0;
   int qrc = CRISPY_OK;
   if (c.fold) {
     // precision modes 1 / 2: LayerNorm as a launch of its own, its output rounded to f16 on the way into the f16 matrix cores
     // against f16 weights (ggml's mul_mat arithmetic for these products too); mode 0: LayerNorm folded in, f32 operands
     const bool ln16 = h->dec_ln16;
-    if (ln16) HIP_TRY(layernorm_f32(h->d_dx, L.ln1_w, L.ln1_b, h->d_dxn, batch, dt, s));
-    GemmArgs g = gemm(ln16 ? h->d_dxn : h->d_dx, dt, nullptr, dt, h->d_dq, dt, ln16 ? L.qkv_b : nullptr, batch, 3 * dt, dt);
+    if (ln16) HIP_TRY(layernorm_f32(h->dw.dx, L.ln1_w, L.ln1_b, h->dw.dxn, batch, dt, s));
+    GemmArgs g = gemm(ln16 ? h->dw.dxn : h->dw.dx, dt, nullptr, dt, h->dw.dq, dt, ln16 ? L.qkv_b : nullptr, batch, 3 * dt, dt);
     if (!ln16) { g.ln_s = L.qkv_ls; g.ln_c = L.qkv_lc; }
     g.C2 = kv_dst; g.ldc2 = (long)C * 2 * dt; g.n_split = dt;
     if (kv16) { g.C2 = reinterpret_cast<float*>(selfkv_h + (dev_pos ? 0 : (size_t)pos * 2 * dt)); g.c2_half = 1; }
-    if (dev_pos) { g.c_off_dev = h->d_counters; g.c_off_scale = 2L * dt; }
+    if (dev_pos) { g.c_off_dev = h->dw.counters; g.c_off_scale = 2L * dt; }
     // P rows per clip: k | v of row (clip, j) belongs in cache row (clip, pos + j) -- one clip's P rows are adjacent there,
     // but clips are C rows apart.  One clip: the rows land directly (row stride 2 dt).  Several: staged in the MLP's
     // hidden buffer (free until fc1) and scattered by one strided copy.
     const bool stage_kv = P > 1 && clips > 1;
-    if (P > 1) { g.ldc2 = 2L * dt; if (stage_kv) g.C2 = h->d_dh; }
+    if (P > 1) { g.ldc2 = 2L * dt; if (stage_kv) g.C2 = h->dw.dh; }
     if ((qrc = step_proj(c, g, L.qkv_lw, L.qkv_wh, L.r_qkv, ln16 ? nullptr : L.ln1_w, ln16)) != CRISPY_OK) return qrc;
     if (stage_kv) {
       const size_t esz = kv16 ? 2 : 4;
       void* dst = kv16 ? static_cast<void*>(selfkv_h + (size_t)pos * 2 * dt) : static_cast<void*>(selfkv + (size_t)pos * 2 * dt);
-      HIP_TRY(hipMemcpy2DAsync(dst, (size_t)C * 2 * dt * esz, h->d_dh, (size_t)P * 2 * dt * esz, (size_t)P * 2 * dt * esz,
+      HIP_TRY(hipMemcpy2DAsync(dst, (size_t)C * 2 * dt * esz, h->dw.dh, (size_t)P * 2 * dt * esz, (size_t)P * 2 * dt * esz,
                                (size_t)clips, hipMemcpyDeviceToDevice, s));
     }
   } else {
-    HIP_TRY(layernorm_f32(h->d_dx, L.ln1_w, L.ln1_b, h->d_dxn, batch, dt, s));
+    HIP_TRY(layernorm_f32(h->dw.dx, L.ln1_w, L.ln1_b, h->dw.dxn, batch, dt, s));
     const float* qkv_w = step_w32(c, L.qkv_w, L.r_qkv, nullptr, &qrc);
     if (qrc != CRISPY_OK) return qrc;
-    HIP_TRY(gemm_f32_nt(gemm(h->d_dxn, dt, qkv_w, dt, h->d_dq, dt, L.qkv_b, batch, dt, dt), 1, s));
-    GemmArgs g = gemm(h->d_dxn, dt, qkv_w + (size_t)dt * dt, dt, kv_dst, (long)C * 2 * dt, L.qkv_b + dt, batch, 2 * dt, dt);
-    if (dev_pos) { g.c_off_dev = h->d_counters; g.c_off_scale = 2L * dt; }
+    HIP_TRY(gemm_f32_nt(gemm(h->dw.dxn, dt, qkv_w, dt, h->dw.dq, dt, L.qkv_b, batch, dt, dt), 1, s));
+    GemmArgs g = gemm(h->dw.dxn, dt, qkv_w + (size_t)dt * dt, dt, kv_dst, (long)C * 2 * dt, L.qkv_b + dt, batch, 2 * dt, dt);
+    if (dev_pos) { g.c_off_dev = h->dw.counters; g.c_off_scale = 2L * dt; }
     HIP_TRY(gemm_f32_nt(g, 1, s));
   }
   if (kv16)
-    HIP_TRY(attn_decoder_kv16(h->d_dq, dt, selfkv_h, (long)C * 2 * dt, 2L * dt, 64, 0, dt, dev_pos ? 1 : pos + 1, c.pos_dev,
-                              h->d_datt, dt, batch, c.H, s, h->dec_max_keys, c.self_rows));
+    HIP_TRY(attn_decoder_kv16(h->dw.dq, dt, selfkv_h, (long)C * 2 * dt, 2L * dt, 64, 0, dt, dev_pos ? 1 : pos + 1, c.pos_dev,
+                              h->dw.datt, dt, batch, c.H, s, c.max_keys, c.self_rows));
   else
-    HIP_TRY(attn_decoder_f32(h->d_dq, dt, selfkv, (long)C * 2 * dt, 2L * dt, 64, 0, dt, dev_pos ? 1 : pos + 1, c.pos_dev,
-                             h->d_datt, dt, batch, c.H, s, c.self_rows));
+    HIP_TRY(attn_decoder_f32(h->dw.dq, dt, selfkv, (long)C * 2 * dt, 2L * dt, 64, 0, dt, dev_pos ? 1 : pos + 1, c.pos_dev,
+                             h->dw.datt, dt, batch, c.H, s, c.self_rows));
   // mode 1: the projections that have no LayerNorm in front (attention outputs, the MLP's second GEMM) in ggml's
   // arithmetic -- f16 weights, the f32 activation rounded to f16 on the way into the matrix cores, f32 accumulation
   const bool wh = c.fold && h->enc_precision == 1 && (L.out_wh || h->resident);
-  GemmArgs g = gemm(h->d_datt, dt, L.out_w, dt, h->d_dx, dt, L.out_b, batch, dt, dt);
-  g.residual = h->d_dx; g.ldr = dt;
+  GemmArgs g = gemm(h->dw.datt, dt, L.out_w, dt, h->dw.dx, dt, L.out_b, batch, dt, dt);
+  g.residual = h->dw.dx; g.ldr = dt;
   return step_proj(c, g, L.out_w, L.out_wh, L.r_out, nullptr, wh);
 }
 
@@ -423,20 +436,20 @@ int layer_cross_and_mlp(StepCtx& c, size_t l) {
   hipStream_t s = c.s;
   const DecLayer& L = h->dec[l];
   const int dt = c.dt, Tn = c.Tn, batch = c.rows;
-  const float* xkv = h->d_xkv + l * c.xclips * Tn * 2 * dt;
+  const float* xkv = h->dw.xkv + l * c.xclips * Tn * 2 * dt;
   const bool ln16 = h->dec_ln16;
   const bool wh = c.fold && h->enc_precision == 1 && (L.out_wh || h->resident);
   int qrc = CRISPY_OK;
   if (c.fold) {
-    if (ln16) HIP_TRY(layernorm_f32(h->d_dx, L.lnx_w, L.lnx_b, h->d_dxn, batch, dt, s));
-    GemmArgs g = gemm(ln16 ? h->d_dxn : h->d_dx, dt, nullptr, dt, h->d_dq, dt, ln16 ? L.xq_b : nullptr, batch, dt, dt);
+    if (ln16) HIP_TRY(layernorm_f32(h->dw.dx, L.lnx_w, L.lnx_b, h->dw.dxn, batch, dt, s));
+    GemmArgs g = gemm(ln16 ? h->dw.dxn : h->dw.dx, dt, nullptr, dt, h->dw.dq, dt, ln16 ? L.xq_b : nullptr, batch, dt, dt);
     if (!ln16) { g.ln_s = L.xq_ls; g.ln_c = L.xq_lc; }
     if ((qrc = step_proj(c, g, L.xq_lw, L.xq_wh, L.r_xq, ln16 ? nullptr : L.lnx_w, ln16)) != CRISPY_OK) return qrc;
   } else {
-    HIP_TRY(layernorm_f32(h->d_dx, L.lnx_w, L.lnx_b, h->d_dxn, batch, dt, s));
+    HIP_TRY(layernorm_f32(h->dw.dx, L.lnx_w, L.lnx_b, h->dw.dxn, batch, dt, s));
     const float* xq_w = step_w32(c, L.xq_w, L.r_xq, nullptr, &qrc);
     if (qrc != CRISPY_OK) return qrc;
-    HIP_TRY(gemm_f32_nt(gemm(h->d_dxn, dt, xq_w, dt, h->d_dq, dt, L.xq_b, batch, dt, dt), 1, s));
+    HIP_TRY(gemm_f32_nt(gemm(h->dw.dxn, dt, xq_w, dt, h->dw.dq, dt, L.xq_b, batch, dt, dt), 1, s));
   }
   if (h->align.on && l < h->align.slot.size() && h->align.slot[l] >= 0) {
     // word alignment pass (whisper_align.hip): keep the cross q of rows (clip, pos .. pos + P - 1) -- what the attention
@@ -444,69 +457,54 @@ int layer_cross_and_mlp(StepCtx& c, size_t l) {
     AlignWs& A = h->align;
     if (c.dev_pos || c.pos + c.P > A.rows) return fail(CRISPY_ERR_INVALID_ARG, "alignment pass: rows out of range");
     float* dst = A.q + (((size_t)A.slot[l] * c.clips) * A.rows + c.pos) * dt;
-    HIP_TRY(hipMemcpy2DAsync(dst, (size_t)A.rows * dt * sizeof(float), h->d_dq, (size_t)c.P * dt * sizeof(float),
+    HIP_TRY(hipMemcpy2DAsync(dst, (size_t)A.rows * dt * sizeof(float), h->dw.dq, (size_t)c.P * dt * sizeof(float),
                              (size_t)c.P * dt * sizeof(float), (size_t)c.clips, hipMemcpyDeviceToDevice, s));
   }
   if (h->enc_precision == 1)
-    HIP_TRY(attn_decoder_kv16(h->d_dq, dt, reinterpret_cast<const char*>(h->d_xkv_h) + l * c.xclips * Tn * 2 * dt * 2,
-                              (long)Tn * 2 * dt, 64, 64L * Tn, 0, (long)Tn * dt, Tn, nullptr, h->d_datt, dt, batch, c.H, s, 0,
+    HIP_TRY(attn_decoder_kv16(h->dw.dq, dt, h->dw.xkv_h.as<const char>() + l * c.xclips * Tn * 2 * dt * 2,
+                              (long)Tn * 2 * dt, 64, 64L * Tn, 0, (long)Tn * dt, Tn, nullptr, h->dw.datt, dt, batch, c.H, s, 0,
                               c.cross_rows));
   else
-    HIP_TRY(attn_decoder_f32(h->d_dq, dt, xkv, (long)Tn * 2 * dt, 64, 64L * Tn, 0, (long)Tn * dt, Tn, nullptr, h->d_datt, dt,
+    HIP_TRY(attn_decoder_f32(h->dw.dq, dt, xkv, (long)Tn * 2 * dt, 64, 64L * Tn, 0, (long)Tn * dt, Tn, nullptr, h->dw.datt, dt,
                              batch, c.H, s, c.cross_rows));
   {
-    GemmArgs g = gemm(h->d_datt, dt, L.xout_w, dt, h->d_dx, dt, L.xout_b, batch, dt, dt);
-    g.residual = h->d_dx; g.ldr = dt;
+    GemmArgs g = gemm(h->dw.datt, dt, L.xout_w, dt, h->dw.dx, dt, L.xout_b, batch, dt, dt);
+    g.residual = h->dw.dx; g.ldr = dt;
     if ((qrc = step_proj(c, g, L.xout_w, L.xout_wh, L.r_xout, nullptr, wh)) != CRISPY_OK) return qrc;
   }
   // MLP
   if (c.fold) {
-    if (ln16) HIP_TRY(layernorm_f32(h->d_dx, L.ln2_w, L.ln2_b, h->d_dxn, batch, dt, s));
-    GemmArgs g = gemm(ln16 ? h->d_dxn : h->d_dx, dt, nullptr, dt, h->d_dh, 4L * dt, ln16 ? L.fc1_b : nullptr, batch, 4 * dt, dt);
+    if (ln16) HIP_TRY(layernorm_f32(h->dw.dx, L.ln2_w, L.ln2_b, h->dw.dxn, batch, dt, s));
+    GemmArgs g = gemm(ln16 ? h->dw.dxn : h->dw.dx, dt, nullptr, dt, h->dw.dh, 4L * dt, ln16 ? L.fc1_b : nullptr, batch, 4 * dt, dt);
     if (!ln16) { g.ln_s = L.fc1_ls; g.ln_c = L.fc1_lc; }
     g.gelu = h->enc_precision == 1 ? 2 : 1;      // mode 1: ggml's GELU (asr_common.h: gelu_ggml)
     if ((qrc = step_proj(c, g, L.fc1_lw, L.fc1_wh, L.r_fc1, ln16 ? nullptr : L.ln2_w, ln16)) != CRISPY_OK) return qrc;
   } else {
-    HIP_TRY(layernorm_f32(h->d_dx, L.ln2_w, L.ln2_b, h->d_dxn, batch, dt, s));
-    GemmArgs g = gemm(h->d_dxn, dt, step_w32(c, L.fc1_w, L.r_fc1, nullptr, &qrc), dt, h->d_dh, 4L * dt, L.fc1_b, batch, 4 * dt, dt);
+    HIP_TRY(layernorm_f32(h->dw.dx, L.ln2_w, L.ln2_b, h->dw.dxn, batch, dt, s));
+    GemmArgs g = gemm(h->dw.dxn, dt, step_w32(c, L.fc1_w, L.r_fc1, nullptr, &qrc), dt, h->dw.dh, 4L * dt, L.fc1_b, batch, 4 * dt, dt);
     if (qrc != CRISPY_OK) return qrc;
     g.gelu = h->enc_precision == 1 ? 2 : 1;
     HIP_TRY(gemm_f32_nt(g, 1, s));
   }
-  GemmArgs g = gemm(h->d_dh, 4L * dt, L.fc2_w, 4L * dt, h->d_dx, dt, L.fc2_b, batch, dt, 4 * dt);
-  g.residual = h->d_dx; g.ldr = dt;
+  GemmArgs g = gemm(h->dw.dh, 4L * dt, L.fc2_w, 4L * dt, h->dw.dx, dt, L.fc2_b, batch, dt, 4 * dt);
+  g.residual = h->dw.dx; g.ldr = dt;
   return step_proj(c, g, L.fc2_w, L.fc2_wh, L.r_fc2, nullptr, wh);
 }
 
-// one decoder step for all clips: token ids in h->d_tok; leaves logits in h->d_logits.
-// dev_pos = false: the position is the host value `pos` (prompt tokens).
-// dev_pos = true : the position is read from h->d_counters[0] by the kernels, so the identical launch
-//                  sequence can be captured once in a hipGraph and replayed for every generated token.
-//
-// P > 1 (prefill only: host position, folded path): the step covers P consecutive positions pos .. pos + P - 1 of every
-// clip at once -- row = clip * P + j, token ids [batch][P] in h->d_tok.  Every row goes through exactly the arithmetic of
-// the one-position step it replaces (the skinny GEMMs split K by K alone; one attention workgroup per (row, head) with the row's
-// own key count), so the result is bit-identical to P steps -- at the cost of one.
-int decoder_step(crispy_asr* h, int batch, int pos, bool dev_pos, bool want_logits, hipStream_t s, bool embedded = false,
-                 int P = 1) {
+// what is the same for every layer of an un-fused step of pass `p`: P positions from `pos` on (a prompt step), or one at the
+// device position (a generated token)
+StepCtx step_ctx(crispy_asr* h, const DecodePass& p, int pos, int P, bool dev_pos, hipStream_t s) {
   const int dt = h->hp.n_text_state, Tn = h->hp.n_audio_ctx;
-  const int clips = batch;
-  if (P < 1) P = 1;
-  // a generated token (its embedding written by the pick, its position on the device): the fused step kernels
-  if (P == 1 && dev_pos && embedded && want_logits && fused_step_ok(h, clips)) return decoder_step_fused(h, clips, s);
   StepCtx c{};
-  c.h = h; c.s = s; c.clips = clips; c.P = P; c.rows = clips * P; c.pos = pos; c.dev_pos = dev_pos;
-  c.pos_dev = dev_pos ? h->d_counters : nullptr;
+  c.h = h; c.s = s; c.clips = p.rows; c.P = P; c.rows = p.rows * P; c.pos = pos; c.dev_pos = dev_pos;
+  if (dev_pos) c.pos_dev = h->dw.counters;
+  c.max_keys = p.max_keys; c.kv16 = self_kv_half(h, p);
   c.dt = dt; c.H = h->hp.n_text_head; c.Tn = Tn; c.C = h->hp.n_text_ctx;
-  // <= SKINNY_MAX_M rows: the projections run on the skinny kernel (row blocks of 32), which writes q and k|v of the
-  // self-attention block from one launch and, in mode 0, folds the preceding LayerNorm in
-  c.fold = c.rows <= SKINNY_MAX_M && dt % 128 == 0;
-  if (P > 1 && (!c.fold || dev_pos || embedded))
-    return fail(CRISPY_ERR_INVALID_ARG, "decoder_step: a multi-position step needs the folded path and a host position");
+  c.fold = folded(h, c.rows);
   c.self_rows.group = P; c.self_rows.key_step = P > 1 ? 1 : 0;
-  c.self_rows.key_off = h->cur_row_off;      // left-padded prompts (decode_ts): every clip's keys start at its own cache row
-  c.xg = h->cur_xgroup;
-  c.xclips = (size_t)(clips / c.xg);
+  c.self_rows.key_off = p.row_off;      // left-padded prompts (decode_ts): every clip's keys start at its own cache row
+  c.xg = p.xgroup;
+  c.xclips = (size_t)(c.clips / c.xg);
   c.cross_rows.group = P * c.xg;
   // precision mode 2: q and the normalised probabilities rounded to f16 inside the attentions over the f16 caches
   c.cross_rows.attn16 = h->dec_attn16 && h->enc_precision == 1 ? 1 : 0;
@@ -518,16 +516,46 @@ int decoder_step(crispy_asr* h, int batch, int pos, bool dev_pos, bool want_logi
   // served by the Infinity Cache only if the first read allocates there: 2.06 vs 2.18 ms for the prompt of 128 clips)
   static const bool prompt_nt = dev_env("CRISPY_XKV_PROMPT_NT") != nullptr;      // developer A/B (tools/ab_prompt_nt.sh)
   c.cross_rows.stream_kv = (P == 1 || prompt_nt) && c.xclips * h->dec.size() * Tn * 2 * dt * (h->enc_precision == 1 ? 2 : 4) > ((size_t)256 << 20) ? 1 : 0;
-  if (!embedded) {    // (a fused pick has written the residual stream already)
-    if (h->resident)
-      HIP_TRY(embed_tokens_q(h->d_tok, h->q_tok_emb->d, h->q_tok_emb->ttype, h->dec_pos, pos, c.pos_dev, h->d_dx, c.rows, dt, s, P,
-                             h->cur_row_off));
-    else
-      HIP_TRY(embed_tokens_f32(h->d_tok, h->tok_emb, h->dec_pos, pos, c.pos_dev, h->d_dx, c.rows, dt, s, P, h->cur_row_off));
+  return c;
+}
+
+// A prompt step for all rows of pass `p`: token ids in h->dw.tok, the position is the host value `pos`; want_logits leaves
+// the logits in h->dw.logits.
+//
+// P > 1 (prefill only: folded path): the step covers P consecutive positions pos .. pos + P - 1 of every
+// clip at once -- row = clip * P + j, token ids [rows][P] in h->dw.tok.  Every row goes through exactly the arithmetic of
+// the one-position step it replaces (the skinny GEMMs split K by K alone; one attention workgroup per (row, head) with the row's
+// own key count), so the result is bit-identical to P steps -- at the cost of one.
+// A prompt position is a row of a multi-position step or -- when rows x P does not divide the prompt -- a single-position
+// step of the SAME skinny kernels, whatever the batch (never the matrix-vector form of a generated token).
+int prompt_step(crispy_asr* h, const DecodePass& p, int pos, int P, bool want_logits, hipStream_t s) {
+  const int dt = h->hp.n_text_state, clips = p.rows;
+  StepCtx c = step_ctx(h, p, pos, P, false, s);
+  if (P > 1 && !c.fold) return fail(CRISPY_ERR_INVALID_ARG, "prompt_step: a multi-position step needs the folded path");
+  if (h->resident)
+    HIP_TRY(embed_tokens_q(h->dw.tok, h->q_tok_emb->d, h->q_tok_emb->ttype, h->dec_pos, pos, nullptr, h->dw.dx, c.rows, dt, s, P, p.row_off));
+  else
+    HIP_TRY(embed_tokens_f32(h->dw.tok, h->tok_emb, h->dec_pos, pos, nullptr, h->dw.dx, c.rows, dt, s, P, p.row_off));
+  for (size_t l = 0; l < h->dec.size(); ++l) {
+    int rc = layer_self_block(c, l);
+    if (rc == CRISPY_OK) rc = layer_cross_and_mlp(c, l);
+    if (rc != CRISPY_OK) return rc;
   }
-  // generated tokens only (device position): a prompt position is a row of a multi-position step or -- when batch x P does not
-  // divide the prompt -- a single-position step of the SAME skinny kernels, whatever the batch
-  const bool use_gemv = P == 1 && dev_pos && gemv_step_ok(h, c.rows);
+  if (!want_logits) return CRISPY_OK;
+  if (P == 1) return decoder_logits(h, clips, s);
+  // the logits of a prompt step are those of its LAST position: gather row (clip, P - 1) of every clip
+  HIP_TRY(hipMemcpy2DAsync(h->dw.dq, (size_t)dt * 4, h->dw.dx + (size_t)(P - 1) * dt, (size_t)P * dt * 4, (size_t)dt * 4,
+                           (size_t)clips, hipMemcpyDeviceToDevice, s));
+  return decoder_logits(h, clips, s, h->dw.dq);
+}
+
+// A generated token's step for all rows of pass `p`: the pick has written the token's embedding into h->dw.dx, the position
+// is read from h->dw.counters[0] by the kernels, so the identical launch sequence can be captured once in a hipGraph and
+// replayed for every generated token.  Leaves the logits in h->dw.logits.
+int token_step(crispy_asr* h, const DecodePass& p, hipStream_t s) {
+  if (fused_step_ok(h, p)) return decoder_step_fused(h, p, s);
+  StepCtx c = step_ctx(h, p, 0, 1, true, s);
+  const bool use_gemv = gemv_step_ok(h, p);
   for (size_t l = 0; l < h->dec.size(); ++l) {
     int rc;
     if (use_gemv) {
@@ -538,14 +566,7 @@ int decoder_step(crispy_asr* h, int batch, int pos, bool dev_pos, bool want_logi
     }
     if (rc != CRISPY_OK) return rc;
   }
-  if (want_logits) {
-    if (P == 1) return decoder_logits(h, clips, s);
-    // the logits of a prompt step are those of its LAST position: gather row (clip, P - 1) of every clip
-    HIP_TRY(hipMemcpy2DAsync(h->d_dq, (size_t)dt * 4, h->d_dx + (size_t)(P - 1) * dt, (size_t)P * dt * 4, (size_t)dt * 4,
-                             (size_t)clips, hipMemcpyDeviceToDevice, s));
-    return decoder_logits(h, clips, s, h->d_dq);
-  }
-  return CRISPY_OK;
+  return decoder_logits(h, p.rows, s);
 }
 
 // special token ids [UPSTREAM-RECALL, whisper.cpp `whisper_vocab` + the shift applied at load time]: the defaults are the
@@ -573,8 +594,6 @@ Special vocab_specials(int n_vocab) {
 }
 Special special_tokens(const crispy_asr* h) { return vocab_specials(h->hp.n_vocab); }
 
-// cross K | V of every layer once per window, then the prompt tokens one position at a time (the language
-// token may differ per clip); leaves the logits of the last prompt position in h->d_logits
 // cross K | V of every layer, once per window (f16 mode: the decode steps stream an f16 copy of it)
 int compute_cross_kv(crispy_asr* h, const float* d_enc, int batch, hipStream_t s) {
   const int dt = h->hp.n_text_state, Tn = h->hp.n_audio_ctx;
@@ -583,14 +602,14 @@ int compute_cross_kv(crispy_asr* h, const float* d_enc, int batch, hipStream_t s
     // to f16, f32 accumulation), written as f16 head-major straight from the epilogue.  (It used to run as an f32 GEMM
     // followed by a conversion pass: 3.9 + 0.8 ms per layer at 256 Whisper-base clips, more than the whole encoder.)
     const long n = (long)batch * Tn * dt;
-    _Float16* enc_h = reinterpret_cast<_Float16*>(h->d_xkv);       // the f32 cross K|V buffer is unused in this mode
+    _Float16* enc_h = h->dw.xkv.as<_Float16>();       // the f32 cross K|V buffer is unused in this mode
     HIP_TRY(convert_f32_to_f16(d_enc, enc_h, n, s));
     for (size_t l = 0; l < h->dec.size(); ++l) {
       const void* xkv_wh = h->dec[l].xkv_wh;
       if (h->resident) { const int rq = dq(h, h->dec[l].r_xkv, true, nullptr, s, &xkv_wh); if (rq != CRISPY_OK) return rq; }
       HGemmArgs g{};
       g.A = enc_h; g.lda = dt; g.W = reinterpret_cast<const _Float16*>(xkv_wh); g.ldw = dt;
-      g.C = reinterpret_cast<_Float16*>(h->d_xkv_h) + l * (size_t)batch * Tn * 2 * dt;
+      g.C = h->dw.xkv_h.as<_Float16>() + l * (size_t)batch * Tn * 2 * dt;
       g.bias = h->dec[l].xkv_b; g.M = batch * Tn; g.N = 2 * dt; g.K = dt; g.vt_T = Tn; g.kv_width = dt;
       g.xcd_swizzle = h->xcd_swizzle;
       HIP_TRY(gemm_hh(g, HGEMM_KVH, 1, s));
@@ -598,34 +617,34 @@ int compute_cross_kv(crispy_asr* h, const float* d_enc, int batch, hipStream_t s
     return CRISPY_OK;
   }
   for (size_t l = 0; l < h->dec.size(); ++l) {
-    float* xkv = h->d_xkv + l * (size_t)batch * Tn * 2 * dt;
+    float* xkv = h->dw.xkv + l * (size_t)batch * Tn * 2 * dt;
     // head-major store: per clip [K | V][head][Tn][64], so the decode-step attention streams contiguous runs
     GemmArgs g = gemm(d_enc, dt, h->dec[l].xkv_w, dt, xkv, 2L * dt, h->dec[l].xkv_b, batch * Tn, 2 * dt, dt);
     g.hm_rows = Tn; g.hm_width = dt;
     HIP_TRY(gemm_f32_nt(g, 1, s));
   }
   if (h->enc_precision == 1)
-    HIP_TRY(convert_f32_to_f16(h->d_xkv, h->d_xkv_h, (long)h->dec.size() * batch * Tn * 2 * dt, s));
+    HIP_TRY(convert_f32_to_f16(h->dw.xkv, h->dw.xkv_h, (long)h->dec.size() * batch * Tn * 2 * dt, s));
   return CRISPY_OK;
 }
 
 // cross K | V of every layer once per window, then the prompts: tok_mat [batch][n_rows] (host) holds every clip's prompt
 // RIGHT-aligned -- a clip whose prompt is shorter than n_rows is padded on the left (token 0) with rows it never attends
-// to (h->cur_row_off: the padding per clip; nullptr = none).  Leaves the logits of the last prompt position in h->d_logits.
-int prefill(crispy_asr* h, const float* d_enc, int batch, const int* tok_mat, int n_rows, hipStream_t s, int* pos_out) {
+// to (pass.row_off: the padding per clip; nullptr = none).  Leaves the logits of the last prompt position in h->dw.logits.
+int prefill(crispy_asr* h, const DecodePass& pass, const float* d_enc, const int* tok_mat, int n_rows, hipStream_t s, int* pos_out) {
+  const int batch = pass.rows;
   {
-    const int rc = compute_cross_kv(h, d_enc, batch / h->cur_xgroup, s);
+    const int rc = compute_cross_kv(h, d_enc, batch / pass.xgroup, s);
     if (rc != CRISPY_OK) return rc;
   }
-  // The prompt runs as multi-position steps: P positions of every clip per step (decoder_step, P > 1), as many as the
+  // The prompt runs as multi-position steps: P positions of every clip per step (prompt_step, P > 1), as many as the
   // skinny kernels' row range allows -- batch x P <= SKINNY_MAX_M, so a 4-token prompt of up to 128 clips is ONE step
   // instead of four, and a long prompt (previous-text conditioning: up to 228 tokens per clip) takes one step per
   // 512 / batch positions.  Bit-identical to the position-by-position prefill (CRISPY_ASR_PREFILL=seq keeps that one
   // available for the A/B test).
   const char* pf_env = test_env("CRISPY_ASR_PREFILL");      // read per call: the A/B test flips it inside one process
   const bool seq = pf_env && std::strcmp(pf_env, "seq") == 0;
-  const bool fold = batch <= SKINNY_MAX_M && h->hp.n_text_state % 128 == 0;
-  const int p_max = (!fold || seq) ? 1 : std::max(1, SKINNY_MAX_M / batch);
+  const int p_max = (!folded(h, batch) || seq) ? 1 : std::max(1, SKINNY_MAX_M / batch);
   std::vector<int> tok;
   int pos = 0;
   while (pos < n_rows) {
@@ -633,9 +652,9 @@ int prefill(crispy_asr* h, const float* d_enc, int batch, const int* tok_mat, in
     tok.resize((size_t)batch * P);
     for (int b = 0; b < batch; ++b)
       for (int j = 0; j < P; ++j) tok[(size_t)b * P + j] = tok_mat[(size_t)b * n_rows + pos + j];
-    HIP_TRY(hipMemcpyAsync(h->d_tok, tok.data(), sizeof(int) * tok.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->dw.tok, tok.data(), sizeof(int) * tok.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));  // tok is reused by the next iteration
-    const int rc = decoder_step(h, batch, pos, false, pos + P == n_rows, s, false, P);
+    const int rc = prompt_step(h, pass, pos, P, pos + P == n_rows, s);
     if (rc != CRISPY_OK) return rc;
     pos += P;
   }
@@ -643,8 +662,8 @@ int prefill(crispy_asr* h, const float* d_enc, int batch, const int* tok_mat, in
   return CRISPY_OK;
 }
 
-StepFuse step_fuse(crispy_asr* h) {
-  StepFuse f{h->tok_emb, h->dec_pos, h->d_dx, h->hp.n_text_state, h->d_counters, nullptr, 0, h->cur_row_off};
+StepFuse step_fuse(crispy_asr* h, const DecodePass& p) {
+  StepFuse f{h->tok_emb, h->dec_pos, h->dw.dx, h->hp.n_text_state, h->dw.counters, nullptr, 0, p.row_off};
   if (h->resident) { f.tok_emb_q = h->q_tok_emb->d; f.tok_emb_ttype = h->q_tok_emb->ttype; }
   return f;
 }
@@ -652,27 +671,27 @@ StepFuse step_fuse(crispy_asr* h) {
 TsPickArgs ts_args(crispy_asr* h, int rules, const unsigned char* mask, const unsigned char* mask_first) {
   const Special sp = special_tokens(h);
   TsPickArgs a{};
-  a.logits = h->d_logits;
+  a.logits = h->dw.logits;
   a.ld = logits_ld(h);
   a.mask = mask;
   a.mask_first = mask_first;
-  a.st = h->d_ts_state;
+  a.st = h->dw.ts_state;
   a.V = h->hp.n_vocab;
   a.beg = sp.beg;
   a.eot = h->eot;
   a.not_tok = sp.not_;
   a.rules = rules;
   a.max_initial_ts = 50;     // whisper.cpp max_initial_ts = 1.0 s at 0.02 s per timestamp; HF/openai: 50
-  a.tokens_out = h->d_tok;
-  a.tokens_all = h->d_tokens_all;
-  a.tids_all = h->d_tids_all;
-  a.plog_all = h->d_plog_all;
-  a.step_dev = h->d_counters + 1;
-  a.done_count = h->d_done_count;
+  a.tokens_out = h->dw.tok;
+  a.tokens_all = h->dw.tokens_all;
+  a.tids_all = h->dw.tids_all;
+  a.plog_all = h->dw.plog_all;
+  a.step_dev = h->dw.counters + 1;
+  a.done_count = h->dw.done_count;
   a.delta_min = TS_DELTA_MIN;
-  a.temperature = h->d_temperature;
+  a.temperature = h->dw.temperature;
   a.u_all = nullptr;
-  a.x_scratch = h->d_ts_x;
+  a.x_scratch = h->dw.ts_x;
   return a;
 }
 
@@ -711,7 +730,7 @@ int step_graph(crispy_asr* h, crispy_asr::TsKey key, Body body, hipGraphExec_t* 
 }
 
 // Replays `n_steps` generated tokens (kStepsPerReplay at a time, then singly); every 8 tokens it asks whether every row
-// is done (h->d_done_count >= rows) and stops early.  Returns the steps run in *steps_run.
+// is done (h->dw.done_count >= rows) and stops early.  Returns the steps run in *steps_run.
 template <class Body>
 int run_steps(crispy_asr* h, crispy_asr::TsKey key, int rows, int n_steps, Body body, int* steps_run) {
   hipStream_t s = h->stream;
@@ -725,12 +744,47 @@ int run_steps(crispy_asr* h, crispy_asr::TsKey key, int rows, int n_steps, Body 
     const int before = ran;
     ran += key.steps;
     if (ran / 8 != before / 8) {       // every 8 tokens: has every row ended?  (nothing behind its end is returned)
-      HIP_TRY(hipMemcpyAsync(&done, h->d_done_count, sizeof(int), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(&done, h->dw.done_count, sizeof(int), hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
       if (done >= rows) break;
     }
   }
   *steps_run = ran;
+  return CRISPY_OK;
+}
+
+// Key class of a pass: the self-attention kernel of mode 1 is baked into a captured step by the positions it can reach
+// (<= 128 / 256 / 512).  A transcribe call with previous-text conditioning alternates between classes from window to
+// window (bare prompt, then prompt + past), hence a captured step per class (crispy_asr::TsKey).
+int key_class(int max_keys) { return max_keys <= 128 ? 0 : max_keys <= 256 ? 1 : 2; }
+
+int begin_pass(crispy_asr* h, const char* who, const std::vector<std::vector<int>>& prompts, int xgroup, int max_new, int fixed_keys,
+               bool row_offsets, PassStart* out) {
+  const int rows = (int)prompts.size();
+  if (xgroup < 1 || rows % xgroup != 0) return fail(CRISPY_ERR_INVALID_ARG, "%s %d rows are not whole groups of %d", who, rows, xgroup);
+  int n_rows = 0;
+  for (const auto& p : prompts) {
+    if (p.empty()) return fail(CRISPY_ERR_INVALID_ARG, "%s empty prompt", who);
+    for (int t : p)
+      if (t < 0 || t >= h->hp.n_vocab) return fail(CRISPY_ERR_INVALID_ARG, "%s prompt token %d out of range", who, t);
+    n_rows = std::max(n_rows, (int)p.size());
+  }
+  if (n_rows + max_new > h->hp.n_text_ctx)
+    return fail(CRISPY_ERR_INVALID_ARG, "%s %d prompt + %d new tokens exceed n_text_ctx %d", who, n_rows, max_new, h->hp.n_text_ctx);
+  const int rc = reserve_dec(h, rows, rows / xgroup);
+  if (rc != CRISPY_OK) return rc;
+  choose_decode_path(h);
+  out->pass = DecodePass{rows, xgroup, fixed_keys > 0 ? fixed_keys : n_rows + max_new, row_offsets ? h->dw.row_off.p : nullptr};
+  out->n_rows = n_rows;
+  std::vector<int> off(rows);
+  out->tok_mat.assign((size_t)rows * n_rows, 0);
+  for (int b = 0; b < rows; ++b) {
+    off[b] = n_rows - (int)prompts[b].size();
+    std::copy(prompts[b].begin(), prompts[b].end(), out->tok_mat.begin() + (size_t)b * n_rows + off[b]);
+  }
+  if (!row_offsets) return CRISPY_OK;
+  HIP_TRY(hipMemcpyAsync(h->dw.row_off, off.data(), sizeof(int) * rows, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
   return CRISPY_OK;
 }
 
@@ -750,57 +804,37 @@ int decode_ts(crispy_asr* h, const float* d_enc, int batch, const std::vector<st
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   if ((int)prompts.size() != batch) return fail(CRISPY_ERR_INVALID_ARG, "decode: %zu prompts for %d rows", prompts.size(), batch);
-  if (xgroup < 1 || batch % xgroup != 0) return fail(CRISPY_ERR_INVALID_ARG, "decode: %d rows are not whole groups of %d", batch, xgroup);
-  int n_rows = 0;
-  for (const auto& p : prompts) {
-    if (p.empty()) return fail(CRISPY_ERR_INVALID_ARG, "decode: empty prompt");
-    for (int t : p)
-      if (t < 0 || t >= h->hp.n_vocab) return fail(CRISPY_ERR_INVALID_ARG, "decode: prompt token %d out of range", t);
-    n_rows = std::max(n_rows, (int)p.size());
-  }
-  if (n_rows + max_new > h->hp.n_text_ctx)
-    return fail(CRISPY_ERR_INVALID_ARG, "decode: %d prompt + %d new tokens exceed n_text_ctx %d", n_rows, max_new, h->hp.n_text_ctx);
   if (u && !(temperature > 0.f)) return fail(CRISPY_ERR_INVALID_ARG, "decode: sampling needs a temperature > 0");
-  int rc = reserve_dec(h, batch, batch / xgroup);
+  PassStart ps;
+  int rc = begin_pass(h, "decode:", prompts, xgroup, max_new, 0, true, &ps);
   if (rc != CRISPY_OK) return rc;
-  choose_decode_path(h);
-  h->dec_max_keys = n_rows + max_new;
-  std::vector<int> off(batch), tok_mat((size_t)batch * n_rows, 0);
-  for (int b = 0; b < batch; ++b) {
-    off[b] = n_rows - (int)prompts[b].size();
-    std::copy(prompts[b].begin(), prompts[b].end(), tok_mat.begin() + (size_t)b * n_rows + off[b]);
-  }
-  HIP_TRY(hipMemcpyAsync(h->d_row_off, off.data(), sizeof(int) * batch, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  struct OffGuard { crispy_asr* h; ~OffGuard() { h->cur_row_off = nullptr; h->cur_xgroup = 1; } } guard{h};
-  h->cur_row_off = h->d_row_off;
-  h->cur_xgroup = xgroup;
+  const DecodePass& pass = ps.pass;
   int pos = 0;
-  rc = prefill(h, d_enc, batch, tok_mat.data(), n_rows, s, &pos);
+  rc = prefill(h, pass, d_enc, ps.tok_mat.data(), ps.n_rows, s, &pos);
   if (rc != CRISPY_OK) return rc;
   const Special sp = special_tokens(h);
-  HIP_TRY(softmax_prob_f32(h->d_logits, h->hp.n_vocab, logits_ld(h), sp.nosp, h->d_nosp, batch, s));
+  HIP_TRY(softmax_prob_f32(h->dw.logits, h->hp.n_vocab, logits_ld(h), sp.nosp, h->dw.nosp, batch, s));
   std::vector<TsState> st(batch);
   for (int b = 0; b < batch; ++b) st[b] = TsState{-1, -1, 0, -1, 0, seek ? seek[b] : 0, seek_end ? seek_end[b] : (1 << 30), 0};
   // {position of the previous step, index of the next pick, ticket}: the fused pick of a replay embeds at counters[0] + 1
   const int counters[4] = {pos - 1, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(h->d_counters, counters, sizeof(counters), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(h->d_ts_state, st.data(), sizeof(TsState) * batch, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemsetAsync(h->d_done_count, 0, sizeof(int), s));
-  HIP_TRY(hipMemcpyAsync(h->d_temperature, &temperature, sizeof(float), hipMemcpyHostToDevice, s));
-  if (u) HIP_TRY(hipMemcpyAsync(h->d_u_all, u, sizeof(double) * (size_t)max_new * batch, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->dw.counters, counters, sizeof(counters), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->dw.ts_state, st.data(), sizeof(TsState) * batch, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(h->dw.done_count, 0, sizeof(int), s));
+  HIP_TRY(hipMemcpyAsync(h->dw.temperature, &temperature, sizeof(float), hipMemcpyHostToDevice, s));
+  if (u) HIP_TRY(hipMemcpyAsync(h->dw.u_all, u, sizeof(double) * (size_t)max_new * batch, hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));
   TsPickArgs pa = ts_args(h, rules, mask, mask_first);
-  pa.u_all = u ? h->d_u_all : nullptr;
+  pa.u_all = u ? h->dw.u_all : nullptr;
   int steps_run = 1;      // picks made = decoder steps replayed + the final pick
   if (max_new > 1) {
-    const crispy_asr::TsKey key{h->dec_max_keys <= 128 ? 0 : h->dec_max_keys <= 256 ? 1 : 2, u ? 1 : 0, batch, xgroup, rules, mask, 1};
+    const crispy_asr::TsKey key{key_class(pass.max_keys), u ? 1 : 0, batch, xgroup, rules, mask, 1};
     TsPickArgs pf = pa;                     // the pick of a replay also embeds its token and moves the counters on
-    pf.fuse = step_fuse(h);
+    pf.fuse = step_fuse(h, pass);
     int ran = 0;
     rc = run_steps(h, key, batch, max_new - 1, [&]() -> int {
       HIP_TRY(ts_pick(pf, batch, s));
-      return decoder_step(h, batch, 0, true, true, s, true);
+      return token_step(h, pass, s);
     }, &ran);
     if (rc != CRISPY_OK) return rc;
     steps_run += ran;
@@ -808,11 +842,11 @@ int decode_ts(crispy_asr* h, const float* d_enc, int batch, const std::vector<st
   HIP_TRY(ts_pick(pa, batch, s));   // the last pick needs no further decoder step
   std::vector<int> all((size_t)steps_run * batch), tids((size_t)steps_run * batch);
   std::vector<float> plog((size_t)steps_run * batch), nosp(batch);
-  HIP_TRY(hipMemcpyAsync(all.data(), h->d_tokens_all, all.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(tids.data(), h->d_tids_all, tids.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(plog.data(), h->d_plog_all, plog.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(nosp.data(), h->d_nosp, nosp.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(st.data(), h->d_ts_state, sizeof(TsState) * batch, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(all.data(), h->dw.tokens_all, all.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(tids.data(), h->dw.tids_all, tids.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(plog.data(), h->dw.plog_all, plog.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(nosp.data(), h->dw.nosp, nosp.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(st.data(), h->dw.ts_state, sizeof(TsState) * batch, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   for (int b = 0; b < batch; ++b) {
     const int n = st[b].n < max_new ? st[b].n : max_new;
@@ -843,12 +877,12 @@ int beam_collect(crispy_asr* h, int rows, int n_dec, int n_cand, int max_new, in
   std::vector<BeamRow> br((size_t)rows);
   std::vector<int> rec_tok((size_t)steps_run * rows), rec_tid((size_t)steps_run * rows), rec_par((size_t)steps_run * rows);
   std::vector<float> rec_plog((size_t)steps_run * rows), nosp(rows);
-  HIP_TRY(hipMemcpyAsync(rec_tok.data(), h->d_tokens_all, rec_tok.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(rec_tid.data(), h->d_tids_all, rec_tid.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(rec_par.data(), h->d_beam_rec_parent, rec_par.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(rec_plog.data(), h->d_plog_all, rec_plog.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(br.data(), h->d_beam_row, sizeof(BeamRow) * rows, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(nosp.data(), h->d_nosp, nosp.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(rec_tok.data(), h->dw.tokens_all, rec_tok.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(rec_tid.data(), h->dw.tids_all, rec_tid.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(rec_par.data(), h->dw.beam_rec_parent, rec_par.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(rec_plog.data(), h->dw.plog_all, rec_plog.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(br.data(), h->dw.beam_row, sizeof(BeamRow) * rows, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(nosp.data(), h->dw.nosp, nosp.size() * sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   for (int r = 0; r < rows; ++r) {
     const int n = br[r].n;
@@ -902,57 +936,29 @@ int decode_beam(crispy_asr* h, const float* d_enc, int n_clips, int n_dec, int n
   if (n_clips < 1 || n_dec < 1 || n_dec > TS_MAX_CAND || n_cand < 1 || n_cand > TS_MAX_CAND || (int)clip_prompts.size() != n_clips ||
       (int)rng.size() != rows || max_new < 1)
     return fail(CRISPY_ERR_INVALID_ARG, "beam decode: %d clips x %d decoders, %d candidates", n_clips, n_dec, n_cand);
-  int n_rows = 0;
-  for (const auto& p : clip_prompts) {
-    if (p.empty()) return fail(CRISPY_ERR_INVALID_ARG, "beam decode: empty prompt");
-    for (int t : p)
-      if (t < 0 || t >= h->hp.n_vocab) return fail(CRISPY_ERR_INVALID_ARG, "beam decode: prompt token %d out of range", t);
-    n_rows = std::max(n_rows, (int)p.size());
-  }
-  if (n_rows + max_new > h->hp.n_text_ctx)
-    return fail(CRISPY_ERR_INVALID_ARG, "beam decode: %d prompt + %d new tokens exceed n_text_ctx %d", n_rows, max_new, h->hp.n_text_ctx);
-  int rc = reserve_dec(h, rows, n_clips);
+  std::vector<std::vector<int>> prompts((size_t)rows);      // every decoder of a clip starts from the clip's prompt
+  for (int r = 0; r < rows; ++r) prompts[r] = clip_prompts[r / n_dec];
+  PassStart ps;
+  int rc = begin_pass(h, "beam decode:", prompts, n_dec, max_new, 0, true, &ps);
   if (rc != CRISPY_OK) return rc;
-  choose_decode_path(h);
-  h->dec_max_keys = n_rows + max_new;
+  const DecodePass& pass = ps.pass;
   const int dt = h->hp.n_text_state, C = h->hp.n_text_ctx, L = (int)h->dec.size();
-  std::vector<int> off(rows), tok_mat((size_t)rows * n_rows, 0);
-  for (int r = 0; r < rows; ++r) {
-    const std::vector<int>& p = clip_prompts[r / n_dec];
-    off[r] = n_rows - (int)p.size();
-    std::copy(p.begin(), p.end(), tok_mat.begin() + (size_t)r * n_rows + off[r]);
-  }
   // the bytes of a row's cache the decoders of a clip can differ in (the generated positions), and the variates of the pass:
   // both grow with the pass, and a captured step holds their addresses
-  const size_t esz = self_kv_half(h, rows) ? 2 : 4;
+  const size_t esz = self_kv_half(h, pass) ? 2 : 4;
   const size_t row_bytes = (size_t)C * 2 * dt * esz, pos_bytes = (size_t)2 * dt * esz;
   const size_t need_kv = (size_t)L * rows * (size_t)max_new * pos_bytes, need_u = (size_t)max_new * rows * n_cand * sizeof(double);
-  if (need_kv > h->beam_kv_bytes || need_u > h->beam_u_bytes) {
+  if (need_kv > h->dw.beam_kv.bytes || need_u > h->dw.beam_u.bytes) {
     HIP_TRY(hipStreamSynchronize(s));
     h->drop_graphs();
-    if (need_kv > h->beam_kv_bytes) {
-      if (h->d_beam_kv) (void)hipFree(h->d_beam_kv);
-      h->d_beam_kv = nullptr; h->beam_kv_bytes = 0;
-      HIP_TRY(hipMalloc(&h->d_beam_kv, need_kv));
-      h->beam_kv_bytes = need_kv;
-    }
-    if (need_u > h->beam_u_bytes) {
-      if (h->d_beam_u) (void)hipFree(h->d_beam_u);
-      h->d_beam_u = nullptr; h->beam_u_bytes = 0;
-      HIP_TRY(hipMalloc(&h->d_beam_u, need_u));
-      h->beam_u_bytes = need_u;
-    }
+    HIP_TRY(h->dw.beam_kv.grow(need_kv));
+    HIP_TRY(h->dw.beam_u.grow(need_u));
   }
-  HIP_TRY(hipMemcpyAsync(h->d_row_off, off.data(), sizeof(int) * rows, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  struct OffGuard { crispy_asr* h; ~OffGuard() { h->cur_row_off = nullptr; h->cur_xgroup = 1; } } guard{h};
-  h->cur_row_off = h->d_row_off;
-  h->cur_xgroup = n_dec;
   int pos = 0;
-  rc = prefill(h, d_enc, rows, tok_mat.data(), n_rows, s, &pos);
+  rc = prefill(h, pass, d_enc, ps.tok_mat.data(), ps.n_rows, s, &pos);
   if (rc != CRISPY_OK) return rc;
   const Special sp = special_tokens(h);
-  HIP_TRY(softmax_prob_f32(h->d_logits, h->hp.n_vocab, logits_ld(h), sp.nosp, h->d_nosp, rows, s));
+  HIP_TRY(softmax_prob_f32(h->dw.logits, h->hp.n_vocab, logits_ld(h), sp.nosp, h->dw.nosp, rows, s));
   const float t_eff = temperature > 0.f ? temperature : 1.0f;       // temperature 0: the logits as they are (x / 1)
   // u[step][row][k]: variate step * n_cand + k of the row's generator (a copy draws; the generator is moved on below)
   std::vector<double> u((size_t)max_new * rows * n_cand);
@@ -970,35 +976,35 @@ int decode_beam(crispy_asr* h, const float* d_enc, int n_clips, int n_dec, int n
   }
   // {position of the previous step, index of the next pick, ticket, spare, first generated cache row, max_new}
   const int counters[6] = {pos - 1, 0, 0, 0, pos, max_new};
-  HIP_TRY(hipMemcpyAsync(h->d_counters, counters, sizeof(counters), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(h->d_ts_state, st.data(), sizeof(TsState) * rows, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(h->d_beam_row, br.data(), sizeof(BeamRow) * rows, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemsetAsync(h->d_done_count, 0, sizeof(int), s));
-  HIP_TRY(hipMemcpyAsync(h->d_temperature, &t_eff, sizeof(float), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(h->d_beam_u, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->dw.counters, counters, sizeof(counters), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->dw.ts_state, st.data(), sizeof(TsState) * rows, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->dw.beam_row, br.data(), sizeof(BeamRow) * rows, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(h->dw.done_count, 0, sizeof(int), s));
+  HIP_TRY(hipMemcpyAsync(h->dw.temperature, &t_eff, sizeof(float), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->dw.beam_u, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));
   TsPickArgs pa = ts_args(h, rules, mask, mask_first);
-  pa.u_all = h->d_beam_u;
+  pa.u_all = h->dw.beam_u;
   pa.n_cand = n_cand;
-  pa.cand_tok = h->d_beam_cand; pa.cand_tid = h->d_beam_cand + (size_t)h->dcap_batch * TS_MAX_CAND;
-  pa.cand_plog = reinterpret_cast<float*>(h->d_beam_cand + 2 * (size_t)h->dcap_batch * TS_MAX_CAND);
+  pa.cand_tok = h->dw.beam_cand; pa.cand_tid = h->dw.beam_cand + (size_t)h->dw.cap_rows * TS_MAX_CAND;
+  pa.cand_plog = reinterpret_cast<float*>(h->dw.beam_cand + 2 * (size_t)h->dw.cap_rows * TS_MAX_CAND);
   BeamArgs ba{};
-  ba.st = h->d_ts_state; ba.row = h->d_beam_row;
+  ba.st = h->dw.ts_state; ba.row = h->dw.beam_row;
   ba.cand_tok = pa.cand_tok; ba.cand_tid = pa.cand_tid; ba.cand_plog = pa.cand_plog;
   ba.n_dec = n_dec; ba.n_cand = n_cand; ba.rows = rows; ba.beg = sp.beg; ba.eot = h->eot; ba.rules = rules; ba.delta_min = TS_DELTA_MIN;
-  ba.rec_tok = h->d_tokens_all; ba.rec_tid = h->d_tids_all; ba.rec_plog = h->d_plog_all; ba.rec_parent = h->d_beam_rec_parent;
-  ba.parent = h->d_beam_parent; ba.feed = h->d_tok; ba.done_count = h->d_done_count; ba.counters = h->d_counters;
+  ba.rec_tok = h->dw.tokens_all; ba.rec_tid = h->dw.tids_all; ba.rec_plog = h->dw.plog_all; ba.rec_parent = h->dw.beam_rec_parent;
+  ba.parent = h->dw.beam_parent; ba.feed = h->dw.tok; ba.done_count = h->dw.done_count; ba.counters = h->dw.counters;
   int steps_run = 1;
   if (max_new > 1) {
-    const crispy_asr::TsKey key{h->dec_max_keys <= 128 ? 0 : h->dec_max_keys <= 256 ? 1 : 2, 16 + n_cand, rows, n_dec, rules, mask, 1};
+    const crispy_asr::TsKey key{key_class(pass.max_keys), 16 + n_cand, rows, n_dec, rules, mask, 1};
     BeamArgs bf = ba;                       // the deal of a replay also embeds the rows' next inputs and moves the counters on
-    bf.fuse = step_fuse(h);
+    bf.fuse = step_fuse(h, pass);
     int ran = 0;
     rc = run_steps(h, key, rows, max_new - 1, [&]() -> int {
       HIP_TRY(ts_pick(pa, rows, s));
       HIP_TRY(beam_advance(bf, n_clips, s));
-      HIP_TRY(beam_kv_reorder(h->d_selfkv, h->d_beam_kv, h->d_beam_parent, L, rows, (long)row_bytes, (long)pos_bytes, h->d_counters, s));
-      return decoder_step(h, rows, 0, true, true, s, true);
+      HIP_TRY(beam_kv_reorder(h->dw.selfkv, h->dw.beam_kv, h->dw.beam_parent, L, rows, (long)row_bytes, (long)pos_bytes, h->dw.counters, s));
+      return token_step(h, pass, s);
     }, &ran);
     if (rc != CRISPY_OK) return rc;
     steps_run += ran;
@@ -1010,11 +1016,12 @@ int decode_beam(crispy_asr* h, const float* d_enc, int n_clips, int n_dec, int n
 
 // pick a token from the current logits (step-aware suppression), record it, run the next step on it,
 // advance the device counters: the body of one generated token
-int generation_body(crispy_asr* h, int batch, hipStream_t s) {
-  const StepFuse f = step_fuse(h);         // pick + embedding of the pick + counters in one launch
-  HIP_TRY(argmax_f32(h->d_logits, h->d_suppress, h->d_suppress_first, h->d_counters + 1, h->hp.n_vocab, logits_ld(h), h->d_tok,
-                     h->d_tokens_all, h->d_best, batch, s, h->eot, h->d_finished, h->d_done_count, &f));
-  return decoder_step(h, batch, 0, true, true, s, true);
+int generation_body(crispy_asr* h, const DecodePass& pass, hipStream_t s) {
+  const int batch = pass.rows;
+  const StepFuse f = step_fuse(h, pass);         // pick + embedding of the pick + counters in one launch
+  HIP_TRY(argmax_f32(h->dw.logits, h->d_suppress, h->d_suppress_first, h->dw.counters + 1, h->hp.n_vocab, logits_ld(h), h->dw.tok,
+                     h->dw.tokens_all, h->dw.best, batch, s, h->eot, h->dw.finished, h->dw.done_count, &f));
+  return token_step(h, pass, s);
 }
 
 
@@ -1055,10 +1062,10 @@ int crispy_asr_stage_logits_device(crispy_asr* h, const float* d_x, int batch, f
   if (rc != CRISPY_OK) return rc;
   const int dt = h->hp.n_text_state, V = h->hp.n_vocab;
   // through the decode step's own buffers, so that the code under test is decoder_step's last block
-  HIP_TRY(hipMemcpyAsync(h->d_dx, d_x, sizeof(float) * batch * dt, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->dw.dx, d_x, sizeof(float) * batch * dt, hipMemcpyDeviceToDevice, s));
   rc = decoder_logits(h, batch, s);
   if (rc != CRISPY_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(d_logits, sizeof(float) * (size_t)V, h->d_logits, sizeof(float) * (size_t)logits_ld(h), sizeof(float) * (size_t)V,
+  HIP_TRY(hipMemcpy2DAsync(d_logits, sizeof(float) * (size_t)V, h->dw.logits, sizeof(float) * (size_t)logits_ld(h), sizeof(float) * (size_t)V,
                            (size_t)batch, hipMemcpyDeviceToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));
   return CRISPY_OK;
@@ -1087,43 +1094,38 @@ int crispy_asr_decode_greedy_lang_device(crispy_asr* h, const float* d_enc, int 
       return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_decode_greedy_device: prompt token %d out of range", prompt[i]);
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  int rc = reserve_dec(h, batch);
+  std::vector<std::vector<int>> prompts((size_t)batch, std::vector<int>(prompt, prompt + n_prompt));
+  if (lang_tokens && n_prompt > 1)
+    for (int b = 0; b < batch; ++b) prompts[b][1] = lang_tokens[b];        // per-clip language token
+  // (no row offsets: the prompts are equally long, and the null pointer is a kernel argument of this pass's captured steps)
+  PassStart ps;
+  int rc = begin_pass(h, "decode:", prompts, 1, max_new, 0, false, &ps);
   if (rc != CRISPY_OK) return rc;
-  choose_decode_path(h);
-  h->dec_max_keys = n_prompt + max_new;
+  const DecodePass& pass = ps.pass;
   const int V = h->hp.n_vocab;
   int pos = 0;
-  {
-    std::vector<int> tok_mat((size_t)batch * n_prompt);
-    for (int b = 0; b < batch; ++b)
-      for (int j = 0; j < n_prompt; ++j) {
-        const int t = (j == 1 && lang_tokens) ? lang_tokens[b] : prompt[j];        // per-clip language token
-        if (t < 0 || t >= h->hp.n_vocab) return fail(CRISPY_ERR_INVALID_ARG, "decode: language token %d out of range", t);
-        tok_mat[(size_t)b * n_prompt + j] = t;
-      }
-    rc = prefill(h, d_enc, batch, tok_mat.data(), n_prompt, s, &pos);
-  }
+  rc = prefill(h, pass, d_enc, ps.tok_mat.data(), ps.n_rows, s, &pos);
   if (rc != CRISPY_OK) return rc;
   const int counters[4] = {pos - 1, 0, 0, 0};     // {position of the previous step, index of the next pick, ticket} (StepFuse)
-  HIP_TRY(hipMemcpyAsync(h->d_counters, counters, sizeof(counters), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemsetAsync(h->d_done_count, 0, sizeof(int), s));
-  HIP_TRY(hipMemsetAsync(h->d_finished, 0, sizeof(int) * batch, s));
+  HIP_TRY(hipMemcpyAsync(h->dw.counters, counters, sizeof(counters), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(h->dw.done_count, 0, sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(h->dw.finished, 0, sizeof(int) * batch, s));
   HIP_TRY(hipStreamSynchronize(s));
   int steps_run = 1;      // picks made: replayed decoder steps + the final pick
   if (max_new > 1) {
-    const crispy_asr::TsKey key{h->dec_max_keys <= 128 ? 0 : h->dec_max_keys <= 256 ? 1 : 2, 2, batch, 1, 0, nullptr, 1};
+    const crispy_asr::TsKey key{key_class(pass.max_keys), 2, batch, 1, 0, nullptr, 1};
     int ran = 0;
-    rc = run_steps(h, key, batch, max_new - 1, [&]() -> int { return generation_body(h, batch, s); }, &ran);
+    rc = run_steps(h, key, batch, max_new - 1, [&]() -> int { return generation_body(h, pass, s); }, &ran);
     if (rc != CRISPY_OK) return rc;
     steps_run += ran;
   }
   // the last pick needs no further decoder step
-  HIP_TRY(argmax_f32(h->d_logits, h->d_suppress, h->d_suppress_first, h->d_counters + 1, V, logits_ld(h), h->d_tok, h->d_tokens_all,
-                     h->d_best, batch, s, h->eot, h->d_finished, h->d_done_count));
+  HIP_TRY(argmax_f32(h->dw.logits, h->d_suppress, h->d_suppress_first, h->dw.counters + 1, V, logits_ld(h), h->dw.tok, h->dw.tokens_all,
+                     h->dw.best, batch, s, h->eot, h->dw.finished, h->dw.done_count));
   std::vector<int> all((size_t)max_new * batch, h->eot);
   std::vector<float> best((size_t)max_new * batch, 0.f);
-  HIP_TRY(hipMemcpyAsync(all.data(), h->d_tokens_all, (size_t)steps_run * batch * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(best.data(), h->d_best, (size_t)steps_run * batch * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(all.data(), h->dw.tokens_all, (size_t)steps_run * batch * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(best.data(), h->dw.best, (size_t)steps_run * batch * sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   for (int b = 0; b < batch; ++b) {
     int n = max_new;
@@ -1208,10 +1210,9 @@ int crispy_asr_detect_language_device(crispy_asr* h, const float* d_enc, int bat
   if (rc != CRISPY_OK) return rc;
   const int sot = h->eot + 1, n_lang = 99 + (V - 51865);
   std::vector<int> tok(batch, sot);
-  HIP_TRY(hipMemcpyAsync(h->d_tok, tok.data(), sizeof(int) * batch, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->dw.tok, tok.data(), sizeof(int) * batch, hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));
-  h->dec_max_keys = 1;      // one position: the self K|V form (f16 in mode 1) must not depend on what the last decode call left here
-  rc = decoder_step(h, batch, 0, false, true, s);
+  rc = prompt_step(h, DecodePass{batch, 1, 1, nullptr}, 0, 1, true, s);      // a pass of one position
   if (rc != CRISPY_OK) return rc;
   if (!h->d_lang_mask) {
     std::vector<unsigned char> m(V, 1);
@@ -1219,8 +1220,8 @@ int crispy_asr_detect_language_device(crispy_asr* h, const float* d_enc, int bat
     HIP_TRY(hipMalloc(&h->d_lang_mask, V));
     HIP_TRY(hipMemcpy(h->d_lang_mask, m.data(), V, hipMemcpyHostToDevice));
   }
-  HIP_TRY(argmax_f32(h->d_logits, h->d_lang_mask, nullptr, nullptr, V, logits_ld(h), h->d_tok, nullptr, nullptr, batch, s));
-  HIP_TRY(hipMemcpyAsync(lang_tokens_out, h->d_tok, sizeof(int) * batch, hipMemcpyDeviceToHost, s));
+  HIP_TRY(argmax_f32(h->dw.logits, h->d_lang_mask, nullptr, nullptr, V, logits_ld(h), h->dw.tok, nullptr, nullptr, batch, s));
+  HIP_TRY(hipMemcpyAsync(lang_tokens_out, h->dw.tok, sizeof(int) * batch, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return CRISPY_OK;
 } CRISPY_CATCH_RET("crispy_asr_detect_language_device")
@@ -1235,12 +1236,8 @@ int crispy_asr_transcribe_tokens(crispy_asr* h, const float* pcm, long pcm_strid
   HIP_TRY(hipSetDevice(h->device));
   int rc = reserve_enc(h, batch);
   if (rc != CRISPY_OK) return rc;
-  if (!h->w_pcm || pcm_stride > h->cap_pcm_stride) {
-    if (h->w_pcm) (void)hipFree(h->w_pcm);
-    h->w_pcm = nullptr;
-    HIP_TRY(hipMalloc(&h->w_pcm, (size_t)h->cap_batch * pcm_stride * sizeof(float)));
-    h->cap_pcm_stride = pcm_stride;
-  }
+  rc = reserve_pcm(h, pcm_stride);
+  if (rc != CRISPY_OK) return rc;
   HIP_TRY(hipMemcpyAsync(h->w_pcm, pcm, (size_t)batch * pcm_stride * sizeof(float), hipMemcpyHostToDevice, h->stream));
   rc = crispy_mel_compute_device(h->mel, h->w_pcm, pcm_stride, n_samples, batch, nullptr, h->w_melt, h->stream);
   if (rc != CRISPY_OK) return rc;

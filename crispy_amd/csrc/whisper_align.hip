@@ -338,14 +338,6 @@ struct Carve {
   }
 };
 
-int grow(void** buf, size_t* cap, size_t need) {
-  if (need <= *cap) return CRISPY_OK;
-  if (*buf) { (void)hipFree(*buf); *buf = nullptr; *cap = 0; }
-  HIP_TRY(hipMalloc(buf, need));
-  *cap = need;
-  return CRISPY_OK;
-}
-
 int resolve_heads(const crispy_asr* h, const int* heads, int n_heads, std::vector<int>& out) {
   const int L = h->hp.n_text_layer, H = h->hp.n_text_head;
   out.clear();
@@ -398,16 +390,14 @@ int run_alignment(crispy_asr* h, const float* d_enc, const std::vector<std::vect
   int n_slots = 0;
   for (int k = 0; k < n_heads; ++k)
     if (A.slot[heads[2 * k]] < 0) A.slot[heads[2 * k]] = n_slots++;
-  int rc = grow(reinterpret_cast<void**>(&A.q), &A.q_bytes, (size_t)n_slots * batch * n_rows * dt * sizeof(float));
-  if (rc != CRISPY_OK) return rc;
+  HIP_TRY(A.q.grow((size_t)n_slots * batch * n_rows * dt * sizeof(float)));
   const int ld_f = Tn;
   int max_n = 0;
   for (int b = 0; b < batch; ++b) max_n = std::max(max_n, (int)rows[b].size() - n_sot - 1 + n_frames[b] / 2);
   const size_t need = 256 * 8 + (size_t)batch * n_heads * n_rows * sizeof(float2) + (d_matrix_out ? 0 : (size_t)batch * ld_rows * ld_f * sizeof(float)) +
                       (size_t)batch * n_rows * sizeof(int) + (size_t)batch * sizeof(AlignClip) + (size_t)n_heads * (sizeof(int2) + sizeof(int));
-  rc = grow(&A.ws, &A.ws_bytes, need);
-  if (rc != CRISPY_OK) return rc;
-  Carve cv{static_cast<char*>(A.ws)};
+  HIP_TRY(A.ws.grow(need));
+  Carve cv{A.ws.as<char>()};
   float2* d_stats = cv.take<float2>((size_t)batch * n_heads * n_rows);
   float* d_matrix = d_matrix_out ? d_matrix_out : cv.take<float>((size_t)batch * ld_rows * ld_f);
   int* d_jumps = cv.take<int>((size_t)batch * n_rows);
@@ -415,41 +405,37 @@ int run_alignment(crispy_asr* h, const float* d_enc, const std::vector<std::vect
   int2* d_heads = cv.take<int2>((size_t)n_heads);
   int* d_head_layer = cv.take<int>((size_t)n_heads);
   std::vector<AlignClip> hc((size_t)batch);
-  std::vector<int> off((size_t)batch), tok_mat((size_t)batch * n_rows, 0);
   for (int b = 0; b < batch; ++b) {
     const int R = (int)rows[b].size();
-    off[b] = n_rows - R;
-    std::copy(rows[b].begin(), rows[b].end(), tok_mat.begin() + (size_t)b * n_rows + off[b]);
-    hc[b] = AlignClip{off[b], R, n_frames[b] / 2, n_sot, R - n_sot - 1};
+    hc[b] = AlignClip{n_rows - R, R, n_frames[b] / 2, n_sot, R - n_sot - 1};      // (the left padding begin_pass gives the row)
   }
   std::vector<int2> hh((size_t)n_heads);
   std::vector<int> hl((size_t)n_heads);
   for (int k = 0; k < n_heads; ++k) { hh[k] = make_int2(A.slot[heads[2 * k]], heads[2 * k + 1]); hl[k] = heads[2 * k]; }
-  // the pass: decode_ts's left padding, one cross K|V per clip (the window's own), a fixed key bound (not the batch's
-  // longest row: a clip's arithmetic must not depend on its neighbours)
-  rc = reserve_dec(h, batch, batch);
-  if (rc != CRISPY_OK) return rc;
-  choose_decode_path(h);
-  HIP_TRY(hipMemcpyAsync(h->d_row_off, off.data(), sizeof(int) * batch, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d_clips, hc.data(), sizeof(AlignClip) * batch, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d_heads, hh.data(), sizeof(int2) * n_heads, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d_head_layer, hl.data(), sizeof(int) * n_heads, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  // the pass: decode_ts's left padding, one cross K|V per clip (the window's own), a fixed key bound (not the batch's
+  // longest row: a clip's arithmetic must not depend on its neighbours).  Its wait for the row offsets is the wait for
+  // the three uploads above too.
+  PassStart ps;
+  int rc = begin_pass(h, "alignment:", rows, 1, 0, C, true, &ps);
+  if (rc != CRISPY_OK) {
+    (void)hipStreamSynchronize(s);      // the uploads above read host vectors of this frame
+    return rc;
+  }
   {
-    struct Guard { crispy_asr* h; ~Guard() { h->cur_row_off = nullptr; h->cur_xgroup = 1; h->align.on = false; h->align.rows = 0; } } guard{h};
-    h->dec_max_keys = C;
-    h->cur_row_off = h->d_row_off;
-    h->cur_xgroup = 1;
+    struct Guard { crispy_asr* h; ~Guard() { h->align.on = false; h->align.rows = 0; } } guard{h};
     A.rows = n_rows;
     A.on = true;
     int pos = 0;
-    rc = prefill(h, d_enc, batch, tok_mat.data(), n_rows, s, &pos);
+    rc = prefill(h, ps.pass, d_enc, ps.tok_mat.data(), n_rows, s, &pos);
     if (rc != CRISPY_OK) return rc;
   }
   AlignArgs a{};
   a.q = A.q; a.q_clip_stride = (long)n_rows * dt; a.q_slot_stride = (long)batch * a.q_clip_stride; a.dt = dt;
   a.kv16 = h->enc_precision == 1 ? 1 : 0;
-  a.kv = a.kv16 ? static_cast<const void*>(h->d_xkv_h) : static_cast<const void*>(h->d_xkv);
+  a.kv = a.kv16 ? static_cast<const void*>(h->dw.xkv_h) : static_cast<const void*>(h->dw.xkv);
   a.q16 = h->dec_attn16 && h->enc_precision == 1 ? 1 : 0;
   a.kv_layer_stride = (long)batch * Tn * 2 * dt; a.kv_clip_stride = (long)Tn * 2 * dt; a.Tn = Tn;
   a.heads = d_heads; a.head_layer = d_head_layer; a.n_heads = n_heads; a.clips = d_clips;
@@ -539,9 +525,8 @@ int crispy_asr_dtw_device(crispy_asr* h, const float* d_x, int n_rows, int n_col
   hipStream_t s = h->stream;
   AlignWs& A = h->align;
   const size_t L = (size_t)n_rows + n_cols;
-  int rc = grow(&A.ws, &A.ws_bytes, 256 * 4 + L * 2 * sizeof(int) + (size_t)n_rows * sizeof(int) + sizeof(int) + sizeof(AlignClip));
-  if (rc != CRISPY_OK) return rc;
-  Carve cv{static_cast<char*>(A.ws)};
+  HIP_TRY(A.ws.grow(256 * 4 + L * 2 * sizeof(int) + (size_t)n_rows * sizeof(int) + sizeof(int) + sizeof(AlignClip)));
+  Carve cv{A.ws.as<char>()};
   int* d_path = cv.take<int>(L * 2);
   int* d_jumps = cv.take<int>((size_t)n_rows);
   int* d_n = cv.take<int>(1);

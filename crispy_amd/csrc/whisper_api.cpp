@@ -177,38 +177,10 @@ void free_ws(crispy_asr* h) {
   h->cap_batch = 0;
   h->cap_pcm_stride = 0;
 }
+// the captured steps hold the workspace's addresses: they go first
 void free_dec_ws(crispy_asr* h) {
-  for (float** p : {&h->d_xkv, &h->d_selfkv, &h->d_dx, &h->d_dxn, &h->d_dq, &h->d_datt, &h->d_dh, &h->d_logits, &h->d_best})
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-  if (h->d_tok) { (void)hipFree(h->d_tok); h->d_tok = nullptr; }
-  if (h->d_tokens_all) { (void)hipFree(h->d_tokens_all); h->d_tokens_all = nullptr; }
-  if (h->d_counters) { (void)hipFree(h->d_counters); h->d_counters = nullptr; }
   h->drop_graphs();
-  if (h->d_ts_state) { (void)hipFree(h->d_ts_state); h->d_ts_state = nullptr; }
-  if (h->d_tids_all) { (void)hipFree(h->d_tids_all); h->d_tids_all = nullptr; }
-  if (h->d_done_count) { (void)hipFree(h->d_done_count); h->d_done_count = nullptr; }
-  if (h->d_finished) { (void)hipFree(h->d_finished); h->d_finished = nullptr; }
-  if (h->d_xkv_h) { (void)hipFree(h->d_xkv_h); h->d_xkv_h = nullptr; }
-  if (h->d_plog_all) { (void)hipFree(h->d_plog_all); h->d_plog_all = nullptr; }
-  if (h->d_nosp) { (void)hipFree(h->d_nosp); h->d_nosp = nullptr; }
-  if (h->d_u_all) { (void)hipFree(h->d_u_all); h->d_u_all = nullptr; }
-  if (h->d_ts_x) { (void)hipFree(h->d_ts_x); h->d_ts_x = nullptr; }
-  if (h->d_beam_kv) { (void)hipFree(h->d_beam_kv); h->d_beam_kv = nullptr; h->beam_kv_bytes = 0; }
-  if (h->d_beam_parent) { (void)hipFree(h->d_beam_parent); h->d_beam_parent = nullptr; }
-  if (h->d_beam_row) { (void)hipFree(h->d_beam_row); h->d_beam_row = nullptr; }
-  if (h->d_beam_cand) { (void)hipFree(h->d_beam_cand); h->d_beam_cand = nullptr; }
-  if (h->d_beam_rec_parent) { (void)hipFree(h->d_beam_rec_parent); h->d_beam_rec_parent = nullptr; }
-  if (h->d_beam_u) { (void)hipFree(h->d_beam_u); h->d_beam_u = nullptr; h->beam_u_bytes = 0; }
-  if (h->d_temperature) { (void)hipFree(h->d_temperature); h->d_temperature = nullptr; }
-  if (h->d_row_off) { (void)hipFree(h->d_row_off); h->d_row_off = nullptr; }
-  if (h->d_gvpart) { (void)hipFree(h->d_gvpart); h->d_gvpart = nullptr; }
-  for (int i = 0; i < 3; ++i) {
-    if (h->d_fx[i]) { (void)hipFree(h->d_fx[i]); h->d_fx[i] = nullptr; }
-    if (h->d_fpart[i]) { (void)hipFree(h->d_fpart[i]); h->d_fpart[i] = nullptr; }
-  }
-  h->cur_row_off = nullptr;
-  h->dcap_batch = 0;
-  h->dcap_xclips = 0;
+  h->dw = DecWs{};
 }
 
 int reserve_enc(crispy_asr* h, int batch) {
@@ -232,6 +204,16 @@ int reserve_enc(crispy_asr* h, int batch) {
   // 0..7 of the first 256-clip call, intermittently: tests/test_gpu_pipeline.py cfg5)
   HIP_TRY(hipDeviceSynchronize());
   h->cap_batch = batch;
+  return CRISPY_OK;
+}
+
+// the PCM rows of the encoder workspace [cap_batch][stride] (after reserve_enc), regrown when a call's rows are longer
+int reserve_pcm(crispy_asr* h, long stride) {
+  if (h->w_pcm && stride <= h->cap_pcm_stride) return CRISPY_OK;
+  if (h->w_pcm) (void)hipFree(h->w_pcm);
+  h->w_pcm = nullptr;
+  HIP_TRY(hipMalloc(&h->w_pcm, (size_t)h->cap_batch * stride * sizeof(float)));
+  h->cap_pcm_stride = stride;
   return CRISPY_OK;
 }
 
@@ -874,12 +856,8 @@ int crispy_asr_encode(crispy_asr* h, const float* pcm, long pcm_stride, const in
   HIP_TRY(hipSetDevice(h->device));
   int rc = reserve_enc(h, batch);
   if (rc != CRISPY_OK) return rc;
-  if (!h->w_pcm || pcm_stride > h->cap_pcm_stride) {
-    if (h->w_pcm) (void)hipFree(h->w_pcm);
-    h->w_pcm = nullptr;
-    HIP_TRY(hipMalloc(&h->w_pcm, (size_t)h->cap_batch * pcm_stride * sizeof(float)));
-    h->cap_pcm_stride = pcm_stride;
-  }
+  rc = reserve_pcm(h, pcm_stride);
+  if (rc != CRISPY_OK) return rc;
   HIP_TRY(hipMemcpyAsync(h->w_pcm, pcm, (size_t)batch * pcm_stride * sizeof(float), hipMemcpyHostToDevice, h->stream));
   rc = crispy_mel_compute_device(h->mel, h->w_pcm, pcm_stride, n_samples, batch, nullptr, h->w_melt, h->stream);
   if (rc != CRISPY_OK) return rc;

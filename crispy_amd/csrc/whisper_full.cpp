@@ -387,7 +387,6 @@ class BatchCall {
       : h(h_), pcm(pcm_), n(n_), batch(batch_), opts(opts_), cancel(cancel_), sp(special_tokens(h_)) {}
   ~BatchCall() {
     for (auto* r : impl) delete r;
-    if (d_enc_rep) (void)hipFree(d_enc_rep);
   }
   int prepare();                       // argument checks, which clips are live, the prompt, one result object per clip
   int run();                           // everything on the device
@@ -442,8 +441,7 @@ class BatchCall {
   // the encoder outputs of a group of fallback clips, gathered (one per clip).  The group size changes from pass to pass
   // (every pending clip in one group at n_dec == 1, kLadderRowsMax / n_dec otherwise): kept by capacity and regrown -- round 5
   // sized it from the first group that needed it, and a later, larger group overflowed it
-  float* d_enc_rep = nullptr;
-  int enc_rep_clips = 0;
+  DevBuf<float> d_enc_rep;
   size_t enc_clip = 0;
 };
 
@@ -524,12 +522,8 @@ int BatchCall::upload_and_encode() {
   HIP_TRY(hipSetDevice(h->device));
   int rc = reserve_enc(h, nb);
   if (rc != CRISPY_OK) return rc;
-  if (!h->w_pcm || (long)stride > h->cap_pcm_stride) {
-    if (h->w_pcm) (void)hipFree(h->w_pcm);
-    h->w_pcm = nullptr;
-    HIP_TRY(hipMalloc(&h->w_pcm, (size_t)h->cap_batch * stride * sizeof(float)));
-    h->cap_pcm_stride = (long)stride;
-  }
+  rc = reserve_pcm(h, (long)stride);
+  if (rc != CRISPY_OK) return rc;
   // every clip straight from the caller's memory into its row (no packed host copy: for the 21 chunks of a ten-minute
   // recording that was 40 MB zero-filled, copied and then copied again); what lies behind a clip's end in its row is
   // never read -- the log-mel takes n_samples per clip
@@ -643,14 +637,10 @@ int BatchCall::setup_ladder() {
 }
 
 int BatchCall::reserve_enc_rep(int n_clips) {
-  if (n_clips <= enc_rep_clips) return CRISPY_OK;
-  if (d_enc_rep) {                                    // copies into / decodes from the old buffer may be in flight
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    (void)hipFree(d_enc_rep);
-    d_enc_rep = nullptr; enc_rep_clips = 0;
-  }
-  HIP_TRY(hipMalloc(&d_enc_rep, (size_t)n_clips * enc_clip * sizeof(float)));
-  enc_rep_clips = n_clips;
+  const size_t need = (size_t)n_clips * enc_clip * sizeof(float);
+  if (need <= d_enc_rep.bytes) return CRISPY_OK;
+  if (d_enc_rep) HIP_TRY(hipStreamSynchronize(h->stream));      // copies into / decodes from the old buffer may be in flight
+  HIP_TRY(d_enc_rep.alloc(need));
   return CRISPY_OK;
 }
 

@@ -1,8 +1,8 @@
 // whisper_internal.h -- what the four translation units of the Whisper engine share (not part of the ABI):
 //   whisper_api.cpp    the model container: tensors, derived copies, precision modes, encoder, workspaces
 //   ggml_load.cpp      whisper.cpp GGML model files: reader, de-quantiser, resident block bookkeeping
-//   decode_steps.cpp   the decoder: workspaces, the step forms (fused / matrix-vector / skinny), prompts, captured steps,
-//                      the greedy / timestamp-rule / beam passes over one window
+//   decode_steps.cpp   the decoder: its workspace (DecWs), the start of a pass (DecodePass), the step forms (fused / matrix-vector /
+//                      skinny), prompts, captured steps, the greedy / timestamp-rule / beam passes over one window
 //   whisper_full.cpp   whisper_full on top of them: seek loop, temperature ladder, segments, results, the recording chunker
 //   whisper_align.hip  word-level timestamps: the alignment pass, its kernels, crispy_asr_{align,dtw}_device (reached from
 //                      whisper_full.cpp through a hook that file installs: not linked, a dtw request is unsupported)
@@ -69,22 +69,70 @@ struct DecLayer {
   const float *qkv_lw, *qkv_ls, *qkv_lc, *xq_lw, *xq_ls, *xq_lc, *fc1_lw, *fc1_ls, *fc1_lc;
 };
 
+// A device allocation that belongs to its holder: freed with it (or when a fresh one is assigned over it), moved, never
+// copied.  alloc replaces what it holds, grow only when that is too small -- neither carries the contents over.  After a
+// failed alloc it holds nothing (bytes 0): the next call allocates again.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t n) {
+    if (p) (void)hipFree(p);
+    p = nullptr; bytes = 0;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n);
+    if (e == hipSuccess) bytes = n; else p = nullptr;
+    return e;
+  }
+  hipError_t grow(size_t n) { return n <= bytes ? hipSuccess : alloc(n); }
+  operator T*() const { return p; }
+  template <class U> U* as() const { return reinterpret_cast<U*>(p); }      // the same bytes as another element type (the f16 caches)
+};
+
 // Word alignment (whisper_align.hip): while an alignment prefill runs (`on`), layer_cross_and_mlp copies the cross-q rows
 // of every layer that holds an alignment head into q [slot][clip][row][n_text_state] -- the rows that layer's own
 // cross-attention reads.  Buffers grow on demand and live as long as the handle.
 struct AlignWs {
-  float* q = nullptr; size_t q_bytes = 0;
-  void* ws = nullptr; size_t ws_bytes = 0;     // row statistics, matrix, DTW outputs, per-clip arguments
+  DevBuf<float> q;
+  DevBuf<void> ws;                             // row statistics, matrix, DTW outputs, per-clip arguments
   std::vector<int> slot;                       // [n_text_layer]: the layer's slot in q, -1 = none
   int rows = 0;                                // token rows per clip of the running pass
   bool on = false;
-  AlignWs() = default;
-  AlignWs(const AlignWs&) = delete;
-  AlignWs& operator=(const AlignWs&) = delete;
-  ~AlignWs() {
-    if (q) (void)hipFree(q);
-    if (ws) (void)hipFree(ws);
-  }
+};
+
+// The decoder workspace (reserve_dec: sizes; [cap_rows] = one entry per row the workspace holds).  Captured steps hold these
+// addresses: free_dec_ws drops them before it lets the buffers go.
+struct DecWs {
+  int cap_rows = 0, cap_xclips = 0;          // rows / audio clips the workspace holds
+  DevBuf<float> xkv, selfkv, dx, dxn, dq, datt, dh, logits, best;
+  DevBuf<int> tok;
+  DevBuf<int> tokens_all;
+  DevBuf<int> counters;                      // [0] position, [1] generation step (device-side, advanced in-graph)
+  // timestamp-mode decoding (whisper.cpp no_timestamps = false)
+  DevBuf<TsState> ts_state;                  // [cap_rows]
+  DevBuf<int> tids_all;                      // [n_text_ctx][cap_rows]
+  DevBuf<int> done_count;
+  DevBuf<int> finished;                      // [cap_rows] plain greedy decoding: clip has produced its EOT
+  DevBuf<void> xkv_h;                        // f16 copy of the cross K|V (precision mode 1)
+  DevBuf<float> plog_all;                    // [n_text_ctx][cap_rows] log-probability of every pick
+  DevBuf<float> nosp;                        // [cap_rows] no_speech_prob of the window
+  DevBuf<double> u_all;                      // [n_text_ctx][cap_rows] uniform variates of a sampling pass (drawn on the host)
+  DevBuf<float> ts_x;                        // [cap_rows][TS_SCRATCH_ROW] the sampling pick's filtered rows
+  DevBuf<float> temperature;                 // device scalar
+  DevBuf<int> row_off;                       // [cap_rows] left padding of every clip's prompt (cache rows)
+  DevBuf<int> beam_parent;                   // [cap_rows]
+  DevBuf<BeamRow> beam_row;                  // [cap_rows] a decoder's bookkeeping (beam_advance_kernel)
+  DevBuf<int> beam_cand;                     // [3][cap_rows][TS_MAX_CAND] the candidates of a step: ids, timestamp ids, log-probabilities
+  DevBuf<int> beam_rec_parent;               // [n_text_ctx][cap_rows] the row a step's sequence came from
+  DevBuf<float> fx[3];                       // fused step: residual stream after the self / cross / MLP input sums [rows][dt]
+  DevBuf<float> fpart[3];                    // fused step: partial rows of the self / cross out-projection [heads][rows][dt], MLP [dt / 32][rows][dt]
+  DevBuf<float> gvpart;                      // gemv step (catalog widths): partial soft-maxes of the cross-attention [GEMV_MAX_M][heads][XA_PARTS][XA_PART_FLOATS]
+  // beam search, grown with the pass (decode_beam)
+  DevBuf<void> beam_kv;                      // the rows' cache bytes in flight between parents and children
+  DevBuf<double> beam_u;                     // [max_new][rows][n_cand] the variates of a beam pass
 };
 
 }  // namespace asr
@@ -124,9 +172,6 @@ struct crispy_asr {
   bool dec_attn16 = false;                   // precision mode 2: + the query and the normalised probabilities rounded to f16 inside every attention
   bool ln16_ready = false;
   bool fused_path = true;                    // generated tokens through the fused step kernels when the model allows (CRISPY_ASR_DECODE=stages: never)
-  float* d_fx[3] = {nullptr, nullptr, nullptr};      // fused step: residual stream after the self / cross / MLP input sums [rows][dt]
-  float* d_fpart[3] = {nullptr, nullptr, nullptr};
-  float* d_gvpart = nullptr;                 // gemv step (catalog widths): partial soft-maxes of the cross-attention [GEMV_MAX_M][heads][XA_PARTS][XA_PART_FLOATS]   // fused step: partial rows of the self / cross out-projection [heads][rows][dt], MLP [dt / 32][rows][dt]
   bool half_ready = false;                   // every f16 weight copy of mode 1 exists (set after the last one and a stream sync)
   int xcd_swizzle = 1;                       // mode 1 GEMMs: column tiles of a row tile on one XCD (CRISPY_ASR_XCD=0 turns it off)
   std::vector<crispy::asr::EncLayer> enc;
@@ -140,25 +185,8 @@ struct crispy_asr {
   float *w_melt = nullptr, *w_pcm = nullptr, *w_h1 = nullptr, *w_x = nullptr, *w_xn = nullptr, *w_qkv = nullptr,
         *w_att = nullptr, *w_h = nullptr, *w_enc = nullptr;
   long cap_pcm_stride = 0;
-  // decoder workspace
-  int dcap_batch = 0, dcap_xclips = 0;       // rows / audio clips the decoder workspace holds
-  float *d_xkv = nullptr, *d_selfkv = nullptr, *d_dx = nullptr, *d_dxn = nullptr, *d_dq = nullptr, *d_datt = nullptr,
-        *d_dh = nullptr, *d_logits = nullptr, *d_best = nullptr;
-  int* d_tok = nullptr;
-  int* d_tokens_all = nullptr;
-  int* d_counters = nullptr;                 // [0] position, [1] generation step (device-side, advanced in-graph)
-  // one captured decode step, replayed per generated token -- one per key class (<= 128 / 256 / 512 positions: the
-  // self-attention kernel of mode 1 is baked into the capture).  A transcribe call with previous-text conditioning
-  // alternates between classes from window to window (bare prompt, then prompt + past): with a single slot every window
-  // re-instantiated the graph (1 - 2 ms each).
-
-  int dec_max_keys = 0;                      // positions the current decode call can reach (prompt + new tokens)
+  crispy::asr::DecWs dw;                     // decoder workspace
   // timestamp-mode decoding (whisper.cpp no_timestamps = false)
-  crispy::TsState* d_ts_state = nullptr;             // [dcap_batch]
-  int* d_tids_all = nullptr;                 // [n_text_ctx][dcap_batch]
-  int* d_done_count = nullptr;
-  int* d_finished = nullptr;                 // [dcap_batch] plain greedy decoding: clip has produced its EOT
-  void* d_xkv_h = nullptr;                   // f16 copy of the cross K|V (precision mode 1)
   unsigned char* d_ts_mask = nullptr;        // [n_vocab] whisper.cpp's always-suppressed specials
   unsigned char* d_ts_mask_first = nullptr;  // ... plus suppress_blank (" " and EOT) at the first position
   unsigned char* d_ts_mask_nst = nullptr;    // the two masks with whisper.cpp's non-speech tokens added (opts.suppress_nst; built on first use)
@@ -183,21 +211,6 @@ struct crispy_asr {
     }
   };
   std::map<TsKey, hipGraphExec_t> ts_graphs;
-  float* d_plog_all = nullptr;               // [n_text_ctx][dcap_batch] log-probability of every pick
-  float* d_nosp = nullptr;                   // [dcap_batch] no_speech_prob of the window
-  float* d_ts_x = nullptr;                   // [dcap_batch][TS_SCRATCH_ROW] the sampling pick's filtered rows
-  double* d_u_all = nullptr;                 // [n_text_ctx][dcap_batch] uniform variates of a sampling pass (drawn on the host)
-  float* d_temperature = nullptr;            // device scalar
-  int* d_row_off = nullptr;                  // [dcap_batch] left padding of every clip's prompt (cache rows)
-  const int* cur_row_off = nullptr;          // d_row_off while a window decode is running, else nullptr (decoder_step reads it)
-  void* d_beam_kv = nullptr; size_t beam_kv_bytes = 0;      // beam search: the rows' cache bytes in flight between parents and children
-  int* d_beam_parent = nullptr;              // [dcap_batch]
-  crispy::BeamRow* d_beam_row = nullptr;             // [dcap_batch] a decoder's bookkeeping (beam_advance_kernel)
-  int* d_beam_cand = nullptr;                // [3][dcap_batch][TS_MAX_CAND] the candidates of a step: ids, timestamp ids, log-probabilities
-  int* d_beam_rec_parent = nullptr;          // [n_text_ctx][dcap_batch] the row a step's sequence came from
-  double* d_beam_u = nullptr; size_t beam_u_bytes = 0;      // [max_new][rows][n_cand] the variates of a beam pass
-  int cur_xgroup = 1;                        // rows per audio clip while a window decode is running: the best-of decoders of a clip are
-                                             // rows of their own (own self K|V cache) over ONE cross K|V (decode_ts)
   void drop_graphs() {
     for (auto& kv : ts_graphs)
       if (kv.second) (void)hipGraphExecDestroy(kv.second);
@@ -218,6 +231,7 @@ std::map<std::string, size_t> expected_tensors(const crispy_asr_hparams& hp);
 int dq(crispy_asr* h, const QRef& r, bool f16, const float* gamma, hipStream_t s, const void** out);
 void free_dec_ws(crispy_asr* h);
 int reserve_enc(crispy_asr* h, int batch);
+int reserve_pcm(crispy_asr* h, long stride);
 GemmArgs gemm(const float* A, long lda, const float* W, long ldw, float* C, long ldc, const float* bias, int M, int N, int K);
 
 // ---- decode_steps.cpp ----
@@ -244,8 +258,26 @@ int decode_beam(crispy_asr* h, const float* d_enc, int n_clips, int n_dec, int n
                 float temperature, const std::vector<std::mt19937*>& rng, int* tokens_out, int* tids_out, float* plog_out,
                 float* nosp_out, int* n_out);
 
-void choose_decode_path(crispy_asr* h);
-int prefill(crispy_asr* h, const float* d_enc, int batch, const int* tok_mat, int n_rows, hipStream_t s, int* pos_out);
+// What a decode call fixes for all of its steps.  begin_pass makes it and every step function takes it: which kernel form
+// runs, whether the self K|V cache holds halves or floats and how many key slots an attention gets follow from the call
+// in hand, never from what an earlier call left on the handle.
+struct DecodePass {
+  int rows = 0;                    // sequences, each with a self K|V cache of its own
+  int xgroup = 1;                  // rows per audio clip: the best-of / beam decoders of a clip are rows of their own over ONE cross K|V
+  int max_keys = 0;                // positions the call can reach (prompt + new tokens)
+  const int* row_off = nullptr;    // [rows] left padding of every row's prompt (cache rows); null: none
+};
+struct PassStart {
+  DecodePass pass;
+  std::vector<int> tok_mat;        // [rows][n_rows] the prompts right-aligned, token 0 in front of the shorter ones
+  int n_rows = 0;                  // the longest prompt
+};
+// Begins a pass over one prompt per row: checks the tokens and lengths (`who` names the pass in a message: "decode:"),
+// left-pads, reserves the workspace, reads the decode-path knob and -- row_offsets -- uploads the padding per row and waits
+// for it.  max_keys = fixed_keys, or (0) the longest prompt + max_new.
+int begin_pass(crispy_asr* h, const char* who, const std::vector<std::vector<int>>& prompts, int xgroup, int max_new, int fixed_keys,
+               bool row_offsets, PassStart* out);
+int prefill(crispy_asr* h, const DecodePass& pass, const float* d_enc, const int* tok_mat, int n_rows, hipStream_t s, int* pos_out);
 
 // ---- whisper_full.cpp ----
 int build_ts_masks(crispy_asr* h);
