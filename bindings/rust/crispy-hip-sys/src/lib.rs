@@ -33,7 +33,7 @@ pub const CRISPY_RN_FRAME_SIZE: usize = 480;
 pub const CRISPY_RN_WEIGHT_BYTES: usize = 87503;
 pub const CRISPY_RN_TAPS: usize = 72;
 /// The ABI this file was written against (crispy_hip.h: CRISPY_ABI_VERSION); every constructor checks it.
-pub const CRISPY_ABI_VERSION: c_int = 5;
+pub const CRISPY_ABI_VERSION: c_int = 6;
 pub const CRISPY_MEL_FRAMES: usize = 3000;
 pub const CRISPY_MEL_BINS: usize = 201;
 
@@ -203,6 +203,14 @@ extern "C" {
     pub fn crispy_rn_process_device(h: *mut crispy_rn, d_in: *const c_float, d_out: *mut c_float, d_vad: *mut c_float, d_taps: *mut c_float, n_frames: c_int, layout: crispy_rn_layout, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_rn_process_s16(h: *mut crispy_rn, input: *const i16, out: *mut i16, vad: *mut c_float, n_frames: c_int, layout: crispy_rn_layout) -> c_int;
     pub fn crispy_rn_process_s16_device(h: *mut crispy_rn, d_in: *const i16, d_out: *mut i16, d_vad: *mut c_float, n_frames: c_int, layout: crispy_rn_layout, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_rn_adapter_configure(h: *mut crispy_rn, input_rate: c_float, volume: c_float) -> c_int;
+    pub fn crispy_rn_adapter_set_volume(h: *mut crispy_rn, volume: c_float) -> c_int;
+    pub fn crispy_rn_adapter_produced_rate_hz(h: *const crispy_rn, rate_hz: *mut c_float) -> c_int;
+    pub fn crispy_rn_push_out_len(h: *const crispy_rn, n_in: c_long) -> c_long;
+    pub fn crispy_rn_push_device(h: *mut crispy_rn, d_in: *const c_float, in_stride: c_long, n_in: c_long, d_out: *mut c_float, out_stride: c_long, d_frames48: *mut c_float, frames_stride: c_long, d_vad: *mut c_float, n_out: *mut c_long, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_rn_push(h: *mut crispy_rn, input: *const c_float, in_stride: c_long, n_in: c_long, out: *mut c_float, out_stride: c_long, vad: *mut c_float, n_out: *mut c_long) -> c_int;
+    pub fn crispy_rn_last_push_ms(h: *mut crispy_rn, adapt_in_ms: *mut c_float, adapt_out_ms: *mut c_float) -> c_int;
+    pub fn crispy_linear_resampler_count(input_rate: c_float, output_rate: c_float, n_before: c_long, n_in: c_long) -> c_long;
     pub fn crispy_rn_synchronize(h: *mut crispy_rn) -> c_int;
     pub fn crispy_rn_set_timing(h: *mut crispy_rn, enable: c_int) -> c_int;
     pub fn crispy_rn_last_kernel_ms(h: *mut crispy_rn, frame_kernel_ms: *mut c_float, total_ms: *mut c_float) -> c_int;
@@ -401,6 +409,47 @@ impl BatchDenoiser {
         }
         let vp = vad.map_or(std::ptr::null_mut(), |v| v.as_mut_ptr());
         check(unsafe { crispy_rn_process(self.h, input.as_ptr(), output.as_mut_ptr(), vp, n_frames as c_int, CRISPY_RN_LAYOUT_TBF) })
+    }
+    /// `RnnNoiseProcessor::new(input_rate, _, volume)` (audio.rs:216-240) for every stream: a capture rate that is not
+    /// within 1 Hz of 48 kHz puts the reference's `LinearResampler` in front; fresh adapter and denoiser state.
+    pub fn configure_adapter(&mut self, input_rate: f32, volume: f32) -> Result<(), CrispyError> {
+        // SAFETY: valid handle.
+        check(unsafe { crispy_rn_adapter_configure(self.h, input_rate, volume) })
+    }
+    /// `NsState::set_volume` (audio.rs:337-343); holds from the next `push` on.
+    pub fn set_volume(&mut self, volume: f32) -> Result<(), CrispyError> {
+        check(unsafe { crispy_rn_adapter_set_volume(self.h, volume) })
+    }
+    /// `NsState::produced_rate_hz` (audio.rs:352-357).
+    pub fn produced_rate_hz(&self) -> Result<f32, CrispyError> {
+        let mut r = 0f32;
+        check(unsafe { crispy_rn_adapter_produced_rate_hz(self.h, &mut r) })?;
+        Ok(r)
+    }
+    /// Samples per stream the next `push` of `n_in` samples returns.
+    pub fn push_out_len(&self, n_in: usize) -> Result<usize, CrispyError> {
+        let n = unsafe { crispy_rn_push_out_len(self.h, n_in as c_long) };
+        if n < 0 {
+            check(n as c_int)?;
+        }
+        Ok(n as usize)
+    }
+    /// The body of one capture callback: what a loop of `RnnNoiseProcessor::push_sample` (audio.rs:242-295) over `n_in`
+    /// raw samples of every stream returns, from one call.  input: `n_streams` rows of `n_in` samples (+-1, at the
+    /// configured capture rate); output: `n_streams` rows of `push_out_len(n_in)` samples (resized here).  Returns the
+    /// samples per stream.  (The VAD probabilities, which push_sample discards, are available through the C entry point.)
+    pub fn push(&mut self, input: &[f32], n_in: usize, output: &mut Vec<f32>) -> Result<usize, CrispyError> {
+        if input.len() != n_in * self.n_streams {
+            return Err(CrispyError { code: CRISPY_ERR_INVALID_ARG, message: "BatchDenoiser::push: input length".into() });
+        }
+        let want = self.push_out_len(n_in)?;
+        output.resize(want * self.n_streams, 0.0);
+        let mut got: c_long = 0;
+        // SAFETY: input holds n_streams rows of n_in samples, output n_streams rows of `want` samples -- what the library
+        // announced for this push; the call returns when output is complete.
+        check(unsafe { crispy_rn_push(self.h, input.as_ptr(), n_in as c_long, n_in as c_long, output.as_mut_ptr(), want as c_long, std::ptr::null_mut(), &mut got) })?;
+        debug_assert_eq!(got as usize, want);
+        Ok(got as usize)
     }
 }
 impl Drop for BatchDenoiser {

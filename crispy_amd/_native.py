@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CRISPY_HIP_LIB") or os.path.join(_HERE, "libcrispy_hip.so")
 
 RN_FRAME = 480
-ABI_VERSION = 5
+ABI_VERSION = 6
 RN_WEIGHT_BYTES = 87503
 RN_TAPS = 72
 RN_DBG_FLOATS = 4304
@@ -29,6 +29,9 @@ RN_SYMBOLS = (
     "crispy_rn_debug_capture", "crispy_rn_debug_read", "crispy_rn_stage_tansig_device",
     "crispy_host_register", "crispy_host_unregister",
     "crispy_rn_weights_from_file", "crispy_rn_create_from_file", "crispy_selftest_exception_guard",
+    "crispy_rn_adapter_configure", "crispy_rn_adapter_set_volume", "crispy_rn_adapter_produced_rate_hz",
+    "crispy_rn_push_out_len", "crispy_rn_push_device", "crispy_rn_push", "crispy_rn_last_push_ms",
+    "crispy_linear_resampler_count",
 )
 
 
@@ -159,6 +162,17 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_rn_set_timing.argtypes = [C.c_void_p, C.c_int]
     L.crispy_rn_last_kernel_ms.argtypes = [C.c_void_p, f32p, f32p]
     L.crispy_rn_stage_tansig_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    L.crispy_rn_adapter_configure.argtypes = [C.c_void_p, C.c_float, C.c_float]
+    L.crispy_rn_adapter_set_volume.argtypes = [C.c_void_p, C.c_float]
+    L.crispy_rn_adapter_produced_rate_hz.argtypes = [C.c_void_p, f32p]
+    L.crispy_rn_push_out_len.argtypes = [C.c_void_p, C.c_long]
+    L.crispy_rn_push_out_len.restype = C.c_long
+    L.crispy_rn_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_long,
+                                        C.c_void_p, C.POINTER(C.c_long), C.c_void_p]
+    L.crispy_rn_push.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.POINTER(C.c_long)]
+    L.crispy_rn_last_push_ms.argtypes = [C.c_void_p, f32p, f32p]
+    L.crispy_linear_resampler_count.argtypes = [C.c_float, C.c_float, C.c_long, C.c_long]
+    L.crispy_linear_resampler_count.restype = C.c_long
     L.crispy_rn_debug_capture.argtypes = [C.c_void_p, C.c_int]
     L.crispy_rn_debug_read.argtypes = [C.c_void_p, C.c_int, f32p, C.c_size_t]
     L.crispy_mel_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]

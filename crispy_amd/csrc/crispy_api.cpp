@@ -3,10 +3,11 @@
 // Host side of the batched RNNoise path: owns the per-stream state tensors in HBM, the device
 // tables, the repacked weights and the workspace; enqueues high-pass -> frame -> history-roll
 // kernels per chunk of frames.  No CPU compute path exists here: without a gfx950 device every
-// constructor fails.
+// constructor fails.  The handle is declared in rn_handle.h; the capture-rate adapter (crispy_rn_push*) is rn_adapter.hip.
 #include "../../include/crispy_hip.h"
 #include "api_util.h"
 #include "rn_common.h"
+#include "rn_handle.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -197,63 +198,7 @@ void pack_weights(std::vector<uint32_t>& out, const int8_t* w) {
 }
 
 
-}  // namespace
-
-struct crispy_rn {
-  int device = 0;
-  int B = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t hp_stream = nullptr;   // helper stream: the latency-bound high-pass runs beside the frame kernel
-  hipEvent_t ev_begin = nullptr;
-  std::vector<hipEvent_t> ev_hp;     // one per sub-chunk: high-pass done
-  // constants
-  RnTables* d_tab = nullptr;
-  uint32_t* d_wpack = nullptr;
-  // state
-  float* d_hp_mem = nullptr;
-  float* d_synth = nullptr;       // overlap-add tails [B][480]
-  float* d_ceps = nullptr;
-  float* d_lastg = nullptr;
-  float* d_rnn = nullptr;
-  float* d_last_gain = nullptr;
-  int* d_last_period = nullptr;
-  int* d_memid = nullptr;
-  // workspace
-  float* d_xhp = nullptr;
-  long xhp_stride = 0;
-  // Frames per high-pass launch.  A high-pass wave keeps the VALU of its SIMD ~35 % busy (nine dependent f64
-  // operations per sample) and a frame-kernel launch lasts as long as its slowest wave, so a sub-chunk's high-pass as
-  // one 0.3 ms kernel delays the four frame waves that share its SIMD by ~0.08 ms per launch (0.8 ms per 100-frame
-  // step, measured with CRISPY_RN_HP=upfront).  As kernels of two frames the 64 waves land on other SIMDs every
-  // ~50 us and the delay spreads: 8.17 -> 7.68 ms per step (1 frame: 7.83, 3: 8.07, 4: 8.15, 6: 8.0, whole: 8.17).
-  int hp_split = 2;
-  // Waves per stream of the frame kernel: 1 = one wave runs the whole frame (every pipe of the chip is busy from ~4 waves per
-  // SIMD = 4096 streams up); 3 = the frame's three stages on three waves, a frame apart (rn_frame3_kernel: a stream
-  // advances a frame per ~10 k quad-cycles instead of ~26 k -- what counts while there are fewer waves than SIMD slots).
-  // Chosen at create time from the stream count; CRISPY_RN_WAVES=1|3 overrides (tests run both forms).
-  int waves = 1;
-  int hp_ahead = 0;          // > 0: the high-pass runs at most this many sub-chunks in front of the frame kernels
-  std::vector<hipEvent_t> ev_fr;   // one per sub-chunk: frame kernel done (only used with hp_ahead)
-  bool hp_deep = false;      // the high-pass requests 32 samples ahead (80 registers): set where a wave of it fits beside the frame waves
-  bool hp_upfront = false;   // diagnostic (CRISPY_RN_HP=upfront): every high-pass of a call segment first, on the main stream
-  float* d_dbg = nullptr;
-  // host-pointer staging
-  float* d_stage_in = nullptr;
-  float* d_stage_out = nullptr;
-  float* d_stage_vad = nullptr;
-  size_t stage_frames = 0;
-  // pipelined host path: copy-in / compute / copy-out streams and per-piece events
-  hipStream_t h2d_stream = nullptr;
-  hipStream_t d2h_stream = nullptr;
-  std::vector<hipEvent_t> ev_in, ev_done;
-  // timing
-  bool timing = false;
-  std::vector<hipEvent_t> ev;  // per segment: begin, (frame_begin, frame_end) x sub-chunks, end
-  size_t ev_used = 0;
-  std::vector<int> seg_subs;   // sub-chunks of every timed segment
-};
-
-namespace {
+// (struct crispy_rn: rn_handle.h)
 
 void free_all(crispy_rn* h) {
   if (!h) return;
@@ -264,6 +209,7 @@ void free_all(crispy_rn* h) {
                   h->d_stage_out, h->d_stage_vad};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
+  if (h->ad && h->ad_free) h->ad_free(h->ad);
   for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ev_hp) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ev_fr) (void)hipEventDestroy(e);
@@ -921,3 +867,12 @@ int crispy_rn_debug_read(crispy_rn* h, int stream, float* dst, size_t n_floats) 
 } CRISPY_CATCH_RET("crispy_rn_debug_read")
 
 }  // extern "C"
+
+// what rn_adapter.hip (crispy_rn_push*) uses of this file
+namespace crispy {
+int rn_zero_state(crispy_rn* h, int stream) { return zero_state(h, stream); }
+int rn_process_frames_device(crispy_rn* h, const float* d_in, float* d_out, float* d_vad, int n_frames, long stride_t, long stride_b,
+                             hipStream_t s) {
+  return process_device_impl(h, d_in, d_out, d_vad, nullptr, n_frames, stride_t, stride_b, s);
+}
+}  // namespace crispy

@@ -127,4 +127,42 @@ hipError_t rn_launch_frames(const RnArgs& a, hipStream_t s, int waves_per_stream
 hipError_t rn_launch_roll_history(const RnArgs& a, hipStream_t s);
 hipError_t rn_launch_tansig(const RnTables* tab, const float* x, float* y, long n, int sigmoid, hipStream_t s);
 
+// ---- crispy_rn_push*: RnnNoiseProcessor::push_sample around the frame kernels (rn_adapter.hip) ----
+// One push of n_in capture samples per stream.  The 48 kHz sequence of the push is, per stream, the `carry_len` samples
+// left over from the previous push followed by `n_new` new ones: the capture samples themselves (idx == nullptr, rates
+// within 1 Hz) or LinearResampler outputs -- new sample r interpolates capture samples idx[r] - 1 and idx[r] of this push
+// (idx[r] == 0: the previous push's last sample) at t[r]; both arrays are the same for every stream of the handle.  The
+// first `frames` x 480 of them go x32768 to `stage` (and `frames48`), the rest, unscaled, to carry_new.
+struct RnAdaptIn {
+  const float* in;         // [B][in_stride]
+  long in_stride;
+  long n_in;
+  const int* idx;          // [n_new] or null
+  const float* t;          // [n_new]
+  int carry_len;           // < 480
+  long n_new;
+  int frames;
+  const float* carry_old;  // [B][480]
+  float* carry_new;        // [B][480]
+  const float* last_old;   // [B]
+  float* last_new;         // [B]: in[b][n_in - 1]
+  float* stage;            // [B][frames * 480]: what the frame kernels read as a stream-major (BTF) tensor
+  float* frames48;         // [B][frames_stride] or null
+  long frames_stride;
+  int B;
+};
+// d_out[b][r] = clamp(y[b][skip + r] / 32768, -1, 1) * volume for r < n_out (a multiple of 480)
+struct RnAdaptOut {
+  const float* y;          // [B][y_stride], 16-byte aligned rows
+  long y_stride;
+  long skip;               // 480 while the first frame is dropped, else 0
+  float* out;              // [B][out_stride]
+  long out_stride;
+  long n_out;
+  float volume;
+  int B;
+};
+hipError_t rn_launch_adapt_in(const RnAdaptIn& a, hipStream_t s);
+hipError_t rn_launch_adapt_out(const RnAdaptOut& a, hipStream_t s);
+
 }  // namespace crispy

@@ -5,6 +5,7 @@
 * `RnnNoiseProcessor`   -- the adapter of audio.rs:202-315 (`push_sample`, x32768, clamp, volume,
                            first-frame drop, optional input LinearResampler), batched: one
                            processor object drives B streams that are pushed in lock step.
+                           `push_block` is the same on the device (crispy_rn_push), a block per call.
 * `LinearResampler`     -- audio.rs:73-134.
 
 All arithmetic of `process_frame` runs in libcrispy_hip.so on the GPU; nothing here falls back
@@ -135,6 +136,60 @@ class DenoiseState:
         N.check(self._L.crispy_rn_process_device(self._h, d_in, d_out, d_vad or None, d_taps or None,
                                                  int(n_frames), lay, stream or None), self._L)
 
+    # -- the capture-rate adapter (RnnNoiseProcessor on the device: crispy_rn_adapter_* / crispy_rn_push*) -----
+    def adapter_configure(self, input_rate: float, volume: float = 1.0):
+        """`RnnNoiseProcessor::new(input_rate, _, volume)` for every stream: fresh adapter and denoiser state."""
+        N.check(self._L.crispy_rn_adapter_configure(self._h, float(input_rate), float(volume)), self._L)
+
+    def adapter_set_volume(self, volume: float):
+        N.check(self._L.crispy_rn_adapter_set_volume(self._h, float(volume)), self._L)
+
+    def adapter_produced_rate_hz(self) -> float:
+        r = C.c_float()
+        N.check(self._L.crispy_rn_adapter_produced_rate_hz(self._h, C.byref(r)), self._L)
+        return r.value
+
+    def push_out_len(self, n_in: int) -> int:
+        """Samples per stream the NEXT push of n_in samples returns."""
+        n = self._L.crispy_rn_push_out_len(self._h, int(n_in))
+        if n < 0:
+            N.check(int(n), self._L)
+        return int(n)
+
+    def push(self, x: np.ndarray, want_vad: bool = False):
+        """`crispy_rn_push`: x [B, n] raw capture samples in +-1 at the configured rate -> out [B, n_out] (and, with
+        want_vad, the VAD probabilities [frames, B] of the frames this push completed)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[0] != self.n_streams:
+            raise ValueError(f"push: x must be [{self.n_streams}, n]")
+        n_in = x.shape[1]
+        n_out = self.push_out_len(n_in)
+        out = np.empty((self.n_streams, n_out), dtype=np.float32)
+        # frames completed: those returned, and the dropped first one if this push completes it
+        vad = np.full((n_out // FRAME_SIZE + 1, self.n_streams), np.nan, dtype=np.float32) if want_vad else None
+        got = C.c_long()
+        N.check(self._L.crispy_rn_push(self._h, x.ctypes.data, n_in, n_in, out.ctypes.data, max(n_out, 1),
+                                       vad.ctypes.data if want_vad else None, C.byref(got)), self._L)
+        assert got.value == n_out
+        if want_vad:
+            return out, vad[~np.isnan(vad[:, 0])]
+        return out
+
+    def push_device(self, d_in: int, in_stride: int, n_in: int, d_out: int, out_stride: int, d_frames48: int = 0,
+                    frames_stride: int = 0, d_vad: int = 0, stream: int = 0) -> int:
+        """`crispy_rn_push_device` on device pointers; returns n_out (known on return, the work is only enqueued)."""
+        got = C.c_long()
+        N.check(self._L.crispy_rn_push_device(self._h, d_in, int(in_stride), int(n_in), d_out, int(out_stride),
+                                              d_frames48 or None, int(frames_stride), d_vad or None, C.byref(got),
+                                              stream or None), self._L)
+        return int(got.value)
+
+    def last_push_ms(self):
+        """With `set_timing(True)`: device time of (rn_adapt_in_kernel, rn_adapt_out_kernel) of the last push."""
+        a, b = C.c_float(), C.c_float()
+        N.check(self._L.crispy_rn_last_push_ms(self._h, C.byref(a), C.byref(b)), self._L)
+        return a.value, b.value
+
     def stage_tansig_device(self, d_x: int, d_y: int, n: int, sigmoid: bool = False):
         """tansig_approx / sigmoid_approx as the frame kernel evaluates them (stage entry point for parity tests)."""
         N.check(self._L.crispy_rn_stage_tansig_device(self._h, d_x, d_y, int(n), int(sigmoid), None), self._L)
@@ -219,15 +274,24 @@ class RnnNoiseProcessor:
         self.first_frame = True
         self.max_output_len = int(self.input_rate)
         self.denoise = DenoiseState(weights, n_streams, device)
+        self.denoise.adapter_configure(input_rate, self.volume)     # the device form of all of the above: push_block
         self.input_buf: deque = deque()
         self.output_buf: deque = deque()
         self.resample_pos = 0.0
 
     def set_volume(self, volume: float):
         self.volume = float(min(max(volume, 0.0), 1.0))
+        self.denoise.adapter_set_volume(self.volume)
 
     def produced_rate_hz(self) -> float:
         return self.input_rate
+
+    def push_block(self, x: np.ndarray) -> np.ndarray:
+        """A loop of `push_sample` over the columns of x [B, n], as one `crispy_rn_push`: resampler, framing, scaling,
+        process_frame, clamp, volume and the first-frame drop all run on the device.  Returns [B, n_out] (n_out = 480 per
+        completed frame; possibly 0).  The carried samples and the resampler state live in the handle, those of
+        `push_sample` in this object: drive a processor through one of the two.  `next_sample`'s ring is not fed."""
+        return self.denoise.push(x)
 
     def push_sample(self, samples) -> Optional[np.ndarray]:
         samples = np.atleast_1d(np.asarray(samples, dtype=np.float32))

@@ -79,8 +79,9 @@ const char *crispy_version(void);
  *   pipeline entry points removed).   3: round 5.   4: round 6 (this header: crispy_asr_transcribe_recording and its
  *   CRISPY_ERR_CANCELLED, the int16 sample transport crispy_rn_process_s16*).   5: word-level timestamps
  *   (crispy_asr_opts::dtw_token_timestamps / dtw_heads / n_dtw_heads, crispy_asr_result::token_t_dtw / n_words / words,
- *   crispy_asr_word, crispy_asr_align_device, crispy_asr_dtw_device). */
-#define CRISPY_ABI_VERSION 5
+ *   crispy_asr_word, crispy_asr_align_device, crispy_asr_dtw_device).   6: the capture-rate adapter on the device
+ *   (crispy_rn_adapter_*, crispy_rn_push*, crispy_linear_resampler_count). */
+#define CRISPY_ABI_VERSION 6
 int crispy_abi_version(void);
 /* Number of usable gfx950 devices (0 when there is none; never fails). */
 int crispy_device_count(void);
@@ -133,7 +134,7 @@ int crispy_rn_n_launches(int n_frames);
  * process_frame for every stream, n_frames consecutive frames each (audio.rs:268).
  * in/out are HOST pointers to n_frames*n_streams*480 floats in `layout`; samples are f32 in
  * int16 range (the x32768 / /32768, clamp, volume and first-frame drop of audio.rs:261-278 stay
- * with the caller).  vad (nullable) receives the value process_frame returns,
+ * with the caller; crispy_rn_push below does them on the device).  vad (nullable) receives the value process_frame returns,
  * [n_frames][n_streams].  Copies through a device staging buffer; returns when `out` is complete.
  * Calls above 8 MB are pipelined in pieces of frames: copy-in of piece i+1, the kernels of piece i and
  * copy-out of piece i-1 overlap (the copy-out side on its own host thread, because copies from pageable
@@ -179,6 +180,50 @@ int crispy_rn_process_s16(crispy_rn *h, const int16_t *in, int16_t *out, float *
                           crispy_rn_layout layout);
 int crispy_rn_process_s16_device(crispy_rn *h, const int16_t *d_in, int16_t *d_out, float *d_vad, int n_frames,
                                  crispy_rn_layout layout, void *hip_stream);
+
+/*
+ * RnnNoiseProcessor (audio.rs:202-295) for all streams of a handle at once: raw capture samples at any rate in, denoised
+ * samples out, every arithmetic step on the device -- the input LinearResampler (audio.rs:73-134), the assembly of
+ * 480-sample frames from whatever arrives, x32768, process_frame, /32768, clamp, volume, the dropped first frame.  One
+ * crispy_rn_push per capture callback replaces the callback's per-sample push_sample loop.  The streams of a handle share
+ * one capture rate and are pushed in lock step (the same n_in for all).  The crispy_rn_process* entry points never touch
+ * the adapter's state (carry, resampler, first-frame flag); both share the DenoiseState of the streams.
+ *
+ * The resampler's position arithmetic is the reference's own f64 recurrence, run once per push on the host for all
+ * streams (the positions do not depend on the samples) from the first sample of a stream on; the interpolation, with its
+ * separately rounded multiply and add, and everything else run in two streaming kernels around the frame kernels.  Device
+ * workspace: 2 x n_streams x frames x 480 floats for the largest push so far, 2 x (n_streams x 481) floats of state.
+ */
+/* RnnNoiseProcessor::new(input_rate, _, volume) on an existing handle: |input_rate - 48000| >= 1 inserts the
+ * LinearResampler(input_rate, 48000); volume is clamped to [0, 1].  Resets the adapter state (carry, resampler,
+ * first-frame flag) and the DenoiseState of every stream (what audio.rs:955-965 does by replacing the processor).
+ * A handle that was never configured behaves as 48 kHz with volume 1. */
+int crispy_rn_adapter_configure(crispy_rn *h, float input_rate, float volume);
+int crispy_rn_adapter_set_volume(crispy_rn *h, float volume);          /* NsState::set_volume; holds from the next push on */
+/* NsState::produced_rate_hz (audio.rs:352-357): 48000 with the resampler, else the configured rate.  (Through an
+ * out-pointer: every entry point returns a status.) */
+int crispy_rn_adapter_produced_rate_hz(const crispy_rn *h, float *rate_hz);
+/* samples the NEXT push of n_in samples will return per stream (a function of the adapter state), < 0 = error */
+long crispy_rn_push_out_len(const crispy_rn *h, long n_in);
+/* DEVICE pointers. d_in [n_streams][in_stride], n_in raw capture samples in +-1 per stream (at most 2^24 per push).
+ * d_out [n_streams][out_stride] receives *n_out = 480 x (completed frames, minus the dropped first one) samples per stream:
+ * clamp(y / 32768, -1, 1) x volume.  d_frames48 (nullable) [n_streams][frames_stride]: the frames exactly as they entered
+ * process_frame (48 kHz, x32768), all completed ones including the dropped first.  d_vad (nullable) [frames][n_streams].
+ * Enqueued on hip_stream (NULL = own stream); n_out is known on return.  n_in == 0 is a no-op.  CRISPY_ERR_INVALID_ARG:
+ * n_in < 0, a stride shorter than its data, NULL d_in / d_out / n_out, d_out overlapping d_in; CRISPY_ERR_OOM: the
+ * workspace could not grow -- in both cases the handle's state is as it was. */
+int crispy_rn_push_device(crispy_rn *h, const float *d_in, long in_stride, long n_in, float *d_out, long out_stride,
+                          float *d_frames48, long frames_stride, float *d_vad, long *n_out, void *hip_stream);
+/* the same with HOST pointers; returns when out is complete */
+int crispy_rn_push(crispy_rn *h, const float *in, long in_stride, long n_in, float *out, long out_stride,
+                   float *vad, long *n_out);
+/* With crispy_rn_set_timing: device time of rn_adapt_in_kernel and rn_adapt_out_kernel of the last push that returned
+ * samples, from hipEvents around each (tools/rn_push_timing.py). */
+int crispy_rn_last_push_ms(crispy_rn *h, float *adapt_in_ms, float *adapt_out_ms);
+/* Pure, no device: how many samples a fresh LinearResampler(input_rate, output_rate) emits for its inputs
+ * n_before ... n_before + n_in - 1 (audio.rs:108-133; n_in when the rates are within 1 Hz).  Runs the recurrence:
+ * time proportional to n_before + n_in.  < 0 = error (negative count, rate not a positive number). */
+long crispy_linear_resampler_count(float input_rate, float output_rate, long n_before, long n_in);
 
 /* Block until everything enqueued on the handle's own stream has finished. */
 int crispy_rn_synchronize(crispy_rn *h);
