@@ -1,6 +1,8 @@
-// api_util.h -- error plumbing shared by the extern "C" translation units.
+// api_util.h -- error plumbing and the owner of a device allocation (DevBuf) shared by the extern "C" translation units.
 #pragma once
+#include <cstddef>
 #include <cstdlib>
+#include <utility>
 
 #include <hip/hip_runtime.h>
 
@@ -31,6 +33,30 @@ inline const char* dev_env(const char* name) { return std::getenv(name); }
 #else
 inline const char* dev_env(const char*) { return nullptr; }
 #endif
+
+// A device allocation that belongs to its holder: freed with it (or when a fresh one is assigned over it), moved, never
+// copied.  alloc replaces what it holds, grow only when that is too small -- neither carries the contents over.  After a
+// failed alloc it holds nothing (bytes 0): the next call allocates again.  The holder's device must be current when one
+// is let go.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t n) {
+    if (p) (void)hipFree(p);
+    p = nullptr; bytes = 0;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n);
+    if (e == hipSuccess) bytes = n; else p = nullptr;
+    return e;
+  }
+  hipError_t grow(size_t n) { return n <= bytes ? hipSuccess : alloc(n); }
+  operator T*() const { return p; }
+  template <class U> U* as() const { return reinterpret_cast<U*>(p); }      // the same bytes as another element type (the f16 caches)
+};
 
 }  // namespace crispy
 

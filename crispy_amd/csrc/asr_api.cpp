@@ -14,16 +14,16 @@ struct crispy_mel {
   int device = 0;
   int n_mel = 0;
   hipStream_t stream = nullptr;
-  MelTables* d_tab = nullptr;
+  DevBuf<MelTables> d_tab;
   // workspace, grown on demand
   int cap_batch = 0;
   long cap_stride = 0;
-  float* d_pcm = nullptr;
-  int* d_n = nullptr;
-  float* d_raw = nullptr;
-  int* d_max = nullptr;
-  float* d_out = nullptr;
-  int* d_idx = nullptr;     // [2][cap_batch]: clip index | seek of a window call
+  DevBuf<float> d_pcm;
+  DevBuf<int> d_n;
+  DevBuf<float> d_raw;
+  DevBuf<int> d_max;
+  DevBuf<float> d_out;
+  DevBuf<int> d_idx;        // [2][cap_batch]: clip index | seek of a window call
   int last_batch = 0;       // clips whose raw frames d_raw / d_max currently hold
 };
 
@@ -31,25 +31,21 @@ namespace {
 
 int mel_reserve(crispy_mel* h, int batch, long stride, bool need_pcm, bool need_out) {
   if (batch > h->cap_batch) {
-    for (void* p : {(void*)h->d_n, (void*)h->d_raw, (void*)h->d_max, (void*)h->d_out, (void*)h->d_idx})
-      if (p) (void)hipFree(p);
-    h->d_n = nullptr; h->d_raw = nullptr; h->d_max = nullptr; h->d_out = nullptr; h->d_idx = nullptr;
+    h->d_n = {}; h->d_raw = {}; h->d_max = {}; h->d_out = {}; h->d_idx = {}; h->d_pcm = {};
     h->last_batch = 0;
-    if (h->d_pcm) { (void)hipFree(h->d_pcm); h->d_pcm = nullptr; h->cap_stride = 0; }
+    h->cap_stride = 0;
     h->cap_batch = 0;
     const size_t elems = (size_t)batch * h->n_mel * MEL_RAW_FRAMES;
-    HIP_TRY(hipMalloc(&h->d_n, sizeof(int) * batch));
-    HIP_TRY(hipMalloc(&h->d_idx, sizeof(int) * 2 * batch));
-    HIP_TRY(hipMalloc(&h->d_max, sizeof(int) * batch));
-    HIP_TRY(hipMalloc(&h->d_raw, sizeof(float) * elems));
+    HIP_TRY(h->d_n.alloc(sizeof(int) * batch));
+    HIP_TRY(h->d_idx.alloc(sizeof(int) * 2 * batch));
+    HIP_TRY(h->d_max.alloc(sizeof(int) * batch));
+    HIP_TRY(h->d_raw.alloc(sizeof(float) * elems));
     h->cap_batch = batch;
   }
   if (need_out && !h->d_out)
-    HIP_TRY(hipMalloc(&h->d_out, sizeof(float) * (size_t)h->cap_batch * h->n_mel * MEL_FRAMES));
+    HIP_TRY(h->d_out.alloc(sizeof(float) * (size_t)h->cap_batch * h->n_mel * MEL_FRAMES));
   if (need_pcm && (!h->d_pcm || stride > h->cap_stride)) {
-    if (h->d_pcm) (void)hipFree(h->d_pcm);
-    h->d_pcm = nullptr;
-    HIP_TRY(hipMalloc(&h->d_pcm, sizeof(float) * (size_t)h->cap_batch * stride));
+    HIP_TRY(h->d_pcm.alloc(sizeof(float) * (size_t)h->cap_batch * stride));
     h->cap_stride = stride;
   }
   return CRISPY_OK;
@@ -106,7 +102,7 @@ int crispy_mel_create(const float* filters, int n_mel, int device, crispy_mel** 
   auto body = [&]() -> int {
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc(&h->d_tab, sizeof(MelTables)));
+    HIP_TRY(h->d_tab.alloc(sizeof(MelTables)));
     HIP_TRY(hipMemcpy(h->d_tab, tab, sizeof(MelTables), hipMemcpyHostToDevice));
     return CRISPY_OK;
   };
@@ -121,10 +117,9 @@ void crispy_mel_destroy(crispy_mel* h) try {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->d_tab, (void*)h->d_pcm, (void*)h->d_n, (void*)h->d_raw, (void*)h->d_max, (void*)h->d_out, (void*)h->d_idx})
-    if (p) (void)hipFree(p);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  const hipStream_t stream = h->stream;
+  delete h;                                // the buffers are members: let go on the handle's device, after the sync
+  if (stream) (void)hipStreamDestroy(stream);
 } CRISPY_CATCH_VOID("crispy_mel_destroy")
 
 int crispy_mel_compute_device(crispy_mel* h, const float* d_pcm, long pcm_stride, const int* n_samples,
@@ -220,14 +215,14 @@ int crispy_mel_synchronize(crispy_mel* h) try {
 struct crispy_resampler {
   int device = 0;
   hipStream_t stream = nullptr;
-  float* d_w = nullptr;     // [684][1040] circulant operator
-  float* d_a = nullptr;     // [rows][1040]
-  float* d_y = nullptr;     // [rows][684]
+  DevBuf<float> d_w;        // [684][1040] circulant operator
+  DevBuf<float> d_a;        // [rows][1040]
+  DevBuf<float> d_y;        // [rows][684]
   long cap_rows = 0;
   // the f16-pair form (asr_common.h: rs_prep_split): W' [342][3 x 2 x RS_PITCH] f16 = W_hi | W_hi | W_lo over the window
   // [previous block | block]; planes [2][streams][(n_blk + 1) x RS_PITCH] f16
-  void* d_w16 = nullptr;
-  void* d_planes = nullptr;
+  DevBuf<void> d_w16;
+  DevBuf<void> d_planes;
   long cap_plane_blocks = 0;
 };
 
@@ -328,9 +323,9 @@ int crispy_resampler_create(int device, crispy_resampler** out) try {
   auto body = [&]() -> int {
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc(&h->d_w, W.size() * sizeof(float)));
+    HIP_TRY(h->d_w.alloc(W.size() * sizeof(float)));
     HIP_TRY(hipMemcpy(h->d_w, W.data(), W.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&h->d_w16, W16.size() * sizeof(uint16_t)));
+    HIP_TRY(h->d_w16.alloc(W16.size() * sizeof(uint16_t)));
     HIP_TRY(hipMemcpy(h->d_w16, W16.data(), W16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     return CRISPY_OK;
   };
@@ -344,10 +339,9 @@ void crispy_resampler_destroy(crispy_resampler* h) try {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->d_w, (void*)h->d_a, (void*)h->d_y, h->d_w16, h->d_planes})
-    if (p) (void)hipFree(p);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  const hipStream_t stream = h->stream;
+  delete h;                                // the buffers are members: let go on the handle's device, after the sync
+  if (stream) (void)hipStreamDestroy(stream);
 } CRISPY_CATCH_VOID("crispy_resampler_destroy")
 
 int crispy_resampler_process_device(crispy_resampler* h, const float* d_in, long in_stride, long n_in, int batch,
@@ -371,10 +365,8 @@ int crispy_resampler_process_device(crispy_resampler* h, const float* d_in, long
     if (group > batch) group = batch;
     const long need = (long)group * (n_blk + 1);
     if (need > h->cap_plane_blocks) {
-      if (h->d_planes) (void)hipFree(h->d_planes);
-      h->d_planes = nullptr;
       h->cap_plane_blocks = 0;
-      HIP_TRY(hipMalloc(&h->d_planes, (size_t)need * RS_PITCH * 2 * sizeof(uint16_t)));
+      HIP_TRY(h->d_planes.alloc((size_t)need * RS_PITCH * 2 * sizeof(uint16_t)));
       h->cap_plane_blocks = need;
     }
     for (int b0 = 0; b0 < batch; b0 += group) {
@@ -384,8 +376,8 @@ int crispy_resampler_process_device(crispy_resampler* h, const float* d_in, long
       // m % (n_blk + 1) of stream m / (n_blk + 1); the last window of a stream [last block | the next stream's zero slot] is
       // not an output block and is dropped by the epilogue (as separate matrices of 1404 rows a tenth of the tiles was padding)
       HGemmArgs g{};
-      g.A = reinterpret_cast<const _Float16*>(h->d_planes); g.lda = RS_PITCH;
-      g.W = reinterpret_cast<const _Float16*>(h->d_w16); g.ldw = 3L * 2 * RS_PITCH;
+      g.A = h->d_planes.as<const _Float16>(); g.lda = RS_PITCH;
+      g.W = h->d_w16.as<const _Float16>(); g.ldw = 3L * 2 * RS_PITCH;
       g.C = d_out + (long)b0 * out_stride; g.ldc = RS_FFT_OUT;
       g.M = nb * (n_blk + 1) - 1; g.N = RS_FFT_OUT; g.K = 3 * 2 * RS_PITCH;      // (- 1: the very last window would read past the planes)
       g.c_group_rows = n_blk + 1; g.c_group_valid = n_blk; g.c_group_stride = out_stride;
@@ -403,12 +395,10 @@ int crispy_resampler_process_device(crispy_resampler* h, const float* d_in, long
   if (group > batch) group = batch;
   const long rows_cap = (long)group * n_blk;
   if (rows_cap > h->cap_rows) {
-    if (h->d_a) (void)hipFree(h->d_a);
-    if (h->d_y) (void)hipFree(h->d_y);
-    h->d_a = h->d_y = nullptr;
+    h->d_a = {}; h->d_y = {};
     h->cap_rows = 0;
-    HIP_TRY(hipMalloc(&h->d_a, (size_t)rows_cap * RS_K * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_y, (size_t)rows_cap * RS_N * sizeof(float)));
+    HIP_TRY(h->d_a.alloc((size_t)rows_cap * RS_K * sizeof(float)));
+    HIP_TRY(h->d_y.alloc((size_t)rows_cap * RS_N * sizeof(float)));
     h->cap_rows = rows_cap;
   }
   for (int b0 = 0; b0 < batch; b0 += group) {

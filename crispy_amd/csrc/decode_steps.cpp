@@ -1045,9 +1045,8 @@ int crispy_asr_set_suppress(crispy_asr* h, const int* ids, int n, int first_only
   std::vector<unsigned char> first(h->hp.n_vocab);
   for (int v = 0; v < h->hp.n_vocab; ++v) first[v] = h->sup_all[v] | h->sup_first[v];   // first position: both lists
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipMemcpy(h->d_suppress, h->sup_all.data(), h->sup_all.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->d_suppress_first, first.data(), first.size(), hipMemcpyHostToDevice));
-  return CRISPY_OK;
+  const int rc = upload_mask(h->d_suppress, h->sup_all);
+  return rc != CRISPY_OK ? rc : upload_mask(h->d_suppress_first, first);
 } CRISPY_CATCH_RET("crispy_asr_set_suppress")
 
 int crispy_asr_stage_logits_device(crispy_asr* h, const float* d_x, int batch, float* d_logits) try {
@@ -1217,8 +1216,8 @@ int crispy_asr_detect_language_device(crispy_asr* h, const float* d_enc, int bat
   if (!h->d_lang_mask) {
     std::vector<unsigned char> m(V, 1);
     for (int t = sot + 1; t < sot + 1 + n_lang && t < V; ++t) m[t] = 0;
-    HIP_TRY(hipMalloc(&h->d_lang_mask, V));
-    HIP_TRY(hipMemcpy(h->d_lang_mask, m.data(), V, hipMemcpyHostToDevice));
+    rc = upload_mask(h->d_lang_mask, m);
+    if (rc != CRISPY_OK) return rc;
   }
   HIP_TRY(argmax_f32(h->dw.logits, h->d_lang_mask, nullptr, nullptr, V, logits_ld(h), h->dw.tok, nullptr, nullptr, batch, s));
   HIP_TRY(hipMemcpyAsync(lang_tokens_out, h->dw.tok, sizeof(int) * batch, hipMemcpyDeviceToHost, s));
@@ -1238,12 +1237,12 @@ int crispy_asr_transcribe_tokens(crispy_asr* h, const float* pcm, long pcm_strid
   if (rc != CRISPY_OK) return rc;
   rc = reserve_pcm(h, pcm_stride);
   if (rc != CRISPY_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(h->w_pcm, pcm, (size_t)batch * pcm_stride * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  rc = crispy_mel_compute_device(h->mel, h->w_pcm, pcm_stride, n_samples, batch, nullptr, h->w_melt, h->stream);
+  HIP_TRY(hipMemcpyAsync(h->ew.pcm, pcm, (size_t)batch * pcm_stride * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  rc = crispy_mel_compute_device(h->mel, h->ew.pcm, pcm_stride, n_samples, batch, nullptr, h->ew.melt, h->stream);
   if (rc != CRISPY_OK) return rc;
-  rc = crispy_asr_encode_device(h, h->w_melt, batch, h->w_enc, h->stream);
+  rc = crispy_asr_encode_device(h, h->ew.melt, batch, h->ew.enc, h->stream);
   if (rc != CRISPY_OK) return rc;
-  return crispy_asr_decode_greedy_device(h, h->w_enc, batch, prompt, n_prompt, max_new, tokens_out, n_out, nullptr);
+  return crispy_asr_decode_greedy_device(h, h->ew.enc, batch, prompt, n_prompt, max_new, tokens_out, n_out, nullptr);
 } CRISPY_CATCH_RET("crispy_asr_transcribe_tokens")
 
 

@@ -101,14 +101,14 @@ int crispy_asr_load_resident(const char* model_path, int device, crispy_asr** ou
 
 int crispy_asr_memory_info(const crispy_asr* h, size_t* weight_bytes, size_t* quantised_bytes, size_t* scratch_bytes) try {
   if (!h) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_memory_info: NULL handle");
-  size_t dense = h->derived_bytes, q = 0;
-  for (const auto& kv : h->tensors)
-    if (kv.second.d) dense += kv.second.n * sizeof(float);
+  size_t dense = 0, q = 0;
+  for (const auto& b : h->derived) dense += b.bytes;
+  for (const auto& kv : h->tensors) dense += kv.second.d.bytes;
   for (const auto& kv : h->qtensors)
-    if (kv.second.owned) q += kv.second.nbytes;
+    if (kv.second.own) q += kv.second.nbytes;      // (without the 16 bytes of slack behind the blocks)
   if (weight_bytes) *weight_bytes = dense + q;
   if (quantised_bytes) *quantised_bytes = q;
-  if (scratch_bytes) *scratch_bytes = h->q_scratch_bytes;
+  if (scratch_bytes) *scratch_bytes = h->q_scratch.bytes;
   return CRISPY_OK;
 } CRISPY_CATCH_RET("crispy_asr_memory_info")
 
@@ -228,13 +228,13 @@ int load_impl(const char* model_path, int device, bool resident, crispy_asr** ou
         // the blocks stay as they are (managers/model.rs:99,137: the catalog's q4_1 / q5_0 files): no f32 tensor is made
         QTensor q;
         q.ttype = ttype; q.n = n; q.cols = ne[0]; q.nbytes = qbuf.size();
-        if (hipSetDevice(device) != hipSuccess || hipMalloc(&q.d, q.nbytes + 16) != hipSuccess ||      // (+16: the in-register block fetch reads whole dwords)
-            hipMemcpy(q.d, qbuf.data(), q.nbytes, hipMemcpyHostToDevice) != hipSuccess) {
-          if (q.d) (void)hipFree(q.d);
+        if (hipSetDevice(device) != hipSuccess || q.own.alloc(q.nbytes + 16) != hipSuccess ||      // (+16: the in-register block fetch reads whole dwords)
+            hipMemcpy(q.own, qbuf.data(), q.nbytes, hipMemcpyHostToDevice) != hipSuccess) {
           fail(CRISPY_ERR_OOM, "crispy_asr_load_resident: no device memory for '%s' (%zu bytes)", name.c_str(), q.nbytes);
           return bail(CRISPY_ERR_OOM);
         }
-        h->qtensors[name] = q;
+        q.d = q.own;
+        h->qtensors[name] = std::move(q);
         h->tensors[name].set = true;
         continue;
       }

@@ -14,28 +14,75 @@ namespace {
 
 void add_spec(std::map<std::string, size_t>& spec, const std::string& name, size_t n) { spec[name] = n; }
 
+// Every copy the handle derives from its tensors is made here: n bytes of device memory that the handle owns until it is freed
+int derived_copy(crispy_asr* h, size_t n, void** out) {
+  DevBuf<void> b;
+  HIP_TRY(b.alloc(n));
+  *out = b.p;
+  h->derived.push_back(std::move(b));
+  return CRISPY_OK;
+}
+
 int upload(crispy_asr* h, const std::vector<float>& host, const float** out) {
-  float* d = nullptr;
-  HIP_TRY(hipMalloc(&d, host.size() * sizeof(float)));
-  h->derived.push_back(d);
-  h->derived_bytes += host.size() * sizeof(float);
+  void* d = nullptr;
+  const int rc = derived_copy(h, host.size() * sizeof(float), &d);
+  if (rc != CRISPY_OK) return rc;
   HIP_TRY(hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-  *out = d;
+  *out = static_cast<const float*>(d);
   return CRISPY_OK;
 }
 
-int download(const Tensor& t, std::vector<float>& host) {
-  host.resize(t.n);
-  HIP_TRY(hipMemcpy(host.data(), t.d, t.n * sizeof(float), hipMemcpyDeviceToHost));
+// f16 copy of n floats, converted on the handle's stream
+int half_copy(crispy_asr* h, const float* w, size_t n, const void** out) {
+  void* p = nullptr;
+  const int rc = derived_copy(h, n * 2, &p);
+  if (rc != CRISPY_OK) return rc;
+  HIP_TRY(convert_f32_to_f16(w, p, (long)n, h->stream));
+  *out = p;
   return CRISPY_OK;
 }
 
-const float* T(crispy_asr* h, const std::string& name) { return h->tensors[name].d; }
+// n halves once more in the fused step kernels' operand order
+int packed_copy(crispy_asr* h, const void* src, size_t n, int kind, const void** out) {
+  void* p = nullptr;
+  const int rc = derived_copy(h, n * 2, &p);
+  if (rc != CRISPY_OK) return rc;
+  HIP_TRY(fused_pack_weights(src, p, h->hp.n_text_state, kind, h->stream));
+  *out = p;
+  return CRISPY_OK;
+}
+
+// a tensor by its model-file name; an unknown name is reported, never inserted
+Tensor* find_tensor(crispy_asr* h, const std::string& name) {
+  const auto it = h->tensors.find(name);
+  if (it != h->tensors.end()) return &it->second;
+  fail(CRISPY_ERR_BAD_MODEL, "crispy_asr_finalize: unknown tensor '%s'", name.c_str());
+  return nullptr;
+}
+
+// T(name): the tensor's device pointer; the first unknown name stays in rc, which the caller returns after its look-ups
+struct Resolver {
+  crispy_asr* h;
+  int rc = CRISPY_OK;
+  const float* operator()(const std::string& name) {
+    const Tensor* t = rc == CRISPY_OK ? find_tensor(h, name) : nullptr;
+    if (!t) { if (rc == CRISPY_OK) rc = CRISPY_ERR_BAD_MODEL; return nullptr; }
+    return t->d;
+  }
+};
+
+int download(crispy_asr* h, const std::string& name, std::vector<float>& host) {
+  const Tensor* t = find_tensor(h, name);
+  if (!t) return CRISPY_ERR_BAD_MODEL;
+  host.resize(t->n);
+  HIP_TRY(hipMemcpy(host.data(), t->d, t->n * sizeof(float), hipMemcpyDeviceToHost));
+  return CRISPY_OK;
+}
 
 // [co][ci][3] -> [co][kk*ci_n + ci]: K order (tap, channel) matches three consecutive frame-major rows
 int reorder_conv(crispy_asr* h, const std::string& name, int co_n, int ci_n, const float** out) {
   std::vector<float> src, dst((size_t)co_n * ci_n * 3);
-  int rc = download(h->tensors[name], src);
+  int rc = download(h, name, src);
   if (rc != CRISPY_OK) return rc;
   for (int co = 0; co < co_n; ++co)
     for (int ci = 0; ci < ci_n; ++ci)
@@ -43,26 +90,41 @@ int reorder_conv(crispy_asr* h, const std::string& name, int co_n, int ci_n, con
   return upload(h, dst, out);
 }
 
-// concatenate row blocks of [d][d] weights (and biases; a missing bias is zeros)
-int fuse_rows(crispy_asr* h, const std::vector<std::string>& wnames, const std::vector<std::string>& bnames, int d,
-              const float** w_out, const float** b_out) {
-  std::vector<float> W, Bv;
-  for (size_t i = 0; i < wnames.size(); ++i) {
-    std::vector<float> t;
-    int rc = download(h->tensors[wnames[i]], t);
-    if (rc != CRISPY_OK) return rc;
-    W.insert(W.end(), t.begin(), t.end());
-    if (!bnames[i].empty()) {
-      rc = download(h->tensors[bnames[i]], t);
+QRef qref(crispy_asr* h, std::initializer_list<std::string> names) {
+  QRef r;
+  for (const std::string& n : names) r.t[r.n++] = &h->qtensors[n];
+  return r;
+}
+
+// concatenated biases of row-fused weights (a missing bias is zeros)
+int fuse_bias(crispy_asr* h, const std::vector<std::string>& bnames, int d, const float** b_out) {
+  std::vector<float> Bv;
+  for (const std::string& b : bnames) {
+    if (!b.empty()) {
+      std::vector<float> t;
+      const int rc = download(h, b, t);
       if (rc != CRISPY_OK) return rc;
       Bv.insert(Bv.end(), t.begin(), t.end());
     } else {
       Bv.insert(Bv.end(), (size_t)d, 0.f);
     }
   }
-  int rc = upload(h, W, w_out);
-  if (rc != CRISPY_OK) return rc;
   return upload(h, Bv, b_out);
+}
+
+// concatenate row blocks of [d][d] weights (and biases: fuse_bias)
+int fuse_rows(crispy_asr* h, const std::vector<std::string>& wnames, const std::vector<std::string>& bnames, int d,
+              const float** w_out, const float** b_out) {
+  std::vector<float> W;
+  for (const std::string& w : wnames) {
+    std::vector<float> t;
+    const int rc = download(h, w, t);
+    if (rc != CRISPY_OK) return rc;
+    W.insert(W.end(), t.begin(), t.end());
+  }
+  const int rc = upload(h, W, w_out);
+  if (rc != CRISPY_OK) return rc;
+  return fuse_bias(h, bnames, d, b_out);
 }
 
 // LayerNorm (gamma, beta over K) folded into W [N][K] (+ bias [N], may be null): see GemmArgs::ln_s
@@ -89,28 +151,6 @@ int fold_ln(crispy_asr* h, const float* d_w, const float* d_bias, const float* d
   if (rc == CRISPY_OK) rc = upload(h, s, ls);
   if (rc == CRISPY_OK) rc = upload(h, c, lc);
   return rc;
-}
-
-QRef qref(crispy_asr* h, std::initializer_list<std::string> names) {
-  QRef r;
-  for (const std::string& n : names) r.t[r.n++] = &h->qtensors[n];
-  return r;
-}
-
-// concatenated biases of row-fused weights (a missing bias is zeros)
-int fuse_bias(crispy_asr* h, const std::vector<std::string>& bnames, int d, const float** b_out) {
-  std::vector<float> Bv;
-  for (const std::string& b : bnames) {
-    if (!b.empty()) {
-      std::vector<float> t;
-      const int rc = download(h->tensors[b], t);
-      if (rc != CRISPY_OK) return rc;
-      Bv.insert(Bv.end(), t.begin(), t.end());
-    } else {
-      Bv.insert(Bv.end(), (size_t)d, 0.f);
-    }
-  }
-  return upload(h, Bv, b_out);
 }
 }  // namespace
 
@@ -159,61 +199,61 @@ std::map<std::string, size_t> expected_tensors(const crispy_asr_hparams& hp) {
 // its consumer: f16 (the operands of precision mode 1), f32, or f32 x gamma[k] (the LayerNorm-folded decode projections).
 int dq(crispy_asr* h, const QRef& r, bool f16, const float* gamma, hipStream_t s, const void** out) {
   const size_t esz = f16 ? 2 : 4;
-  if (r.n <= 0 || r.elems() * esz > h->q_scratch_bytes)
+  if (r.n <= 0 || r.elems() * esz > h->q_scratch.bytes)
     return fail(CRISPY_ERR_INVALID_ARG, "resident model: tensor of %zu elements does not fit the de-quantisation slot", r.elems());
-  char* dst = reinterpret_cast<char*>(h->q_scratch);
+  char* dst = h->q_scratch.as<char>();
   for (int i = 0; i < r.n; ++i) {
     const QTensor& t = *r.t[i];
     HIP_TRY(dequant_blocks(t.d, t.ttype, (long)(t.n / 32), t.cols, dst, f16 ? 1 : 0, gamma, s));
     dst += t.n * esz;
   }
-  *out = h->q_scratch;
+  *out = h->q_scratch.p;
   return CRISPY_OK;
 }
 
-void free_ws(crispy_asr* h) {
-  for (float** p : {&h->w_melt, &h->w_pcm, &h->w_h1, &h->w_x, &h->w_xn, &h->w_qkv, &h->w_att, &h->w_h, &h->w_enc})
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-  h->cap_batch = 0;
-  h->cap_pcm_stride = 0;
-}
 // the captured steps hold the workspace's addresses: they go first
 void free_dec_ws(crispy_asr* h) {
   h->drop_graphs();
   h->dw = DecWs{};
 }
 
+int upload_mask(DevBuf<unsigned char>& mask, const std::vector<unsigned char>& host) {
+  HIP_TRY(mask.grow(host.size()));
+  HIP_TRY(hipMemcpy(mask, host.data(), host.size(), hipMemcpyHostToDevice));
+  return CRISPY_OK;
+}
+
 int reserve_enc(crispy_asr* h, int batch) {
-  if (batch <= h->cap_batch) return CRISPY_OK;
-  free_ws(h);
+  EncWs& w = h->ew;
+  if (batch <= w.cap_batch) return CRISPY_OK;
+  w = EncWs{};
   const size_t B = batch, d = h->hp.n_audio_state, Tn = h->hp.n_audio_ctx;
-  HIP_TRY(hipMalloc(&h->w_melt, B * (MEL_FRAMES + 2) * h->hp.n_mels * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->w_h1, B * (MEL_FRAMES + 1) * d * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->w_x, B * Tn * d * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->w_xn, B * Tn * d * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->w_qkv, B * Tn * 3 * d * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->w_att, B * Tn * d * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->w_h, B * Tn * 4 * d * sizeof(float)));
-  HIP_TRY(hipMalloc(&h->w_enc, B * Tn * d * sizeof(float)));
+  HIP_TRY(w.melt.alloc(B * (MEL_FRAMES + 2) * h->hp.n_mels * sizeof(float)));
+  HIP_TRY(w.h1.alloc(B * (MEL_FRAMES + 1) * d * sizeof(float)));
+  HIP_TRY(w.x.alloc(B * Tn * d * sizeof(float)));
+  HIP_TRY(w.xn.alloc(B * Tn * d * sizeof(float)));
+  HIP_TRY(w.qkv.alloc(B * Tn * 3 * d * sizeof(float)));
+  HIP_TRY(w.att.alloc(B * Tn * d * sizeof(float)));
+  HIP_TRY(w.h.alloc(B * Tn * 4 * d * sizeof(float)));
+  HIP_TRY(w.enc.alloc(B * Tn * d * sizeof(float)));
   // zero padding rows of the frame-major buffers are written once
-  HIP_TRY(hipMemset(h->w_melt, 0, B * (MEL_FRAMES + 2) * h->hp.n_mels * sizeof(float)));
-  HIP_TRY(hipMemset(h->w_h1, 0, B * (MEL_FRAMES + 1) * d * sizeof(float)));
+  HIP_TRY(hipMemset(w.melt, 0, w.melt.bytes));
+  HIP_TRY(hipMemset(w.h1, 0, w.h1.bytes));
   // hipMemset on device memory does not wait on the host, and it runs on the NULL stream, which the handle's
   // non-blocking stream is not ordered against: without this the 1.5 GB memset of a 256-clip workspace was still
   // clearing h1 while the first call's conv1 had already written the first clips (wrong encoder output for clips
   // 0..7 of the first 256-clip call, intermittently: tests/test_gpu_pipeline.py cfg5)
   HIP_TRY(hipDeviceSynchronize());
-  h->cap_batch = batch;
+  w.cap_batch = batch;
   return CRISPY_OK;
 }
 
 // the PCM rows of the encoder workspace [cap_batch][stride] (after reserve_enc), regrown when a call's rows are longer
 int reserve_pcm(crispy_asr* h, long stride) {
-  if (h->w_pcm && stride <= h->cap_pcm_stride) return CRISPY_OK;
-  if (h->w_pcm) (void)hipFree(h->w_pcm);
-  h->w_pcm = nullptr;
-  HIP_TRY(hipMalloc(&h->w_pcm, (size_t)h->cap_batch * stride * sizeof(float)));
-  h->cap_pcm_stride = stride;
+  EncWs& w = h->ew;
+  if (w.pcm && stride <= w.cap_pcm_stride) return CRISPY_OK;
+  HIP_TRY(w.pcm.alloc((size_t)w.cap_batch * stride * sizeof(float)));
+  w.cap_pcm_stride = stride;
   return CRISPY_OK;
 }
 
@@ -234,8 +274,7 @@ int crispy_asr_create(const crispy_asr_hparams* hp, const float* mel_filters, in
   if (!out) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_create: out is NULL");
   *out = nullptr;
   if (!hp || !mel_filters) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_create: NULL argument");
-  auto width_ok = [](int d) { return d == 384 || d == 512 || d == 768 || d == 1024 || d == 1280; };   // tiny ... large
-  if (hp->n_audio_ctx != 1500 || !width_ok(hp->n_audio_state) || !width_ok(hp->n_text_state) ||
+  if (hp->n_audio_ctx != 1500 || !whisper_width_ok(hp->n_audio_state) || !whisper_width_ok(hp->n_text_state) ||
       // (divisions, not products: a hostile head count from a model file must not overflow -- found by the sanitizer
       // harness, tests/test_host_sanitizers.py)
       hp->n_audio_state % 64 != 0 || hp->n_audio_head != hp->n_audio_state / 64 || hp->n_text_head != hp->n_text_state / 64 ||
@@ -257,9 +296,7 @@ int crispy_asr_create(const crispy_asr_hparams* hp, const float* mel_filters, in
     int r = crispy_mel_create(mel_filters, hp->n_mels, device, &h->mel);
     if (r != CRISPY_OK) return r;
     for (const auto& kv : expected_tensors(*hp)) {     // device memory is taken when a tensor is set: a resident
-      Tensor t;                                         // quantised model never holds its matrices as f32
-      t.n = kv.second;
-      h->tensors[kv.first] = t;
+      h->tensors[kv.first].n = kv.second;               // quantised model never holds its matrices as f32
     }
     return CRISPY_OK;
   };
@@ -277,25 +314,14 @@ void crispy_asr_free(crispy_asr* h) try {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (auto& kv : h->tensors)
-    if (kv.second.d) (void)hipFree(kv.second.d);
-  for (float* p : h->derived) (void)hipFree(p);
-  for (auto& kv : h->qtensors)
-    if (kv.second.d && kv.second.owned) (void)hipFree(kv.second.d);
-  if (h->q_scratch) (void)hipFree(h->q_scratch);
-  if (h->ev_scratch) (void)hipEventDestroy(h->ev_scratch);
-  if (h->d_suppress) (void)hipFree(h->d_suppress);
-  if (h->d_suppress_first) (void)hipFree(h->d_suppress_first);
-  if (h->d_ts_mask) (void)hipFree(h->d_ts_mask);
-  if (h->d_ts_mask_first) (void)hipFree(h->d_ts_mask_first);
-  if (h->d_ts_mask_nst) (void)hipFree(h->d_ts_mask_nst);
-  if (h->d_ts_mask_first_nst) (void)hipFree(h->d_ts_mask_first_nst);
-  if (h->d_lang_mask) (void)hipFree(h->d_lang_mask);
-  free_ws(h);
-  free_dec_ws(h);
-  if (h->mel) crispy_mel_destroy(h->mel);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  h->drop_graphs();                        // the captured steps hold the workspaces' addresses: they go first
+  crispy_mel* const mel = h->mel;
+  const hipEvent_t ev_scratch = h->ev_scratch;
+  const hipStream_t stream = h->stream;
+  delete h;                                // every device buffer is a member: let go here, on the handle's device, after the sync
+  if (mel) crispy_mel_destroy(mel);
+  if (ev_scratch) (void)hipEventDestroy(ev_scratch);
+  if (stream) (void)hipStreamDestroy(stream);
 } CRISPY_CATCH_VOID("crispy_asr_free")
 
 int crispy_asr_set_tensor(crispy_asr* h, const char* name, const float* data, size_t n_elems) try {
@@ -307,7 +333,7 @@ int crispy_asr_set_tensor(crispy_asr* h, const char* name, const float* data, si
     return fail(CRISPY_ERR_BAD_MODEL, "crispy_asr_set_tensor: '%s' has %zu elements, expected %zu", name, n_elems,
                 it->second.n);
   HIP_TRY(hipSetDevice(h->device));
-  if (!it->second.d) HIP_TRY(hipMalloc(&it->second.d, n_elems * sizeof(float)));
+  if (!it->second.d) HIP_TRY(it->second.d.alloc(n_elems * sizeof(float)));
   HIP_TRY(hipMemcpy(it->second.d, data, n_elems * sizeof(float), hipMemcpyHostToDevice));
   it->second.set = true;
   return CRISPY_OK;
@@ -320,37 +346,124 @@ namespace asr {
 namespace {
 
 int finalize_tail(crispy_asr* h) {
-  HIP_TRY(hipMalloc(&h->d_suppress, h->hp.n_vocab));
-  HIP_TRY(hipMalloc(&h->d_suppress_first, h->hp.n_vocab));
-  HIP_TRY(hipMemset(h->d_suppress, 0, h->hp.n_vocab));
-  HIP_TRY(hipMemset(h->d_suppress_first, 0, h->hp.n_vocab));
-  HIP_TRY(hipDeviceSynchronize());          // NULL-stream memsets vs the handle's non-blocking stream (see reserve_enc)
-  { const int mrc = build_ts_masks(h); if (mrc != CRISPY_OK) return mrc; }
+  const std::vector<unsigned char> none(h->hp.n_vocab, 0);
+  int rc = upload_mask(h->d_suppress, none);
+  if (rc == CRISPY_OK) rc = upload_mask(h->d_suppress_first, none);
+  if (rc == CRISPY_OK) rc = build_ts_masks(h);
+  if (rc != CRISPY_OK) return rc;
   h->finalized = true;
   return CRISPY_OK;
 }
 
-// f16 copies of the two convolution kernels (precision mode 1; conv1's rows zero-padded to a multiple of 32 columns: the
-// padded operand columns of A read on into the next frames -- finite values -- and meet zeros here)
+// f16 copies of the two convolution kernels (precision mode 1; conv1's rows [3 n_mels] zero-padded to a multiple of 32
+// columns, 3 * 80 = 240 -> 256: the padded operand columns of A read on into the next frames -- finite values -- and meet
+// zeros here)
 int make_conv_halves(crispy_asr* h) {
   const size_t d = h->hp.n_audio_state;
-  {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, d * 3 * d * 2));
-    h->derived.push_back(reinterpret_cast<float*>(p));
-    h->derived_bytes += d * 3 * d * 2;
-    HIP_TRY(convert_f32_to_f16(h->conv2_w, p, (long)(d * 3 * d), h->stream));
-    h->conv2_wh = p;
-  }
+  int rc = half_copy(h, h->conv2_w, d * 3 * d, &h->conv2_wh);
+  if (rc != CRISPY_OK) return rc;
   const int k1 = 3 * h->hp.n_mels, k1p = (k1 + 31) / 32 * 32;
   void* p = nullptr;
-  HIP_TRY(hipMalloc(&p, d * k1p * 2));
-  h->derived.push_back(reinterpret_cast<float*>(p));
-  h->derived_bytes += d * k1p * 2;
+  if ((rc = derived_copy(h, d * k1p * 2, &p)) != CRISPY_OK) return rc;
   HIP_TRY(hipMemsetAsync(p, 0, d * k1p * 2, h->stream));
   HIP_TRY(convert_rows_f32_to_f16(h->conv1_w, k1, p, k1p, k1, (long)d, h->stream));
   h->conv1_wh = p;
   h->conv1_kp = k1p;
+  return CRISPY_OK;
+}
+
+// What both finalize paths resolve alike: the reordered convolution kernels and every vector the kernels read as the model
+// file holds it -- conv biases, positional embeddings, every LayerNorm, the biases that are not row-fused.  The dense path
+// adds the matrices (fuse_rows / fold_ln), the resident path the block references (QRef) and fuse_bias.
+int resolve_shared(crispy_asr* h) {
+  const int d = h->hp.n_audio_state;
+  int rc;
+  if ((rc = reorder_conv(h, "encoder.conv1.weight", d, h->hp.n_mels, &h->conv1_w)) != CRISPY_OK) return rc;
+  if ((rc = reorder_conv(h, "encoder.conv2.weight", d, d, &h->conv2_w)) != CRISPY_OK) return rc;
+  Resolver T{h};
+  h->conv1_b = T("encoder.conv1.bias");
+  h->conv2_b = T("encoder.conv2.bias");
+  h->enc_pos = T("encoder.positional_embedding");
+  h->ln_post_w = T("encoder.ln_post.weight");
+  h->ln_post_b = T("encoder.ln_post.bias");
+  h->enc.resize(h->hp.n_audio_layer);
+  for (int i = 0; i < h->hp.n_audio_layer; ++i) {
+    const std::string p = "encoder.blocks." + std::to_string(i) + ".";
+    EncLayer& L = h->enc[i];
+    L.ln1_w = T(p + "attn_ln.weight"); L.ln1_b = T(p + "attn_ln.bias");
+    L.ln2_w = T(p + "mlp_ln.weight"); L.ln2_b = T(p + "mlp_ln.bias");
+    L.out_b = T(p + "attn.out.bias"); L.fc1_b = T(p + "mlp.0.bias"); L.fc2_b = T(p + "mlp.2.bias");
+    L.qkv_w = L.out_w = L.fc1_w = L.fc2_w = nullptr;
+  }
+  h->dec.resize(h->hp.n_text_layer);
+  for (int i = 0; i < h->hp.n_text_layer; ++i) {
+    const std::string p = "decoder.blocks." + std::to_string(i) + ".";
+    DecLayer& L = h->dec[i];
+    L.ln1_w = T(p + "attn_ln.weight"); L.ln1_b = T(p + "attn_ln.bias");
+    L.lnx_w = T(p + "cross_attn_ln.weight"); L.lnx_b = T(p + "cross_attn_ln.bias");
+    L.ln2_w = T(p + "mlp_ln.weight"); L.ln2_b = T(p + "mlp_ln.bias");
+    L.out_b = T(p + "attn.out.bias"); L.xq_b = T(p + "cross_attn.query.bias");
+    L.xout_b = T(p + "cross_attn.out.bias"); L.fc1_b = T(p + "mlp.0.bias"); L.fc2_b = T(p + "mlp.2.bias");
+    L.qkv_w = L.out_w = L.xq_w = L.xkv_w = L.xout_w = L.fc1_w = L.fc2_w = nullptr;
+    L.qkv_lw = L.xq_lw = L.fc1_lw = nullptr;
+  }
+  h->tok_emb = nullptr;
+  h->dec_pos = T("decoder.positional_embedding");
+  h->dec_ln_w = T("decoder.ln.weight");
+  h->dec_ln_b = T("decoder.ln.bias");
+  return T.rc;
+}
+
+// crispy_asr_finalize of a dense model: every matrix is an f32 tensor; q | k | v and the cross k | v are fused by rows, the
+// LayerNorm in front of q | k | v, cross-q and fc1 is folded into the decode projections
+int finalize_dense(crispy_asr* h) {
+  const int d = h->hp.n_audio_state, dt = h->hp.n_text_state;
+  int rc = resolve_shared(h);
+  if (rc != CRISPY_OK) return rc;
+  Resolver T{h};
+  for (int i = 0; i < h->hp.n_audio_layer; ++i) {
+    const std::string p = "encoder.blocks." + std::to_string(i) + ".";
+    EncLayer& L = h->enc[i];
+    rc = fuse_rows(h, {p + "attn.query.weight", p + "attn.key.weight", p + "attn.value.weight"},
+                   {p + "attn.query.bias", "", p + "attn.value.bias"}, d, &L.qkv_w, &L.qkv_b);
+    if (rc != CRISPY_OK) return rc;
+    L.out_w = T(p + "attn.out.weight"); L.fc1_w = T(p + "mlp.0.weight"); L.fc2_w = T(p + "mlp.2.weight");
+  }
+  h->tok_emb = T("decoder.token_embedding.weight");
+  for (int i = 0; i < h->hp.n_text_layer; ++i) {
+    const std::string p = "decoder.blocks." + std::to_string(i) + ".";
+    DecLayer& L = h->dec[i];
+    rc = fuse_rows(h, {p + "attn.query.weight", p + "attn.key.weight", p + "attn.value.weight"},
+                   {p + "attn.query.bias", "", p + "attn.value.bias"}, dt, &L.qkv_w, &L.qkv_b);
+    if (rc != CRISPY_OK) return rc;
+    L.out_w = T(p + "attn.out.weight"); L.xq_w = T(p + "cross_attn.query.weight");
+    rc = fuse_rows(h, {p + "cross_attn.key.weight", p + "cross_attn.value.weight"}, {"", p + "cross_attn.value.bias"},
+                   dt, &L.xkv_w, &L.xkv_b);
+    if (rc != CRISPY_OK) return rc;
+    L.xout_w = T(p + "cross_attn.out.weight"); L.fc1_w = T(p + "mlp.0.weight"); L.fc2_w = T(p + "mlp.2.weight");
+    if (T.rc != CRISPY_OK) return T.rc;
+    rc = fold_ln(h, L.qkv_w, L.qkv_b, L.ln1_w, L.ln1_b, 3 * (size_t)dt, dt, &L.qkv_lw, &L.qkv_ls, &L.qkv_lc);
+    if (rc == CRISPY_OK) rc = fold_ln(h, L.xq_w, L.xq_b, L.lnx_w, L.lnx_b, dt, dt, &L.xq_lw, &L.xq_ls, &L.xq_lc);
+    if (rc == CRISPY_OK) rc = fold_ln(h, L.fc1_w, L.fc1_b, L.ln2_w, L.ln2_b, 4 * (size_t)dt, dt, &L.fc1_lw, &L.fc1_ls, &L.fc1_lc);
+    if (rc != CRISPY_OK) return rc;
+  }
+  if (T.rc != CRISPY_OK) return T.rc;
+  return finalize_tail(h);
+}
+
+// The resident token embedding for the logits: f16, packed in MFMA operand order, from a dense copy that lives for this
+// function only (pack, stream sync, then release)
+int pack_resident_tok_emb(crispy_asr* h) {
+  const int dt = h->hp.n_text_state, V = h->hp.n_vocab;
+  DevBuf<float> tmp;
+  HIP_TRY(tmp.alloc((size_t)V * dt * sizeof(float)));
+  HIP_TRY(dequant_blocks(h->q_tok_emb->d, h->q_tok_emb->ttype, (long)((size_t)V * dt / 32), dt, tmp, 0, nullptr, h->stream));
+  void* packed = nullptr;
+  const int rc = derived_copy(h, vocab_f16_packed_bytes(V, dt), &packed);
+  if (rc != CRISPY_OK) return rc;
+  HIP_TRY(pack_vocab_f16(tmp, packed, V, dt, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->tok_emb_hp = packed;
   return CRISPY_OK;
 }
 
@@ -360,25 +473,19 @@ int make_conv_halves(crispy_asr* h) {
 // its quantised form stays resident too and serves the embedding look-ups).  Precision mode 1 only: the operands of
 // every matrix product are de-quantised to f16 (f32 x gamma for the folded projections) right in front of the product.
 int finalize_resident(crispy_asr* h) {
-  const int d = h->hp.n_audio_state, dt = h->hp.n_text_state, V = h->hp.n_vocab;
-  if (!(dt == 384 || dt == 512 || dt == 768 || dt == 1024 || dt == 1280))
+  const int d = h->hp.n_audio_state, dt = h->hp.n_text_state;
+  if (!whisper_width_ok(dt))
     return fail(CRISPY_ERR_UNSUPPORTED, "crispy_asr_load_resident: width %d has no f16 logits kernel", dt);
-  int rc;
-  if ((rc = reorder_conv(h, "encoder.conv1.weight", d, h->hp.n_mels, &h->conv1_w)) != CRISPY_OK) return rc;
-  if ((rc = reorder_conv(h, "encoder.conv2.weight", d, d, &h->conv2_w)) != CRISPY_OK) return rc;
-  h->conv1_b = T(h, "encoder.conv1.bias");
-  h->conv2_b = T(h, "encoder.conv2.bias");
-  h->enc_pos = T(h, "encoder.positional_embedding");
-  h->ln_post_w = T(h, "encoder.ln_post.weight");
-  h->ln_post_b = T(h, "encoder.ln_post.bias");
+  int rc = resolve_shared(h);
+  if (rc != CRISPY_OK) return rc;
   // a matrix the file holds dense (f32 / f16: mixed files) takes part as a QT_F32 "block" tensor aliasing its dense copy
   auto matrix = [&](const std::string& name, int cols) -> int {
     if (h->qtensors.count(name)) return CRISPY_OK;
-    Tensor& t = h->tensors[name];
-    if (!t.d) return fail(CRISPY_ERR_BAD_MODEL, "crispy_asr_load_resident: tensor '%s' missing", name.c_str());
-    QTensor q;
-    q.d = reinterpret_cast<unsigned char*>(t.d); q.ttype = QT_F32; q.n = t.n; q.cols = cols; q.nbytes = t.n * 4; q.owned = false;
-    h->qtensors[name] = q;
+    const Tensor* t = find_tensor(h, name);
+    if (!t) return CRISPY_ERR_BAD_MODEL;
+    if (!t->d) return fail(CRISPY_ERR_BAD_MODEL, "crispy_asr_load_resident: tensor '%s' missing", name.c_str());
+    QTensor& q = h->qtensors[name];
+    q.d = reinterpret_cast<const unsigned char*>(t->d.p); q.ttype = QT_F32; q.n = t->n; q.cols = cols; q.nbytes = t->n * 4;
     return CRISPY_OK;
   };
   size_t max_elems = 0;
@@ -388,15 +495,9 @@ int finalize_resident(crispy_asr* h) {
     if (out->elems() > max_elems) max_elems = out->elems();
     return CRISPY_OK;
   };
-  h->enc.resize(h->hp.n_audio_layer);
-  h->dec.resize(h->hp.n_text_layer);
   for (int i = 0; i < h->hp.n_audio_layer; ++i) {
     const std::string p = "encoder.blocks." + std::to_string(i) + ".";
     EncLayer& L = h->enc[i];
-    L.ln1_w = T(h, p + "attn_ln.weight"); L.ln1_b = T(h, p + "attn_ln.bias");
-    L.ln2_w = T(h, p + "mlp_ln.weight"); L.ln2_b = T(h, p + "mlp_ln.bias");
-    L.out_b = T(h, p + "attn.out.bias"); L.fc1_b = T(h, p + "mlp.0.bias"); L.fc2_b = T(h, p + "mlp.2.bias");
-    L.qkv_w = L.out_w = L.fc1_w = L.fc2_w = nullptr;
     if ((rc = ref({p + "attn.query.weight", p + "attn.key.weight", p + "attn.value.weight"}, d, &L.r_qkv)) != CRISPY_OK) return rc;
     if ((rc = ref({p + "attn.out.weight"}, d, &L.r_out)) != CRISPY_OK) return rc;
     if ((rc = ref({p + "mlp.0.weight"}, d, &L.r_fc1)) != CRISPY_OK) return rc;
@@ -406,13 +507,6 @@ int finalize_resident(crispy_asr* h) {
   for (int i = 0; i < h->hp.n_text_layer; ++i) {
     const std::string p = "decoder.blocks." + std::to_string(i) + ".";
     DecLayer& L = h->dec[i];
-    L.ln1_w = T(h, p + "attn_ln.weight"); L.ln1_b = T(h, p + "attn_ln.bias");
-    L.lnx_w = T(h, p + "cross_attn_ln.weight"); L.lnx_b = T(h, p + "cross_attn_ln.bias");
-    L.ln2_w = T(h, p + "mlp_ln.weight"); L.ln2_b = T(h, p + "mlp_ln.bias");
-    L.out_b = T(h, p + "attn.out.bias"); L.xq_b = T(h, p + "cross_attn.query.bias");
-    L.xout_b = T(h, p + "cross_attn.out.bias"); L.fc1_b = T(h, p + "mlp.0.bias"); L.fc2_b = T(h, p + "mlp.2.bias");
-    L.qkv_w = L.out_w = L.xq_w = L.xkv_w = L.xout_w = L.fc1_w = L.fc2_w = nullptr;
-    L.qkv_lw = L.xq_lw = L.fc1_lw = nullptr;
     if ((rc = ref({p + "attn.query.weight", p + "attn.key.weight", p + "attn.value.weight"}, dt, &L.r_qkv)) != CRISPY_OK) return rc;
     if ((rc = ref({p + "attn.out.weight"}, dt, &L.r_out)) != CRISPY_OK) return rc;
     if ((rc = ref({p + "cross_attn.query.weight"}, dt, &L.r_xq)) != CRISPY_OK) return rc;
@@ -425,29 +519,9 @@ int finalize_resident(crispy_asr* h) {
   }
   if ((rc = matrix("decoder.token_embedding.weight", dt)) != CRISPY_OK) return rc;
   h->q_tok_emb = &h->qtensors["decoder.token_embedding.weight"];
-  h->tok_emb = nullptr;
-  h->dec_pos = T(h, "decoder.positional_embedding");
-  h->dec_ln_w = T(h, "decoder.ln.weight");
-  h->dec_ln_b = T(h, "decoder.ln.bias");
   // the one scratch slot: the largest (fused) matrix as f32
-  h->q_scratch_bytes = max_elems * sizeof(float);
-  HIP_TRY(hipMalloc(&h->q_scratch, h->q_scratch_bytes));
-  {   // token embedding for the logits: f16, packed in MFMA operand order, from a dense copy that lives for this block only
-    float* tmp = nullptr;
-    HIP_TRY(hipMalloc(&tmp, (size_t)V * dt * sizeof(float)));
-    hipError_t e = dequant_blocks(h->q_tok_emb->d, h->q_tok_emb->ttype, (long)((size_t)V * dt / 32), dt, tmp, 0, nullptr, h->stream);
-    void* packed = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&packed, vocab_f16_packed_bytes(V, dt));
-    if (e == hipSuccess) {
-      h->derived.push_back(reinterpret_cast<float*>(packed));
-      h->derived_bytes += vocab_f16_packed_bytes(V, dt);
-      e = pack_vocab_f16(tmp, packed, V, dt, h->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(tmp);
-    HIP_TRY(e);
-    h->tok_emb_hp = packed;
-  }
+  HIP_TRY(h->q_scratch.alloc(max_elems * sizeof(float)));
+  if ((rc = pack_resident_tok_emb(h)) != CRISPY_OK) return rc;
   if ((rc = make_conv_halves(h)) != CRISPY_OK) return rc;
   // One matrix per decoder layer is kept de-quantised as well: the cross-q projection, as f16 (the values the blocks
   // de-quantise to at the point of use: same bits).  The matrix-vector decode step computes a head's query in every one of the
@@ -457,9 +531,7 @@ int finalize_resident(crispy_asr* h) {
     for (DecLayer& L : h->dec) {
       if (!gemv_ref_ok(L.r_xq)) continue;
       void* p = nullptr;
-      HIP_TRY(hipMalloc(&p, (size_t)dt * dt * 2));
-      h->derived.push_back(reinterpret_cast<float*>(p));
-      h->derived_bytes += (size_t)dt * dt * 2;
+      if ((rc = derived_copy(h, (size_t)dt * dt * 2, &p)) != CRISPY_OK) return rc;
       HIP_TRY(dequant_blocks(L.r_xq.t[0]->d, L.r_xq.t[0]->ttype, (long)((size_t)dt * dt / 32), dt, p, 1, nullptr, h->stream));
       L.xq_wh = p;
     }
@@ -469,6 +541,53 @@ int finalize_resident(crispy_asr* h) {
   h->enc_precision = 1;
   h->dec_ln16 = true;                        // mode 1: f16 LayerNorm outputs against the blocks de-quantised to f16 (gemm_skinny_q, WH forms)
   return finalize_tail(h);
+}
+
+// Precision mode 1: f16 copies of the encoder GEMM weights and of the decoder's plain projections, made on the device once
+int make_mode1_halves(crispy_asr* h) {
+  const size_t d = h->hp.n_audio_state, dtt = h->hp.n_text_state;
+  int rc = make_conv_halves(h);
+  for (EncLayer& L : h->enc) {
+    if (rc == CRISPY_OK) rc = half_copy(h, L.qkv_w, 3 * d * d, &L.qkv_wh);
+    if (rc == CRISPY_OK) rc = half_copy(h, L.out_w, d * d, &L.out_wh);
+    if (rc == CRISPY_OK) rc = half_copy(h, L.fc1_w, 4 * d * d, &L.fc1_wh);
+    if (rc == CRISPY_OK) rc = half_copy(h, L.fc2_w, 4 * d * d, &L.fc2_wh);
+  }
+  for (DecLayer& L : h->dec) {
+    if (rc == CRISPY_OK) rc = half_copy(h, L.xkv_w, 2 * dtt * dtt, &L.xkv_wh);
+    if (rc == CRISPY_OK) rc = half_copy(h, L.out_w, dtt * dtt, &L.out_wh);
+    if (rc == CRISPY_OK) rc = half_copy(h, L.xout_w, dtt * dtt, &L.xout_wh);
+    if (rc == CRISPY_OK) rc = half_copy(h, L.fc2_w, 4 * dtt * dtt, &L.fc2_wh);
+  }
+  if (rc != CRISPY_OK) return rc;
+  const int dt = h->hp.n_text_state;
+  if (whisper_width_ok(dt)) {    // the widths the f16 logits kernel is built for
+    // token embedding for the logits: f16 (as the model file holds it), packed in MFMA operand order
+    void* p = nullptr;
+    if ((rc = derived_copy(h, vocab_f16_packed_bytes(h->hp.n_vocab, dt), &p)) != CRISPY_OK) return rc;
+    HIP_TRY(pack_vocab_f16(h->tok_emb, p, h->hp.n_vocab, dt, h->stream));
+    h->tok_emb_hp = p;
+  }
+  return CRISPY_OK;
+}
+
+// Precision modes 1 and 2: f16 copies of the decoder's q | k | v, cross-q and fc1 weights (un-folded: the LayerNorm runs as
+// a launch of its own), and the fused step kernels' operand order (same bytes once more)
+int make_ln16_halves(crispy_asr* h) {
+  const size_t dtt = h->hp.n_text_state;
+  const bool fused = fused_decode_supported((int)dtt, 1, h->hp.n_audio_ctx);
+  int rc = CRISPY_OK;
+  for (DecLayer& L : h->dec) {
+    if (rc == CRISPY_OK) rc = half_copy(h, L.qkv_w, 3 * dtt * dtt, &L.qkv_wh);
+    if (rc == CRISPY_OK) rc = half_copy(h, L.xq_w, dtt * dtt, &L.xq_wh);
+    if (rc == CRISPY_OK) rc = half_copy(h, L.fc1_w, 4 * dtt * dtt, &L.fc1_wh);
+    if (!fused) continue;
+    if (rc == CRISPY_OK) rc = packed_copy(h, L.qkv_wh, 3 * dtt * dtt, 0, &L.qkv_p);
+    if (rc == CRISPY_OK) rc = packed_copy(h, L.out_wh, dtt * dtt, 1, &L.out_p);
+    if (rc == CRISPY_OK) rc = packed_copy(h, L.fc1_wh, 4 * dtt * dtt, 2, &L.fc1_p);
+    if (rc == CRISPY_OK) rc = packed_copy(h, L.fc2_wh, 4 * dtt * dtt, 3, &L.fc2_p);
+  }
+  return rc;
 }
 
 }  // namespace
@@ -483,57 +602,7 @@ int crispy_asr_finalize(crispy_asr* h) try {
   for (const auto& kv : h->tensors)
     if (!kv.second.set) return fail(CRISPY_ERR_BAD_MODEL, "crispy_asr_finalize: tensor '%s' was never set", kv.first.c_str());
   HIP_TRY(hipSetDevice(h->device));
-  if (h->resident) return finalize_resident(h);
-  const int d = h->hp.n_audio_state, dt = h->hp.n_text_state;
-  int rc;
-  if ((rc = reorder_conv(h, "encoder.conv1.weight", d, h->hp.n_mels, &h->conv1_w)) != CRISPY_OK) return rc;
-  if ((rc = reorder_conv(h, "encoder.conv2.weight", d, d, &h->conv2_w)) != CRISPY_OK) return rc;
-  h->conv1_b = T(h, "encoder.conv1.bias");
-  h->conv2_b = T(h, "encoder.conv2.bias");
-  h->enc_pos = T(h, "encoder.positional_embedding");
-  h->ln_post_w = T(h, "encoder.ln_post.weight");
-  h->ln_post_b = T(h, "encoder.ln_post.bias");
-  h->enc.resize(h->hp.n_audio_layer);
-  for (int i = 0; i < h->hp.n_audio_layer; ++i) {
-    const std::string p = "encoder.blocks." + std::to_string(i) + ".";
-    EncLayer& L = h->enc[i];
-    L.ln1_w = T(h, p + "attn_ln.weight"); L.ln1_b = T(h, p + "attn_ln.bias");
-    rc = fuse_rows(h, {p + "attn.query.weight", p + "attn.key.weight", p + "attn.value.weight"},
-                   {p + "attn.query.bias", "", p + "attn.value.bias"}, d, &L.qkv_w, &L.qkv_b);
-    if (rc != CRISPY_OK) return rc;
-    L.out_w = T(h, p + "attn.out.weight"); L.out_b = T(h, p + "attn.out.bias");
-    L.ln2_w = T(h, p + "mlp_ln.weight"); L.ln2_b = T(h, p + "mlp_ln.bias");
-    L.fc1_w = T(h, p + "mlp.0.weight"); L.fc1_b = T(h, p + "mlp.0.bias");
-    L.fc2_w = T(h, p + "mlp.2.weight"); L.fc2_b = T(h, p + "mlp.2.bias");
-  }
-  h->tok_emb = T(h, "decoder.token_embedding.weight");
-  h->dec_pos = T(h, "decoder.positional_embedding");
-  h->dec_ln_w = T(h, "decoder.ln.weight");
-  h->dec_ln_b = T(h, "decoder.ln.bias");
-  h->dec.resize(h->hp.n_text_layer);
-  for (int i = 0; i < h->hp.n_text_layer; ++i) {
-    const std::string p = "decoder.blocks." + std::to_string(i) + ".";
-    DecLayer& L = h->dec[i];
-    L.ln1_w = T(h, p + "attn_ln.weight"); L.ln1_b = T(h, p + "attn_ln.bias");
-    rc = fuse_rows(h, {p + "attn.query.weight", p + "attn.key.weight", p + "attn.value.weight"},
-                   {p + "attn.query.bias", "", p + "attn.value.bias"}, dt, &L.qkv_w, &L.qkv_b);
-    if (rc != CRISPY_OK) return rc;
-    L.out_w = T(h, p + "attn.out.weight"); L.out_b = T(h, p + "attn.out.bias");
-    L.lnx_w = T(h, p + "cross_attn_ln.weight"); L.lnx_b = T(h, p + "cross_attn_ln.bias");
-    L.xq_w = T(h, p + "cross_attn.query.weight"); L.xq_b = T(h, p + "cross_attn.query.bias");
-    rc = fuse_rows(h, {p + "cross_attn.key.weight", p + "cross_attn.value.weight"}, {"", p + "cross_attn.value.bias"},
-                   dt, &L.xkv_w, &L.xkv_b);
-    if (rc != CRISPY_OK) return rc;
-    L.xout_w = T(h, p + "cross_attn.out.weight"); L.xout_b = T(h, p + "cross_attn.out.bias");
-    L.ln2_w = T(h, p + "mlp_ln.weight"); L.ln2_b = T(h, p + "mlp_ln.bias");
-    L.fc1_w = T(h, p + "mlp.0.weight"); L.fc1_b = T(h, p + "mlp.0.bias");
-    L.fc2_w = T(h, p + "mlp.2.weight"); L.fc2_b = T(h, p + "mlp.2.bias");
-    rc = fold_ln(h, L.qkv_w, L.qkv_b, L.ln1_w, L.ln1_b, 3 * (size_t)dt, dt, &L.qkv_lw, &L.qkv_ls, &L.qkv_lc);
-    if (rc == CRISPY_OK) rc = fold_ln(h, L.xq_w, L.xq_b, L.lnx_w, L.lnx_b, dt, dt, &L.xq_lw, &L.xq_ls, &L.xq_lc);
-    if (rc == CRISPY_OK) rc = fold_ln(h, L.fc1_w, L.fc1_b, L.ln2_w, L.ln2_b, 4 * (size_t)dt, dt, &L.fc1_lw, &L.fc1_ls, &L.fc1_lc);
-    if (rc != CRISPY_OK) return rc;
-  }
-  return finalize_tail(h);
+  return h->resident ? finalize_resident(h) : finalize_dense(h);
 } CRISPY_CATCH_RET("crispy_asr_finalize")
 
 int crispy_asr_hparams_get(const crispy_asr* h, crispy_asr_hparams* out) try {
@@ -542,7 +611,6 @@ int crispy_asr_hparams_get(const crispy_asr* h, crispy_asr_hparams* out) try {
   return CRISPY_OK;
 } CRISPY_CATCH_RET("crispy_asr_hparams_get")
 
-// mel (frame-major, padded) -> encoder output [B][1500][d]
 int crispy_asr_set_precision(crispy_asr* h, int mode) try {
   if (!h) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_set_precision: NULL handle");
   if (!h->finalized) return fail(CRISPY_ERR_BAD_MODEL, "crispy_asr_set_precision: model not finalized");
@@ -556,95 +624,17 @@ int crispy_asr_set_precision(crispy_asr* h, int mode) try {
   if (h->resident && (mode != 1 || want_attn16))
     return fail(CRISPY_ERR_UNSUPPORTED, "crispy_asr_set_precision: a resident quantised model runs in precision mode 1 only "
                 "(its matrices exist as f16 operands at the point of use, never as f32 tensors)");
+  // `half_ready` / `ln16_ready` are only set after the last copy and a stream sync: an allocation failing part-way (OOM on
+  // a large model) leaves the mode unchanged and a retry starts over (the partial copies stay owned by `derived` until the
+  // handle is freed) -- ADVICE r2.
   if (mode == 1 && !h->half_ready) {
-    // f16 copies of the encoder GEMM weights, made on the device once.  `half_ready` is only set after the last copy
-    // and a stream sync: a hipMalloc failing part-way (OOM on a large model) leaves the mode at 0 and a retry starts
-    // over (the partial copies stay owned by `derived` until the handle is freed) -- ADVICE r2.
-    const size_t d = h->hp.n_audio_state;
-    auto half_copy = [&](const float* w, size_t n, const void** out) -> int {
-      void* p = nullptr;
-      HIP_TRY(hipMalloc(&p, n * 2));
-      h->derived.push_back(reinterpret_cast<float*>(p));
-      h->derived_bytes += n * 2;
-      HIP_TRY(convert_f32_to_f16(w, p, (long)n, h->stream));
-      *out = p;
-      return CRISPY_OK;
-    };
-    int rc = half_copy(h->conv2_w, d * 3 * d, &h->conv2_wh);
-    if (rc == CRISPY_OK) {
-      // conv1 kernel [d][3 n_mels] as f16 rows zero-padded to a multiple of 32 columns (3 * 80 = 240 -> 256): the
-      // padded operand columns of A read on into the next frames (finite values) and meet zeros here
-      const int k1 = 3 * h->hp.n_mels, k1p = (k1 + 31) / 32 * 32;
-      void* p = nullptr;
-      HIP_TRY(hipMalloc(&p, d * k1p * 2));
-      h->derived.push_back(reinterpret_cast<float*>(p));
-      h->derived_bytes += d * k1p * 2;
-      HIP_TRY(hipMemsetAsync(p, 0, d * k1p * 2, h->stream));
-      HIP_TRY(convert_rows_f32_to_f16(h->conv1_w, k1, p, k1p, k1, (long)d, h->stream));
-      h->conv1_wh = p;
-      h->conv1_kp = k1p;
-    }
-    for (EncLayer& L : h->enc) {
-      if (rc == CRISPY_OK) rc = half_copy(L.qkv_w, 3 * d * d, &L.qkv_wh);
-      if (rc == CRISPY_OK) rc = half_copy(L.out_w, d * d, &L.out_wh);
-      if (rc == CRISPY_OK) rc = half_copy(L.fc1_w, 4 * d * d, &L.fc1_wh);
-      if (rc == CRISPY_OK) rc = half_copy(L.fc2_w, 4 * d * d, &L.fc2_wh);
-    }
-    for (DecLayer& L : h->dec)
-    {
-      const size_t dtt = h->hp.n_text_state;
-      if (rc == CRISPY_OK) rc = half_copy(L.xkv_w, 2 * dtt * dtt, &L.xkv_wh);
-      if (rc == CRISPY_OK) rc = half_copy(L.out_w, dtt * dtt, &L.out_wh);
-      if (rc == CRISPY_OK) rc = half_copy(L.xout_w, dtt * dtt, &L.xout_wh);
-      if (rc == CRISPY_OK) rc = half_copy(L.fc2_w, 4 * dtt * dtt, &L.fc2_wh);
-    }
+    const int rc = make_mode1_halves(h);
     if (rc != CRISPY_OK) return rc;
-    const int dt = h->hp.n_text_state;
-    if (dt == 384 || dt == 512 || dt == 768 || dt == 1024 || dt == 1280) {    // the widths the f16 logits kernel is built for
-      // token embedding for the logits: f16 (as the model file holds it), packed in MFMA operand order
-      void* p = nullptr;
-      HIP_TRY(hipMalloc(&p, vocab_f16_packed_bytes(h->hp.n_vocab, dt)));
-      h->derived.push_back(reinterpret_cast<float*>(p));
-      h->derived_bytes += vocab_f16_packed_bytes(h->hp.n_vocab, dt);
-      HIP_TRY(pack_vocab_f16(h->tok_emb, p, h->hp.n_vocab, dt, h->stream));
-      h->tok_emb_hp = p;
-    }
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->half_ready = true;
   }
   if (want_ln16 && !h->resident && !h->ln16_ready) {
-    // f16 copies of the decoder's q | k | v, cross-q and fc1 weights (un-folded: the LayerNorm runs as a launch of its own)
-    const size_t dtt = h->hp.n_text_state;
-    auto half_copy = [&](const float* w, size_t n, const void** out) -> int {
-      void* p = nullptr;
-      HIP_TRY(hipMalloc(&p, n * 2));
-      h->derived.push_back(reinterpret_cast<float*>(p));
-      h->derived_bytes += n * 2;
-      HIP_TRY(convert_f32_to_f16(w, p, (long)n, h->stream));
-      *out = p;
-      return CRISPY_OK;
-    };
-    int rc = CRISPY_OK;
-    for (DecLayer& L : h->dec) {
-      if (rc == CRISPY_OK) rc = half_copy(L.qkv_w, 3 * dtt * dtt, &L.qkv_wh);
-      if (rc == CRISPY_OK) rc = half_copy(L.xq_w, dtt * dtt, &L.xq_wh);
-      if (rc == CRISPY_OK) rc = half_copy(L.fc1_w, 4 * dtt * dtt, &L.fc1_wh);
-      if (fused_decode_supported((int)dtt, 1, h->hp.n_audio_ctx)) {      // the fused step kernels' operand order (same bytes once more)
-        auto packed = [&](const void* src, size_t n, int kind, const void** out) -> int {
-          void* p = nullptr;
-          HIP_TRY(hipMalloc(&p, n * 2));
-          h->derived.push_back(reinterpret_cast<float*>(p));
-          h->derived_bytes += n * 2;
-          HIP_TRY(fused_pack_weights(src, p, (int)dtt, kind, h->stream));
-          *out = p;
-          return CRISPY_OK;
-        };
-        if (rc == CRISPY_OK) rc = packed(L.qkv_wh, 3 * dtt * dtt, 0, &L.qkv_p);
-        if (rc == CRISPY_OK) rc = packed(L.out_wh, dtt * dtt, 1, &L.out_p);
-        if (rc == CRISPY_OK) rc = packed(L.fc1_wh, 4 * dtt * dtt, 2, &L.fc1_p);
-        if (rc == CRISPY_OK) rc = packed(L.fc2_wh, 4 * dtt * dtt, 3, &L.fc2_p);
-      }
-    }
+    const int rc = make_ln16_halves(h);
     if (rc != CRISPY_OK) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->ln16_ready = true;
@@ -664,15 +654,15 @@ namespace crispy {
 namespace asr {
 namespace {
 
-// the convolution stem: padded frame-major mel -> residual stream h->w_x [batch * 1500][d] (GELU, positional embedding added)
+// the convolution stem: padded frame-major mel -> residual stream h->ew.x [batch * 1500][d] (GELU, positional embedding added)
 int encode_stem(crispy_asr* h, const float* d_mel_t, int batch, hipStream_t s) {
   const int d = h->hp.n_audio_state, Tn = h->hp.n_audio_ctx, nm = h->hp.n_mels;
   if (h->enc_precision == 1) {
     // The convolution stem on the f16 matrix cores too (ggml runs a convolution as im2col in f16 x f16 kernel): the
     // frame-major mel is rounded to f16 once, conv1 writes GELU(h1) as f16 (it only feeds conv2), conv2 reads it as
     // a strided view and writes the f32 residual stream.  The f16 buffers alias the hidden-layer / h1 workspace.
-    _Float16* mel_h = reinterpret_cast<_Float16*>(h->w_h);                 // [batch][3002][n_mels] (+ padding)
-    _Float16* h1_h = reinterpret_cast<_Float16*>(h->w_h1);                 // [batch][3001][d], row 0 of a clip = zeros
+    _Float16* mel_h = h->ew.h.as<_Float16>();                 // [batch][3002][n_mels] (+ padding)
+    _Float16* h1_h = h->ew.h1.as<_Float16>();                 // [batch][3001][d], row 0 of a clip = zeros
     const long mel_n = (long)batch * (MEL_FRAMES + 2) * nm;
     HIP_TRY(convert_f32_to_f16(d_mel_t, mel_h, mel_n, s));
     HIP_TRY(hipMemsetAsync(mel_h + mel_n, 0, 64 * sizeof(_Float16), s));  // what the last row's padded columns read
@@ -689,7 +679,7 @@ int encode_stem(crispy_asr* h, const float* d_mel_t, int batch, hipStream_t s) {
       HGemmArgs g{};
       g.A = h1_h; g.lda = 2L * d; g.strideA = (long)(MEL_FRAMES + 1) * d;
       g.W = reinterpret_cast<const _Float16*>(h->conv2_wh); g.ldw = 3L * d;
-      g.C = h->w_x; g.ldc = d; g.strideC = (long)Tn * d;
+      g.C = h->ew.x; g.ldc = d; g.strideC = (long)Tn * d;
       g.bias = h->conv2_b; g.M = Tn; g.N = d; g.K = 3 * d;
       g.rowtab = h->enc_pos; g.rowtab_period = Tn;
       HIP_TRY(gemm_hh(g, HGEMM_TAB, batch, s));
@@ -697,9 +687,9 @@ int encode_stem(crispy_asr* h, const float* d_mel_t, int batch, hipStream_t s) {
   } else {
     // conv1 (k3, p1) + GELU: rows t of the padded frame-major mel are 3*n_mels contiguous floats
     // (the zero row in front of every clip's h1 is rewritten each call: precision mode 1 uses the same workspace as f16)
-    HIP_TRY(hipMemset2DAsync(h->w_h1, (size_t)(MEL_FRAMES + 1) * d * sizeof(float), 0, (size_t)d * sizeof(float), batch, s));
+    HIP_TRY(hipMemset2DAsync(h->ew.h1, (size_t)(MEL_FRAMES + 1) * d * sizeof(float), 0, (size_t)d * sizeof(float), batch, s));
     {
-      GemmArgs g = gemm(d_mel_t, nm, h->conv1_w, 3L * nm, h->w_h1 + d, d, h->conv1_b, MEL_FRAMES, d, 3 * nm);
+      GemmArgs g = gemm(d_mel_t, nm, h->conv1_w, 3L * nm, h->ew.h1 + d, d, h->conv1_b, MEL_FRAMES, d, 3 * nm);
       g.strideA = (long)(MEL_FRAMES + 2) * nm;
       g.strideC = (long)(MEL_FRAMES + 1) * d;
       g.gelu = 1;
@@ -707,7 +697,7 @@ int encode_stem(crispy_asr* h, const float* d_mel_t, int batch, hipStream_t s) {
     }
     // conv2 (k3, s2, p1) + GELU + positional embedding: row t' = frames 2t'-1 .. 2t'+1 of h1 (one zero row in front)
     {
-      GemmArgs g = gemm(h->w_h1, 2L * d, h->conv2_w, 3L * d, h->w_x, d, h->conv2_b, Tn, d, 3 * d);
+      GemmArgs g = gemm(h->ew.h1, 2L * d, h->conv2_w, 3L * d, h->ew.x, d, h->conv2_b, Tn, d, 3 * d);
       g.strideA = (long)(MEL_FRAMES + 1) * d;
       g.strideC = (long)Tn * d;
       g.gelu = 1;
@@ -719,7 +709,7 @@ int encode_stem(crispy_asr* h, const float* d_mel_t, int batch, hipStream_t s) {
   return CRISPY_OK;
 }
 
-// the encoder layers over h->w_x in precision mode 1
+// the encoder layers over h->ew.x in precision mode 1
 int encode_layers_f16(crispy_asr* h, int batch, hipStream_t s) {
   const int d = h->hp.n_audio_state, Tn = h->hp.n_audio_ctx, H = h->hp.n_audio_head;
   const long rows = (long)batch * Tn;
@@ -727,11 +717,11 @@ int encode_layers_f16(crispy_asr* h, int batch, hipStream_t s) {
   // whisper.cpp's numerics with the bytes halved: every activation that only feeds a matrix product is stored as the
   // f16 value the product would round it to anyway (LayerNorm output, q | k, V^T, attention output, MLP hidden
   // layer); the residual stream stays f32.  The f16 buffers alias the f32 workspace of the default mode.
-  void* xn_h = h->w_xn;                                                   // [rows][d] f16
-  void* qk_h = h->w_qkv;                                                  // [rows][2 d] f16
-  void* vt_h = reinterpret_cast<_Float16*>(h->w_qkv) + rows * 2L * d;     // [batch][d][ENC_TP] f16
-  void* att_h = h->w_att;                                                 // [rows][d] f16
-  void* hid_h = h->w_h;                                                   // [rows][4 d] f16
+  void* xn_h = h->ew.xn;                                                   // [rows][d] f16
+  void* qk_h = h->ew.qkv;                                                  // [rows][2 d] f16
+  void* vt_h = h->ew.qkv.as<_Float16>() + rows * 2L * d;     // [batch][d][ENC_TP] f16
+  void* att_h = h->ew.att;                                                 // [rows][d] f16
+  void* hid_h = h->ew.h;                                                   // [rows][4 d] f16
   const int swz = h->xcd_swizzle;
   auto hg = [&](const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias, int N, int K) {
     HGemmArgs g{};
@@ -747,7 +737,7 @@ int encode_layers_f16(crispy_asr* h, int batch, hipStream_t s) {
   };
   for (const EncLayer& L : h->enc) {
     const void* w = nullptr;
-    HIP_TRY(layernorm_f16out(h->w_x, L.ln1_w, L.ln1_b, xn_h, rows, d, s));
+    HIP_TRY(layernorm_f16out(h->ew.x, L.ln1_w, L.ln1_b, xn_h, rows, d, s));
     if ((rc = w16(L.qkv_wh, L.r_qkv, &w)) != CRISPY_OK) return rc;
     HIP_TRY(gemm_hh(hg(xn_h, d, w, d, qk_h, 2L * d, L.qkv_b, 2 * d, d), HGEMM_F16, 1, s));
     HIP_TRY(gemm_hh(hg(xn_h, d, reinterpret_cast<const _Float16*>(w) + 2L * d * d, d, vt_h, 0, L.qkv_b + 2 * d, d, d),
@@ -755,11 +745,11 @@ int encode_layers_f16(crispy_asr* h, int batch, hipStream_t s) {
     HIP_TRY(attn_encoder_h(qk_h, vt_h, att_h, batch, Tn, d, H, s, h->dec_attn16 ? 1 : 0));     // mode 2: ggml's rounding points inside the attention
     {
       if ((rc = w16(L.out_wh, L.r_out, &w)) != CRISPY_OK) return rc;
-      HGemmArgs g = hg(att_h, d, w, d, h->w_x, d, L.out_b, d, d);
-      g.residual = h->w_x; g.ldr = d;
+      HGemmArgs g = hg(att_h, d, w, d, h->ew.x, d, L.out_b, d, d);
+      g.residual = h->ew.x; g.ldr = d;
       HIP_TRY(gemm_hh(g, HGEMM_RES, 1, s));
     }
-    HIP_TRY(layernorm_f16out(h->w_x, L.ln2_w, L.ln2_b, xn_h, rows, d, s));
+    HIP_TRY(layernorm_f16out(h->ew.x, L.ln2_w, L.ln2_b, xn_h, rows, d, s));
     {
       if ((rc = w16(L.fc1_wh, L.r_fc1, &w)) != CRISPY_OK) return rc;
       HGemmArgs g = hg(xn_h, d, w, d, hid_h, 4L * d, L.fc1_b, 4 * d, d);
@@ -768,8 +758,8 @@ int encode_layers_f16(crispy_asr* h, int batch, hipStream_t s) {
     }
     {
       if ((rc = w16(L.fc2_wh, L.r_fc2, &w)) != CRISPY_OK) return rc;
-      HGemmArgs g = hg(hid_h, 4L * d, w, 4L * d, h->w_x, d, L.fc2_b, d, 4 * d);
-      g.residual = h->w_x; g.ldr = d;
+      HGemmArgs g = hg(hid_h, 4L * d, w, 4L * d, h->ew.x, d, L.fc2_b, d, 4 * d);
+      g.residual = h->ew.x; g.ldr = d;
       HIP_TRY(gemm_hh(g, HGEMM_RES, 1, s));
     }
   }
@@ -781,23 +771,23 @@ int encode_layers_f32(crispy_asr* h, int batch, hipStream_t s) {
   const int d = h->hp.n_audio_state, Tn = h->hp.n_audio_ctx, H = h->hp.n_audio_head;
   const long rows = (long)batch * Tn;
   for (const EncLayer& L : h->enc) {
-    HIP_TRY(layernorm_f32(h->w_x, L.ln1_w, L.ln1_b, h->w_xn, rows, d, s));
-    HIP_TRY(gemm_f32_nt(gemm(h->w_xn, d, L.qkv_w, d, h->w_qkv, 3L * d, L.qkv_b, (int)rows, 3 * d, d), 1, s));
-    HIP_TRY(attn_encoder_f32(h->w_qkv, h->w_att, batch, Tn, d, H, s));
+    HIP_TRY(layernorm_f32(h->ew.x, L.ln1_w, L.ln1_b, h->ew.xn, rows, d, s));
+    HIP_TRY(gemm_f32_nt(gemm(h->ew.xn, d, L.qkv_w, d, h->ew.qkv, 3L * d, L.qkv_b, (int)rows, 3 * d, d), 1, s));
+    HIP_TRY(attn_encoder_f32(h->ew.qkv, h->ew.att, batch, Tn, d, H, s));
     {
-      GemmArgs g = gemm(h->w_att, d, L.out_w, d, h->w_x, d, L.out_b, (int)rows, d, d);
-      g.residual = h->w_x; g.ldr = d;
+      GemmArgs g = gemm(h->ew.att, d, L.out_w, d, h->ew.x, d, L.out_b, (int)rows, d, d);
+      g.residual = h->ew.x; g.ldr = d;
       HIP_TRY(gemm_f32_nt(g, 1, s));
     }
-    HIP_TRY(layernorm_f32(h->w_x, L.ln2_w, L.ln2_b, h->w_xn, rows, d, s));
+    HIP_TRY(layernorm_f32(h->ew.x, L.ln2_w, L.ln2_b, h->ew.xn, rows, d, s));
     {
-      GemmArgs g = gemm(h->w_xn, d, L.fc1_w, d, h->w_h, 4L * d, L.fc1_b, (int)rows, 4 * d, d);
+      GemmArgs g = gemm(h->ew.xn, d, L.fc1_w, d, h->ew.h, 4L * d, L.fc1_b, (int)rows, 4 * d, d);
       g.gelu = 1;
       HIP_TRY(gemm_f32_nt(g, 1, s));
     }
     {
-      GemmArgs g = gemm(h->w_h, 4L * d, L.fc2_w, 4L * d, h->w_x, d, L.fc2_b, (int)rows, d, 4 * d);
-      g.residual = h->w_x; g.ldr = d;
+      GemmArgs g = gemm(h->ew.h, 4L * d, L.fc2_w, 4L * d, h->ew.x, d, L.fc2_b, (int)rows, d, 4 * d);
+      g.residual = h->ew.x; g.ldr = d;
       HIP_TRY(gemm_f32_nt(g, 1, s));
     }
   }
@@ -842,7 +832,7 @@ int crispy_asr_encode_device(crispy_asr* h, const float* d_mel_t, int batch, flo
   if (rc != CRISPY_OK) return rc;
   const long rows = (long)batch * h->hp.n_audio_ctx;
   const int d = h->hp.n_audio_state;
-  HIP_TRY(layernorm_f32(h->w_x, h->ln_post_w, h->ln_post_b, d_out, rows, d, s));
+  HIP_TRY(layernorm_f32(h->ew.x, h->ln_post_w, h->ln_post_b, d_out, rows, d, s));
   return CRISPY_OK;
 } CRISPY_CATCH_RET("crispy_asr_encode_device")
 
@@ -858,12 +848,12 @@ int crispy_asr_encode(crispy_asr* h, const float* pcm, long pcm_stride, const in
   if (rc != CRISPY_OK) return rc;
   rc = reserve_pcm(h, pcm_stride);
   if (rc != CRISPY_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(h->w_pcm, pcm, (size_t)batch * pcm_stride * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  rc = crispy_mel_compute_device(h->mel, h->w_pcm, pcm_stride, n_samples, batch, nullptr, h->w_melt, h->stream);
+  HIP_TRY(hipMemcpyAsync(h->ew.pcm, pcm, (size_t)batch * pcm_stride * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  rc = crispy_mel_compute_device(h->mel, h->ew.pcm, pcm_stride, n_samples, batch, nullptr, h->ew.melt, h->stream);
   if (rc != CRISPY_OK) return rc;
-  rc = crispy_asr_encode_device(h, h->w_melt, batch, h->w_enc, h->stream);
+  rc = crispy_asr_encode_device(h, h->ew.melt, batch, h->ew.enc, h->stream);
   if (rc != CRISPY_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(out, h->w_enc, (size_t)batch * h->hp.n_audio_ctx * h->hp.n_audio_state * sizeof(float),
+  HIP_TRY(hipMemcpyAsync(out, h->ew.enc, (size_t)batch * h->hp.n_audio_ctx * h->hp.n_audio_state * sizeof(float),
                          hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return CRISPY_OK;

@@ -50,11 +50,8 @@ int build_ts_masks(crispy_asr* h) {
     if (h->vocab[t] == " ") { blank = (int)t; break; }
   if (blank < V) f[blank] = 1;
   if (h->eot < V) f[h->eot] = 1;
-  if (!h->d_ts_mask) HIP_TRY(hipMalloc(&h->d_ts_mask, V));
-  if (!h->d_ts_mask_first) HIP_TRY(hipMalloc(&h->d_ts_mask_first, V));
-  HIP_TRY(hipMemcpy(h->d_ts_mask, m.data(), V, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->d_ts_mask_first, f.data(), V, hipMemcpyHostToDevice));
-  return CRISPY_OK;
+  const int rc = upload_mask(h->d_ts_mask, m);
+  return rc != CRISPY_OK ? rc : upload_mask(h->d_ts_mask_first, f);
 }
 
 namespace {
@@ -83,19 +80,16 @@ std::vector<int> non_speech_token_ids(const std::vector<std::string>& vocab) {
 }
 
 int build_nst_masks(crispy_asr* h) {
-  if (h->d_ts_mask_nst) return CRISPY_OK;
-  if (!h->d_ts_mask) { const int rc = build_ts_masks(h); if (rc != CRISPY_OK) return rc; }
+  if (h->d_ts_mask_first_nst) return CRISPY_OK;       // (the one made last)
+  if (!h->d_ts_mask_first) { const int rc = build_ts_masks(h); if (rc != CRISPY_OK) return rc; }
   const int V = h->hp.n_vocab;
   std::vector<unsigned char> m(V), f(V);
   HIP_TRY(hipMemcpy(m.data(), h->d_ts_mask, V, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(f.data(), h->d_ts_mask_first, V, hipMemcpyDeviceToHost));
   for (int t : non_speech_token_ids(h->vocab))
     if (t < V) { m[t] = 1; f[t] = 1; }
-  HIP_TRY(hipMalloc(&h->d_ts_mask_nst, V));
-  HIP_TRY(hipMalloc(&h->d_ts_mask_first_nst, V));
-  HIP_TRY(hipMemcpy(h->d_ts_mask_nst, m.data(), V, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->d_ts_mask_first_nst, f.data(), V, hipMemcpyHostToDevice));
-  return CRISPY_OK;
+  const int rc = upload_mask(h->d_ts_mask_nst, m);
+  return rc != CRISPY_OK ? rc : upload_mask(h->d_ts_mask_first_nst, f);
 }
 
 // One decoder of one pass over a window: the picks the device made, and whisper_full's bookkeeping replayed over them
@@ -528,13 +522,13 @@ int BatchCall::upload_and_encode() {
   // recording that was 40 MB zero-filled, copied and then copied again); what lies behind a clip's end in its row is
   // never read -- the log-mel takes n_samples per clip
   for (int k = 0; k < nb; ++k)
-    HIP_TRY(hipMemcpyAsync(h->w_pcm + (size_t)k * stride, pcm[live[k]], (size_t)lens[k] * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  rc = crispy_mel_compute_device(h->mel, h->w_pcm, (long)stride, lens.data(), nb, nullptr, h->w_melt, h->stream);
+    HIP_TRY(hipMemcpyAsync(h->ew.pcm + (size_t)k * stride, pcm[live[k]], (size_t)lens[k] * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  rc = crispy_mel_compute_device(h->mel, h->ew.pcm, (long)stride, lens.data(), nb, nullptr, h->ew.melt, h->stream);
   if (rc != CRISPY_OK) return rc;
-  rc = crispy_asr_encode_device(h, h->w_melt, nb, h->w_enc, h->stream);
+  rc = crispy_asr_encode_device(h, h->ew.melt, nb, h->ew.enc, h->stream);
   if (rc != CRISPY_OK) return rc;
   if (detect) {
-    rc = crispy_asr_detect_language_device(h, h->w_enc, nb, lang.data());
+    rc = crispy_asr_detect_language_device(h, h->ew.enc, nb, lang.data());
     if (rc != CRISPY_OK) return rc;
   } else if (sp.multilingual) {
     std::fill(lang.begin(), lang.end(), prompt[1]);
@@ -545,7 +539,7 @@ int BatchCall::upload_and_encode() {
 
 int BatchCall::decode_plain() {
   std::vector<int> toks((size_t)nb * max_new), n_out(nb, 0);
-  const int rc = crispy_asr_decode_greedy_lang_device(h, h->w_enc, nb, prompt.data(), n_init, detect ? lang.data() : nullptr, max_new,
+  const int rc = crispy_asr_decode_greedy_lang_device(h, h->ew.enc, nb, prompt.data(), n_init, detect ? lang.data() : nullptr, max_new,
                                                       toks.data(), n_out.data(), nullptr);
   if (rc != CRISPY_OK) return rc;
   for (int k = 0; k < nb; ++k) {
@@ -676,9 +670,9 @@ int BatchCall::seek_loop() {
     if (!(round == 0 && na == nb)) {     // round 0 with every clip active: the encoder output is already there
       std::vector<int> sk(na);
       for (int a = 0; a < na; ++a) sk[a] = seek[act[a]];
-      int rc = crispy_mel_window_device(h->mel, act.data(), sk.data(), na, nullptr, h->w_melt, h->stream);
+      int rc = crispy_mel_window_device(h->mel, act.data(), sk.data(), na, nullptr, h->ew.melt, h->stream);
       if (rc != CRISPY_OK) return rc;
-      rc = crispy_asr_encode_device(h, h->w_melt, na, h->w_enc, h->stream);
+      rc = crispy_asr_encode_device(h, h->ew.melt, na, h->ew.enc, h->stream);
       if (rc != CRISPY_OK) return rc;
     }
     for (int a = 0; a < na; ++a) {
@@ -705,7 +699,7 @@ int BatchCall::decode_round(const std::vector<int>& act, std::vector<Accepted>& 
     std::vector<int> still;
     // Groups of clips decoded together, n_dec rows each (rows [c n_dec, (c + 1) n_dec) of a group are the decoders of its
     // clip c: one cross K|V per clip, decode_ts's xgroup).  At temperature 0 that is every pending clip in one group, one
-    // row each, straight off h->w_enc while nothing has dropped out; above it the pending clips x best_of, in groups of
+    // row each, straight off h->ew.enc while nothing has dropped out; above it the pending clips x best_of, in groups of
     // at most kLadderRowsMax rows -- ALL of them side by side, not one clip after the other (a batch in
     // which a third of the windows fall back used to decode them one by one, five rows at a time).
     const int per_group = n_dec == 1 && !beam ? (int)pending.size() : std::max(1, kLadderRowsMax / n_dec);
@@ -727,7 +721,7 @@ int BatchCall::decode_round(const std::vector<int>& act, std::vector<Accepted>& 
 // one decode of the clips act[grp[c]], n_dec rows each, at t_cur
 int BatchCall::decode_group(const std::vector<int>& act, const std::vector<int>& grp, float t_cur, int n_dec, GroupPicks& out) {
   const int n_clips = (int)grp.size(), rows = n_clips * n_dec;
-  const float* d_enc = h->w_enc;
+  const float* d_enc = h->ew.enc;
   bool contiguous = true;               // the group's clips are w_enc's first n_clips, in order
   for (int c = 0; c < n_clips; ++c) contiguous = contiguous && grp[c] == c;
   int rc;
@@ -735,7 +729,7 @@ int BatchCall::decode_group(const std::vector<int>& act, const std::vector<int>&
     rc = reserve_enc_rep(n_clips);
     if (rc != CRISPY_OK) return rc;
     for (int c = 0; c < n_clips; ++c)
-      HIP_TRY(hipMemcpyAsync(d_enc_rep + (size_t)c * enc_clip, h->w_enc + (size_t)grp[c] * enc_clip, enc_clip * sizeof(float),
+      HIP_TRY(hipMemcpyAsync(d_enc_rep + (size_t)c * enc_clip, h->ew.enc + (size_t)grp[c] * enc_clip, enc_clip * sizeof(float),
                              hipMemcpyDeviceToDevice, h->stream));
     d_enc = d_enc_rep;
   }
@@ -875,14 +869,14 @@ int BatchCall::align_round(const std::vector<int>& act, std::vector<Accepted>& a
     n_frames.push_back(nf);
   }
   if (who.empty()) return CRISPY_OK;
-  const float* d_enc = h->w_enc;
+  const float* d_enc = h->ew.enc;
   bool contiguous = true;
   for (size_t c = 0; c < who.size(); ++c) contiguous = contiguous && who[c] == (int)c;
   if (!contiguous) {
     const int rc = reserve_enc_rep((int)who.size());
     if (rc != CRISPY_OK) return rc;
     for (size_t c = 0; c < who.size(); ++c)
-      HIP_TRY(hipMemcpyAsync(d_enc_rep + c * enc_clip, h->w_enc + (size_t)who[c] * enc_clip, enc_clip * sizeof(float),
+      HIP_TRY(hipMemcpyAsync(d_enc_rep + c * enc_clip, h->ew.enc + (size_t)who[c] * enc_clip, enc_clip * sizeof(float),
                              hipMemcpyDeviceToDevice, h->stream));
     d_enc = d_enc_rep;
   }

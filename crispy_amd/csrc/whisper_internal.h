@@ -6,6 +6,11 @@
 //   whisper_full.cpp   whisper_full on top of them: seek loop, temperature ladder, segments, results, the recording chunker
 //   whisper_align.hip  word-level timestamps: the alignment pass, its kernels, crispy_asr_{align,dtw}_device (reached from
 //                      whisper_full.cpp through a hook that file installs: not linked, a dtw request is unsupported)
+// Device memory: every buffer of the handle is a DevBuf member (api_util.h) -- the tensors, the resident blocks (a QTensor reads
+// through `d`, which is its own blocks or a dense Tensor's floats), the copies derived from them (crispy_asr::derived, made by
+// derived_copy in whisper_api.cpp and summed by crispy_asr_memory_info), the token masks (upload_mask), the de-quantisation slot,
+// the workspaces EncWs / DecWs / AlignWs.  crispy_asr_free drops the captured steps, which hold workspace addresses, and deletes
+// the handle; nothing is freed by name.
 // Reference surface: transcribe_rs::whisper_cpp::WhisperEngine::{load, transcribe} (src-tauri/src/managers/transcription.rs:138-141,
 // 183-185).
 #pragma once
@@ -29,7 +34,7 @@ namespace crispy {
 namespace asr {
 
 struct Tensor {
-  float* d = nullptr;
+  DevBuf<float> d;
   size_t n = 0;
   bool set = false;
 };
@@ -37,12 +42,12 @@ struct Tensor {
 // A 2-D tensor kept in HBM as the model file holds it (ggml blocks, asr_quant.h; ttype QT_F32: a dense f32 tensor of a
 // mixed file) and a row-wise concatenation of up to three of them (q | k | v, k | v): `crispy_asr_load_resident`.
 struct QTensor {
-  unsigned char* d = nullptr;
+  DevBuf<unsigned char> own;            // the blocks; holds nothing where d aliases a dense Tensor of the handle
+  const unsigned char* d = nullptr;     // what the kernels read
   int ttype = 0;
   size_t n = 0;          // elements
   int cols = 0;          // innermost dimension (K)
   size_t nbytes = 0;
-  bool owned = true;     // false: d aliases a dense Tensor of the handle
 };
 struct QRef {
   const QTensor* t[3] = {nullptr, nullptr, nullptr};
@@ -69,29 +74,6 @@ struct DecLayer {
   const float *qkv_lw, *qkv_ls, *qkv_lc, *xq_lw, *xq_ls, *xq_lc, *fc1_lw, *fc1_ls, *fc1_lc;
 };
 
-// A device allocation that belongs to its holder: freed with it (or when a fresh one is assigned over it), moved, never
-// copied.  alloc replaces what it holds, grow only when that is too small -- neither carries the contents over.  After a
-// failed alloc it holds nothing (bytes 0): the next call allocates again.
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
-  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) {
-    if (p) (void)hipFree(p);
-    p = nullptr; bytes = 0;
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n);
-    if (e == hipSuccess) bytes = n; else p = nullptr;
-    return e;
-  }
-  hipError_t grow(size_t n) { return n <= bytes ? hipSuccess : alloc(n); }
-  operator T*() const { return p; }
-  template <class U> U* as() const { return reinterpret_cast<U*>(p); }      // the same bytes as another element type (the f16 caches)
-};
-
 // Word alignment (whisper_align.hip): while an alignment prefill runs (`on`), layer_cross_and_mlp copies the cross-q rows
 // of every layer that holds an alignment head into q [slot][clip][row][n_text_state] -- the rows that layer's own
 // cross-attention reads.  Buffers grow on demand and live as long as the handle.
@@ -101,6 +83,13 @@ struct AlignWs {
   std::vector<int> slot;                       // [n_text_layer]: the layer's slot in q, -1 = none
   int rows = 0;                                // token rows per clip of the running pass
   bool on = false;
+};
+
+// The encoder workspace (reserve_enc / reserve_pcm: sizes), grown on demand.
+struct EncWs {
+  int cap_batch = 0;                         // clips the workspace holds
+  long cap_pcm_stride = 0;                   // samples per PCM row
+  DevBuf<float> melt, pcm, h1, x, xn, qkv, att, h, enc;
 };
 
 // The decoder workspace (reserve_dec: sizes; [cap_rows] = one entry per row the workspace holds).  Captured steps hold these
@@ -144,14 +133,12 @@ struct crispy_asr {
   hipStream_t stream = nullptr;
   crispy_mel* mel = nullptr;
   std::map<std::string, crispy::asr::Tensor> tensors;   // as named by the model file
-  std::vector<float*> derived;             // fused / reordered copies owned by the handle
-  size_t derived_bytes = 0;                // ... and their size (crispy_asr_memory_info)
+  std::vector<crispy::DevBuf<void>> derived;   // fused / reordered / f16 / packed copies owned by the handle (derived_copy)
   // resident quantised model (crispy_asr_load_resident): 2-D tensors stay as ggml blocks, de-quantised into ONE scratch
   // slot right in front of the kernel that consumes them (same stream: the consumer has finished before the next fill)
   bool resident = false;
   std::map<std::string, crispy::asr::QTensor> qtensors;
-  void* q_scratch = nullptr;
-  size_t q_scratch_bytes = 0;
+  crispy::DevBuf<void> q_scratch;
   hipEvent_t ev_scratch = nullptr;           // orders a caller's stream against the handle's around the scratch slot
   const crispy::asr::QTensor* q_tok_emb = nullptr;
   bool finalized = false;
@@ -177,20 +164,17 @@ struct crispy_asr {
   std::vector<crispy::asr::EncLayer> enc;
   const float *tok_emb = nullptr, *dec_pos = nullptr, *dec_ln_w = nullptr, *dec_ln_b = nullptr;
   std::vector<crispy::asr::DecLayer> dec;
-  unsigned char* d_suppress = nullptr;      // [n_vocab] tokens never emitted by the greedy decoder
-  unsigned char* d_suppress_first = nullptr;  // additionally suppressed at the first sampled position
-  unsigned char* d_lang_mask = nullptr;       // everything but the language tokens (auto-detection)
-  // workspace (grown on demand)
-  int cap_batch = 0;
-  float *w_melt = nullptr, *w_pcm = nullptr, *w_h1 = nullptr, *w_x = nullptr, *w_xn = nullptr, *w_qkv = nullptr,
-        *w_att = nullptr, *w_h = nullptr, *w_enc = nullptr;
-  long cap_pcm_stride = 0;
+  // token masks [n_vocab] (upload_mask)
+  crispy::DevBuf<unsigned char> d_suppress;        // tokens never emitted by the greedy decoder
+  crispy::DevBuf<unsigned char> d_suppress_first;  // additionally suppressed at the first sampled position
+  crispy::DevBuf<unsigned char> d_lang_mask;       // everything but the language tokens (auto-detection)
+  crispy::asr::EncWs ew;                     // encoder workspace
   crispy::asr::DecWs dw;                     // decoder workspace
   // timestamp-mode decoding (whisper.cpp no_timestamps = false)
-  unsigned char* d_ts_mask = nullptr;        // [n_vocab] whisper.cpp's always-suppressed specials
-  unsigned char* d_ts_mask_first = nullptr;  // ... plus suppress_blank (" " and EOT) at the first position
-  unsigned char* d_ts_mask_nst = nullptr;    // the two masks with whisper.cpp's non-speech tokens added (opts.suppress_nst; built on first use)
-  unsigned char* d_ts_mask_first_nst = nullptr;
+  crispy::DevBuf<unsigned char> d_ts_mask;         // whisper.cpp's always-suppressed specials
+  crispy::DevBuf<unsigned char> d_ts_mask_first;   // ... plus suppress_blank (" " and EOT) at the first position
+  crispy::DevBuf<unsigned char> d_ts_mask_nst;     // the two masks with whisper.cpp's non-speech tokens added (opts.suppress_nst; built on first use)
+  crispy::DevBuf<unsigned char> d_ts_mask_first_nst;
   std::vector<int> prompt_past;              // conditioning text the last single-chunk call ended with (opts.carry_context)
   // captured window-decode steps by what is baked into them: key class, kind of pick (greedy / sampling: different kernels),
   // rows, rows per clip, rules and mask.  A transcribe call alternates between several of them -- the greedy pass over all
@@ -230,6 +214,10 @@ std::map<std::string, size_t> expected_tensors(const crispy_asr_hparams& hp);
 // dense copy of a (row-concatenated) resident tensor in the handle's scratch slot, enqueued on `s` right in front of its consumer
 int dq(crispy_asr* h, const QRef& r, bool f16, const float* gamma, hipStream_t s, const void** out);
 void free_dec_ws(crispy_asr* h);
+// uploads a host byte vector [n_vocab] into one of the handle's token masks, allocating it on first use
+int upload_mask(DevBuf<unsigned char>& mask, const std::vector<unsigned char>& host);
+// the widths the kernels are built for: tiny, base, small, medium, large
+inline bool whisper_width_ok(int d) { return d == 384 || d == 512 || d == 768 || d == 1024 || d == 1280; }
 int reserve_enc(crispy_asr* h, int batch);
 int reserve_pcm(crispy_asr* h, long stride);
 GemmArgs gemm(const float* A, long lda, const float* W, long ldw, float* C, long ldc, const float* bias, int M, int N, int K);

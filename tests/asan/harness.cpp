@@ -10,6 +10,10 @@
 //   harness fuzz-ggml <model.bin> <n> <seed> <offsets.txt> [resident]
 //                                                            n seeded mutations of the file IN PLACE (the test hands over a
 //                                                            scratch copy), each loaded; every load must return a status
+//   harness oom-sweep <model.bin> [resident]                 the load, then what grows the workspaces (two encodes, a resampler),
+//                                                            once cleanly -- N device allocations -- and once per k = 1 .. N
+//                                                            with the k-th allocation failing: every run must return
+//                                                            CRISPY_ERR_OOM and leak nothing; exit status 0 if they all do
 //   harness rnnoise <model.txt>                              crispy_rn_weights_from_file; prints the status
 //   harness fuzz-rnnoise <model.txt> <n> <seed>
 //   harness decide                                           decision-logic cases on stdin, results on stdout (see below)
@@ -79,7 +83,32 @@ hipError_t rn_launch_tansig(const RnTables*, const float*, float*, long, int, hi
 
 namespace {
 
-int load_once(const char* path, bool resident, bool verbose) {
+// what grows the workspaces of a loaded engine (the launchers are no-ops): reserve_enc, reserve_pcm and mel_reserve at batch 1,
+// regrown at batch 2 with longer rows; then a resampler's planes (even row pitch: the f16-pair form) and its f32 workspace
+// (odd pitch), each regrown once
+int grow_workspaces(crispy_asr* h) {
+  crispy_asr_hparams hp{};
+  int rc = crispy_asr_hparams_get(h, &hp);
+  for (int batch = 1; batch <= 2 && rc == CRISPY_OK; ++batch) {
+    const long stride = 16000L * batch;
+    const std::vector<float> pcm((size_t)batch * stride, 0.f);
+    const std::vector<int> n(batch, (int)stride);
+    std::vector<float> out((size_t)batch * hp.n_audio_ctx * hp.n_audio_state);
+    rc = crispy_asr_encode(h, pcm.data(), stride, n.data(), batch, out.data());
+  }
+  if (rc != CRISPY_OK) return rc;
+  crispy_resampler* r = nullptr;
+  rc = crispy_resampler_create(0, &r);
+  const long n_in = 3 * RS_CHUNK, n_out = crispy_resampler_out_len(n_in);
+  std::vector<float> in(2 * n_in, 0.f), out(2 * (n_out + 1));
+  for (long pitch : {n_out, n_out + 1})
+    for (int batch = 1; batch <= 2 && rc == CRISPY_OK; ++batch)
+      rc = crispy_resampler_process_device(r, in.data(), n_in, n_in, batch, 1.f, 0, out.data(), pitch, nullptr);
+  if (r) crispy_resampler_destroy(r);
+  return rc;
+}
+
+int load_once(const char* path, bool resident, bool verbose, bool workspaces = false) {
   crispy_asr* h = nullptr;
   int rc = resident ? crispy_asr_load_resident(path, 0, &h) : crispy_asr_load(path, 0, &h);
   if (rc == CRISPY_OK && !resident) rc = crispy_asr_set_precision(h, 1);
@@ -93,10 +122,31 @@ int load_once(const char* path, bool resident, bool verbose) {
     int lt = 0;
     (void)crispy_asr_language_token(hp.n_vocab, "de", &lt);
     (void)crispy_asr_language_token(hp.n_vocab, "xx", &lt);
+    if (workspaces) rc = grow_workspaces(h);
   }
   if (verbose) printf("{\"status\": %d, \"error\": \"%s\"}\n", rc, rc == CRISPY_OK ? "" : crispy_last_error());
   if (h) crispy_asr_free(h);
   return rc;
+}
+
+int oom_sweep(const char* path, bool resident) {
+  shim_malloc_calls = 0;
+  shim_malloc_fail_at = 0;
+  int rc = load_once(path, resident, false, true);
+  const long n = shim_malloc_calls;
+  if (rc != CRISPY_OK) { printf("{\"fatal\": \"the clean run returned %d: %s\"}\n", rc, crispy_last_error()); return 2; }
+  long oom = 0;
+  std::string other;
+  for (long k = 1; k <= n; ++k) {
+    shim_malloc_calls = 0;
+    shim_malloc_fail_at = k;
+    rc = load_once(path, resident, false, true);
+    if (rc == CRISPY_ERR_OOM) ++oom;
+    else other += (other.empty() ? "[" : ", [") + std::to_string(k) + ", " + std::to_string(rc) + "]";
+  }
+  shim_malloc_fail_at = 0;
+  printf("{\"allocations\": %ld, \"oom\": %ld, \"other\": [%s]}\n", n, oom, other.c_str());
+  return oom == n ? 0 : 1;
 }
 
 std::vector<long> read_offsets(const char* path) {
@@ -293,6 +343,7 @@ int main(int argc, char** argv) {
   if (argc >= 3 && !strcmp(argv[1], "load")) return load_once(argv[2], argc > 3 && !strcmp(argv[3], "resident"), true) == CRISPY_OK ? 0 : 1;
   if (argc >= 6 && !strcmp(argv[1], "fuzz-ggml"))
     return fuzz_ggml(argv[2], atoi(argv[3]), (unsigned)atoi(argv[4]), argv[5], argc > 6 && !strcmp(argv[6], "resident"));
+  if (argc >= 3 && !strcmp(argv[1], "oom-sweep")) return oom_sweep(argv[2], argc > 3 && !strcmp(argv[3], "resident"));
   if (argc >= 3 && !strcmp(argv[1], "rnnoise")) return rnnoise_once(argv[2], true) == CRISPY_OK ? 0 : 1;
   if (argc >= 5 && !strcmp(argv[1], "fuzz-rnnoise")) return fuzz_rnnoise(argv[2], atoi(argv[3]), (unsigned)atoi(argv[4]));
   if (argc >= 2 && !strcmp(argv[1], "decide")) return decide();

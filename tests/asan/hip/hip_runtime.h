@@ -37,8 +37,13 @@ struct dim3 { unsigned x, y, z; dim3(unsigned a = 1, unsigned b = 1, unsigned c 
 // a cap on one allocation: a corrupt header that asks for terabytes must come back as an out-of-memory status, not take the box down
 static const size_t SHIM_MAX_ALLOC = (size_t)3 << 30;
 
+// the allocation-failure sweep of tests/asan/harness.cpp (oom-sweep): hipMalloc calls so far, and the call (counted from 1)
+// that reports out of memory instead of allocating; 0: none
+inline long shim_malloc_calls = 0;
+inline long shim_malloc_fail_at = 0;
+
 template <class T> static inline hipError_t hipMalloc(T** p, size_t n) {
-  if (n > SHIM_MAX_ALLOC) { *p = nullptr; return hipErrorOutOfMemory; }
+  if (++shim_malloc_calls == shim_malloc_fail_at || n > SHIM_MAX_ALLOC) { *p = nullptr; return hipErrorOutOfMemory; }
   *p = static_cast<T*>(malloc(n ? n : 1));
   return *p ? hipSuccess : hipErrorOutOfMemory;
 }

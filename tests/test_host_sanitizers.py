@@ -10,6 +10,8 @@ loaders make is bounds-checked; kernel launchers are no-ops), with -fsanitize=ad
     sized tensors) -- the cases that on a CPU-only box stop at NO_DEVICE before the reader sees them;
   * >= 2 000 seeded mutations (truncations, bit flips in the header / tensor headers / names, hostile 32-bit fields, hostile
     vocabulary lengths) of a valid one-layer Whisper file, through both loaders (inflate at load; resident quantised);
+  * an allocation-failure sweep: the load, set_precision(1), the calls that grow the encoder / log-mel / resampler workspaces,
+    once per device allocation with that allocation failing -- every run an out-of-memory status, nothing leaked or freed twice;
   * >= 2 000 seeded mutations of a valid rnnoise-nu text model;
   * whisper_full's decision logic -- replay_decoder / score_decoder / window_segments and the std::mt19937 variate -- on
     sequences produced by the oracle's decode_temperature over scripted decoders, compared field by field (a CPU parity test
@@ -133,6 +135,22 @@ def test_valid_files_load_and_hand_made_corrupt_ones_are_rejected(harness, one_l
             r = _run(harness, ["load", str(p), *mode])
             out = json.loads(r.stdout)
             assert r.returncode == 1 and out["status"] == -5 and word in out["error"], (word, mode, out)
+
+
+@pytest.mark.parametrize("kind", ["f16", "q5_0"])
+@pytest.mark.parametrize("resident", [False, True])
+def test_every_failing_device_allocation_is_an_out_of_memory_status_and_leaks_nothing(harness, one_layer_files, kind, resident):
+    """`harness oom-sweep`: the load, set_precision(1), two encodes that grow the encoder / mel workspaces and a resampler, run
+    once cleanly (N device allocations) and then N times with the k-th allocation failing.  Every one of the N runs must come
+    back as CRISPY_ERR_OOM -- never CRISPY_OK, never another status -- with no AddressSanitizer, UBSan or LeakSanitizer report
+    (_run asserts that: a buffer let go twice, or not at all, on any of the error paths shows here), exit status 0."""
+    hp, files = one_layer_files
+    r = _run(harness, ["oom-sweep", files[kind][0], *(["resident"] if resident else [])], timeout=1500)
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    print(kind, "resident" if resident else "inflate", out)
+    assert out.get("allocations", 0) >= 60, out
+    assert out["oom"] == out["allocations"] and out["other"] == [], out
+    assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
 
 
 @pytest.mark.parametrize("kind,resident", [("f16", False), ("q5_0", False), ("q5_0", True)])
