@@ -41,6 +41,10 @@ pub const CRISPY_MEL_BINS: usize = 201;
 pub type crispy_rn_layout = c_int;
 pub const CRISPY_RN_LAYOUT_TBF: crispy_rn_layout = 0;
 pub const CRISPY_RN_LAYOUT_BTF: crispy_rn_layout = 1;
+/// Sample formats of `crispy_rn_pull*` (the output callback's conversions, audio.rs:613-650).
+pub const CRISPY_PCM_F32: c_int = 0;
+pub const CRISPY_PCM_I16: c_int = 1;
+pub const CRISPY_PCM_U16: c_int = 2;
 
 #[repr(C)]
 pub struct crispy_rn {
@@ -211,6 +215,10 @@ extern "C" {
     pub fn crispy_rn_push(h: *mut crispy_rn, input: *const c_float, in_stride: c_long, n_in: c_long, out: *mut c_float, out_stride: c_long, vad: *mut c_float, n_out: *mut c_long) -> c_int;
     pub fn crispy_rn_last_push_ms(h: *mut crispy_rn, adapt_in_ms: *mut c_float, adapt_out_ms: *mut c_float) -> c_int;
     pub fn crispy_linear_resampler_count(input_rate: c_float, output_rate: c_float, n_before: c_long, n_in: c_long) -> c_long;
+    pub fn crispy_rn_playback_configure(h: *mut crispy_rn, output_rate: c_float) -> c_int;
+    pub fn crispy_rn_playback_buffered(h: *const crispy_rn) -> c_long;
+    pub fn crispy_rn_pull_device(h: *mut crispy_rn, n_frames: c_long, channels: c_int, format: c_int, d_out: *mut c_void, out_stride: c_long, n_live: *mut c_long, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_rn_pull(h: *mut crispy_rn, n_frames: c_long, channels: c_int, format: c_int, out: *mut c_void, out_stride: c_long, n_live: *mut c_long) -> c_int;
     pub fn crispy_rn_synchronize(h: *mut crispy_rn) -> c_int;
     pub fn crispy_rn_set_timing(h: *mut crispy_rn, enable: c_int) -> c_int;
     pub fn crispy_rn_last_kernel_ms(h: *mut crispy_rn, frame_kernel_ms: *mut c_float, total_ms: *mut c_float) -> c_int;
@@ -450,6 +458,30 @@ impl BatchDenoiser {
         check(unsafe { crispy_rn_push(self.h, input.as_ptr(), n_in as c_long, n_in as c_long, output.as_mut_ptr(), want as c_long, std::ptr::null_mut(), &mut got) })?;
         debug_assert_eq!(got as usize, want);
         Ok(got as usize)
+    }
+    /// The playback side of `RnnNoiseProcessor::new(_, output_rate, _)`: an empty `output_buf` of one second and
+    /// `resample_pos = 0`; from here on every `push` also feeds the ring that `pull` reads.
+    pub fn configure_playback(&mut self, output_rate: f32) -> Result<(), CrispyError> {
+        check(unsafe { crispy_rn_playback_configure(self.h, output_rate) })
+    }
+    /// `output_buf.len()`, the same for every stream.
+    pub fn playback_buffered(&self) -> Result<usize, CrispyError> {
+        let n = unsafe { crispy_rn_playback_buffered(self.h) };
+        if n < 0 {
+            check(n as c_int)?;
+        }
+        Ok(n as usize)
+    }
+    /// The body of one f32 output callback: `n_frames` calls of `next_sample` (audio.rs:297-314) per stream, each written
+    /// to `channels` interleaved channels.  output: `n_streams` rows of `n_frames * channels` samples (resized here).
+    /// Returns how many of the frames were real samples and not underrun zeros.  (i16 / u16 output: the C entry point.)
+    pub fn pull(&mut self, n_frames: usize, channels: usize, output: &mut Vec<f32>) -> Result<usize, CrispyError> {
+        let row = n_frames * channels;
+        output.resize(row * self.n_streams, 0.0);
+        let mut live: c_long = 0;
+        // SAFETY: output holds n_streams rows of n_frames * channels f32; the call returns when output is complete.
+        check(unsafe { crispy_rn_pull(self.h, n_frames as c_long, channels as c_int, CRISPY_PCM_F32, output.as_mut_ptr() as *mut c_void, row as c_long, &mut live) })?;
+        Ok(live as usize)
     }
 }
 impl Drop for BatchDenoiser {

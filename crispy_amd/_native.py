@@ -32,7 +32,9 @@ RN_SYMBOLS = (
     "crispy_rn_adapter_configure", "crispy_rn_adapter_set_volume", "crispy_rn_adapter_produced_rate_hz",
     "crispy_rn_push_out_len", "crispy_rn_push_device", "crispy_rn_push", "crispy_rn_last_push_ms",
     "crispy_linear_resampler_count",
+    "crispy_rn_playback_configure", "crispy_rn_playback_buffered", "crispy_rn_pull_device", "crispy_rn_pull",
 )
+PCM_F32, PCM_I16, PCM_U16 = 0, 1, 2      # CRISPY_PCM_*
 
 
 MEL_SYMBOLS = ("crispy_mel_create", "crispy_mel_destroy", "crispy_mel_compute",
@@ -173,6 +175,11 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_rn_last_push_ms.argtypes = [C.c_void_p, f32p, f32p]
     L.crispy_linear_resampler_count.argtypes = [C.c_float, C.c_float, C.c_long, C.c_long]
     L.crispy_linear_resampler_count.restype = C.c_long
+    L.crispy_rn_playback_configure.argtypes = [C.c_void_p, C.c_float]
+    L.crispy_rn_playback_buffered.argtypes = [C.c_void_p]
+    L.crispy_rn_playback_buffered.restype = C.c_long
+    L.crispy_rn_pull_device.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p]
+    L.crispy_rn_pull.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
     L.crispy_rn_debug_capture.argtypes = [C.c_void_p, C.c_int]
     L.crispy_rn_debug_read.argtypes = [C.c_void_p, C.c_int, f32p, C.c_size_t]
     L.crispy_mel_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]

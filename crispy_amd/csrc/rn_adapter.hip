@@ -5,6 +5,7 @@
 //                         x32768 into the staging rows the high-pass reads; the new remainder into the carry buffer
 //   (frame kernels)       the completed frames as one call through crispy_rn_process_device's enqueue path
 //   rn_adapt_out_kernel   clamp(y / 32768, -1, 1) x volume (audio.rs:270-273), first frame skipped (audio.rs:275-278)
+//   (ring append)         on a handle with playback configured: the returned samples into output_buf (rn_playback.hip)
 // Both kernels are streaming passes: lanes run along the samples of one stream, a workgroup covers 1024 consecutive samples.
 #include <hip/hip_runtime.h>
 
@@ -436,6 +437,10 @@ int push_device_impl(crispy_rn* h, const float* d_in, long in_stride, long n_in,
     HIP_TRY(rn_launch_adapt_out(ao, s));
     if (timed) HIP_TRY(hipEventRecord(a->ev[3], s));
     a->timed = timed;
+    if (h->pb) {      // playback configured: what push_sample appends to output_buf (audio.rs:280-285)
+      rc = rn_playback_append(h, d_out, out_stride, p.n_out, s);
+      if (rc != CRISPY_OK) return rc;
+    }
   }
   *n_out = p.n_out;
   return CRISPY_OK;
@@ -455,12 +460,16 @@ int crispy_rn_adapter_configure(crispy_rn* h, float input_rate, float volume) tr
     return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_adapter_configure: input_rate must be a positive number of Hz");
   if (volume != volume) return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_adapter_configure: volume is NaN");
   HIP_TRY(hipSetDevice(h->device));
-  int rc = rn_zero_state(h, -1);
+  const bool resample = std::fabs(input_rate - 48000.f) >= 1.f;
+  // the new processor's output_buf and resample_pos, on a handle with playback configured; first, as it may allocate
+  int rc = rn_playback_adapter_configured(h, resample ? 48000.f : input_rate, "crispy_rn_adapter_configure");
+  if (rc != CRISPY_OK) return rc;
+  rc = rn_zero_state(h, -1);
   if (rc != CRISPY_OK) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   RnAdapter* a = adapter_of(h);
   a->rate = input_rate;
-  a->resample = std::fabs(input_rate - 48000.f) >= 1.f;
+  a->resample = resample;
   a->volume = volume < 0.f ? 0.f : (volume > 1.f ? 1.f : volume);
   a->first = true;
   a->rs = LinResState();

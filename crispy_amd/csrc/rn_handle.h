@@ -1,5 +1,6 @@
 // rn_handle.h -- the RNNoise handle behind `crispy_rn` (include/crispy_hip.h), shared by the translation units that
-// implement its entry points: crispy_api.cpp (create / process / reset ...) and rn_adapter.hip (crispy_rn_push*).
+// implement its entry points: crispy_api.cpp (create / process / reset ...), rn_adapter.hip (crispy_rn_push*) and
+// rn_playback.hip (crispy_rn_pull*).
 #pragma once
 #include <cstddef>
 #include <vector>
@@ -9,6 +10,7 @@
 
 namespace crispy {
 struct RnAdapter;   // rn_adapter.hip
+struct RnPlayback;  // rn_playback.hip
 }
 
 struct crispy_rn {
@@ -66,6 +68,9 @@ struct crispy_rn {
   // the capture-rate adapter (crispy_rn_push*, rn_adapter.hip): created on first use, released through its own hook
   crispy::RnAdapter* ad = nullptr;
   void (*ad_free)(crispy::RnAdapter*) = nullptr;
+  // the playback ring (crispy_rn_playback_* / crispy_rn_pull*, rn_playback.hip): created by crispy_rn_playback_configure
+  crispy::RnPlayback* pb = nullptr;
+  void (*pb_free)(crispy::RnPlayback*) = nullptr;
 };
 
 namespace crispy {
@@ -74,4 +79,9 @@ namespace crispy {
 int rn_zero_state(crispy_rn* h, int stream);
 int rn_process_frames_device(crispy_rn* h, const float* d_in, float* d_out, float* d_vad, int n_frames, long stride_t, long stride_b,
                              hipStream_t s);
+// rn_playback.hip, both no-ops on a handle without playback configured: a new processor at effective input rate in_rate
+// (empty ring of in_rate samples, resample_pos 0; the output rate stays); the n samples per stream a push has just written to
+// d_rows [B][stride] appended to the ring on s
+int rn_playback_adapter_configured(crispy_rn* h, float in_rate, const char* who);
+int rn_playback_append(crispy_rn* h, const float* d_rows, long stride, long n, hipStream_t s);
 }  // namespace crispy

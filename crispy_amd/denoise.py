@@ -190,6 +190,40 @@ class DenoiseState:
         N.check(self._L.crispy_rn_last_push_ms(self._h, C.byref(a), C.byref(b)), self._L)
         return a.value, b.value
 
+    # -- the playback half (output_buf / next_sample on the device: crispy_rn_playback_* / crispy_rn_pull*) -----
+    PCM = {"f32": (N.PCM_F32, np.float32), "i16": (N.PCM_I16, np.int16), "u16": (N.PCM_U16, np.uint16)}
+
+    def playback_configure(self, output_rate: float):
+        """A fresh `output_buf` (one second at the effective input rate) and `resample_pos = 0`; from here on every push
+        feeds the ring.  Leaves the denoiser and the capture side of the adapter alone."""
+        N.check(self._L.crispy_rn_playback_configure(self._h, float(output_rate)), self._L)
+
+    def playback_buffered(self) -> int:
+        """`output_buf.len()`, the same for every stream."""
+        n = self._L.crispy_rn_playback_buffered(self._h)
+        if n < 0:
+            N.check(int(n), self._L)
+        return int(n)
+
+    def pull(self, n_frames: int, channels: int = 1, fmt: str = "f32", want_live: bool = False):
+        """`crispy_rn_pull`: n_frames calls of `next_sample` per stream, converted as the output callback does and written
+        to `channels` interleaved channels -> [B, n_frames * channels] of float32 / int16 / uint16 (and, with want_live,
+        how many of the frames were real samples, not underrun zeros)."""
+        code, dtype = self.PCM[fmt]
+        n = int(n_frames) * int(channels)
+        out = np.empty((self.n_streams, max(n, 0)), dtype=dtype)
+        live = C.c_long()
+        N.check(self._L.crispy_rn_pull(self._h, int(n_frames), int(channels), code, out.ctypes.data, max(n, 1),
+                                       C.byref(live)), self._L)
+        return (out, int(live.value)) if want_live else out
+
+    def pull_device(self, n_frames: int, d_out: int, out_stride: int, channels: int = 1, fmt: str = "f32", stream: int = 0) -> int:
+        """`crispy_rn_pull_device` on a device pointer; returns n_live (known on return, the work is only enqueued)."""
+        live = C.c_long()
+        N.check(self._L.crispy_rn_pull_device(self._h, int(n_frames), int(channels), self.PCM[fmt][0], d_out, int(out_stride),
+                                              C.byref(live), stream or None), self._L)
+        return int(live.value)
+
     def stage_tansig_device(self, d_x: int, d_y: int, n: int, sigmoid: bool = False):
         """tansig_approx / sigmoid_approx as the frame kernel evaluates them (stage entry point for parity tests)."""
         N.check(self._L.crispy_rn_stage_tansig_device(self._h, d_x, d_y, int(n), int(sigmoid), None), self._L)
@@ -275,6 +309,7 @@ class RnnNoiseProcessor:
         self.max_output_len = int(self.input_rate)
         self.denoise = DenoiseState(weights, n_streams, device)
         self.denoise.adapter_configure(input_rate, self.volume)     # the device form of all of the above: push_block
+        self.denoise.playback_configure(output_rate)                # ... and of output_buf / resample_pos: pull_block
         self.input_buf: deque = deque()
         self.output_buf: deque = deque()
         self.resample_pos = 0.0
@@ -290,8 +325,13 @@ class RnnNoiseProcessor:
         """A loop of `push_sample` over the columns of x [B, n], as one `crispy_rn_push`: resampler, framing, scaling,
         process_frame, clamp, volume and the first-frame drop all run on the device.  Returns [B, n_out] (n_out = 480 per
         completed frame; possibly 0).  The carried samples and the resampler state live in the handle, those of
-        `push_sample` in this object: drive a processor through one of the two.  `next_sample`'s ring is not fed."""
+        `push_sample` in this object: drive a processor through one of the two.  The samples returned also go to the
+        handle's playback ring, which `pull_block` reads; `next_sample` reads the ring `push_sample` fills."""
         return self.denoise.push(x)
+
+    def pull_block(self, n: int) -> np.ndarray:
+        """n calls of `next_sample` as one `crispy_rn_pull`, reading what `push_block` buffered: [B, n] float32."""
+        return self.denoise.pull(n)
 
     def push_sample(self, samples) -> Optional[np.ndarray]:
         samples = np.atleast_1d(np.asarray(samples, dtype=np.float32))

@@ -225,6 +225,48 @@ int crispy_rn_last_push_ms(crispy_rn *h, float *adapt_in_ms, float *adapt_out_ms
  * time proportional to n_before + n_in.  < 0 = error (negative count, rate not a positive number). */
 long crispy_linear_resampler_count(float input_rate, float output_rate, long n_before, long n_in);
 
+/*
+ * The playback half of RnnNoiseProcessor: `output_buf`, the deque of at most one second that push_sample appends to
+ * (audio.rs:280-285), and next_sample (audio.rs:297-314), the linear-interpolating read at input_rate / output_rate that
+ * the output callback makes once per output frame before it converts the sample to the device's format and writes it to
+ * every channel (audio.rs:610-657).  One crispy_rn_pull per playback callback, as there is one crispy_rn_push per capture
+ * callback; every result is bit for bit that of the per-sample loop.
+ *
+ * The ring is a device buffer [n_streams][max_output_len] f32 (max_output_len = the effective input rate `as usize`: 48000
+ * with the input resampler, else the configured rate), filled by a copy kernel at the end of every push; its head, its
+ * length and resample_pos live on the host, the same for every stream.  A pull runs the reference's f64 recurrence on the
+ * host, frame by frame (step = input_rate as f64 / output_rate as f64), uploads one (offset, fraction) pair per output frame,
+ * and one kernel gathers, interpolates -- s0 + (s1 - s0) * frac, three separately rounded f32 operations --, converts and
+ * fans out.  No volume is applied (it was at the push).  Fewer than two samples buffered: the frame is 0.0.
+ *
+ * A push and a pull on one handle must be ordered by the caller: enqueue both on the same stream, or order the streams
+ * with events.  A handle never configured for playback has no ring, its pushes run as before, crispy_rn_pull* on it is
+ * CRISPY_ERR_INVALID_ARG and crispy_rn_playback_buffered 0.
+ */
+#define CRISPY_PCM_F32 0   /* float: the sample */
+#define CRISPY_PCM_I16 1   /* int16_t: (s.clamp(-1, 1) * 32767.0) as i16, truncated toward zero */
+#define CRISPY_PCM_U16 2   /* uint16_t: ((s.clamp(-1, 1) * 0.5 + 0.5) * 65535.0) as u16; silence is 32767 */
+/* (An underrun's 0.0 is converted like any sample.  A NaN converts to integer 0, as Rust's `as` does; a finite input never
+ * produces one.) */
+/* Sets the output rate (a positive number of Hz), allocates the ring for the handle's current effective input rate, empties
+ * it and sets resample_pos = 0.  Touches neither the DenoiseState nor the adapter's carry, resampler or first-frame flag.
+ * crispy_rn_adapter_configure on a handle with playback configured is the new processor of audio.rs:955-965 here too: the
+ * ring is emptied and sized for the new rate, resample_pos = 0; the output rate stays.  The two may come in either order. */
+int crispy_rn_playback_configure(crispy_rn *h, float output_rate);
+/* output_buf.len(): samples per stream in the ring (0 on a handle without playback), < 0 = error */
+long crispy_rn_playback_buffered(const crispy_rn *h);
+/* n_frames calls of next_sample per stream.  DEVICE pointer d_out [n_streams][out_stride] elements of `format`
+ * (CRISPY_PCM_*): n_frames x channels valid elements per stream, frame-major, every channel of a frame the same value;
+ * nothing else is written.  Rows whose pointer and stride are 16-byte aligned are written with 16-byte stores.  n_live
+ * (nullable): how many frames of this pull were real samples and not underrun zeros, known on return.  Enqueued on
+ * hip_stream (NULL = own stream).  n_frames == 0 is a no-op.  CRISPY_ERR_INVALID_ARG: playback not configured, n_frames < 0
+ * or above 2^24, channels outside 1...8, an unknown format, out_stride < n_frames x channels, NULL h / d_out;
+ * CRISPY_ERR_OOM: the position upload buffers could not grow -- in both cases the handle's state is as it was. */
+int crispy_rn_pull_device(crispy_rn *h, long n_frames, int channels, int format, void *d_out, long out_stride,
+                          long *n_live, void *hip_stream);
+/* the same with a HOST pointer; returns when out is complete */
+int crispy_rn_pull(crispy_rn *h, long n_frames, int channels, int format, void *out, long out_stride, long *n_live);
+
 /* Block until everything enqueued on the handle's own stream has finished. */
 int crispy_rn_synchronize(crispy_rn *h);
 
