@@ -219,6 +219,16 @@ extern "C" {
     pub fn crispy_rn_playback_buffered(h: *const crispy_rn) -> c_long;
     pub fn crispy_rn_pull_device(h: *mut crispy_rn, n_frames: c_long, channels: c_int, format: c_int, d_out: *mut c_void, out_stride: c_long, n_live: *mut c_long, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_rn_pull(h: *mut crispy_rn, n_frames: c_long, channels: c_int, format: c_int, out: *mut c_void, out_stride: c_long, n_live: *mut c_long) -> c_int;
+    pub fn crispy_rn_record_configure(h: *mut crispy_rn, ring_samples: c_long) -> c_int;
+    pub fn crispy_rn_record_app_push_device(h: *mut crispy_rn, d_in: *const c_float, in_stride: c_long, n_frames: c_long, channels: c_int, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_rn_record_app_push(h: *mut crispy_rn, input: *const c_float, in_stride: c_long, n_frames: c_long, channels: c_int) -> c_int;
+    pub fn crispy_rn_level_device(h: *mut crispy_rn, d_in: *const c_float, in_stride: c_long, n_in: c_long, d_rms: *mut c_float, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_rn_level(h: *mut crispy_rn, input: *const c_float, in_stride: c_long, n_in: c_long, rms: *mut c_float) -> c_int;
+    pub fn crispy_rn_record_buffered(h: *const crispy_rn, mic: *mut c_long, app: *mut c_long) -> c_int;
+    pub fn crispy_rn_record_frames_ready(h: *const crispy_rn) -> c_long;
+    pub fn crispy_rn_record_drain_device(h: *mut crispy_rn, max_frames: c_long, format: c_int, d_out: *mut c_void, out_stride: c_long, n_frames: *mut c_long, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_rn_record_drain(h: *mut crispy_rn, max_frames: c_long, format: c_int, out: *mut c_void, out_stride: c_long, n_frames: *mut c_long) -> c_int;
+    pub fn crispy_record_worker_plan(mic_len: c_long, app_len: c_long, max_frames: c_long, mic_off: *mut c_long, app_off: *mut c_long, mic_left: *mut c_long, app_left: *mut c_long) -> c_long;
     pub fn crispy_rn_synchronize(h: *mut crispy_rn) -> c_int;
     pub fn crispy_rn_set_timing(h: *mut crispy_rn, enable: c_int) -> c_int;
     pub fn crispy_rn_last_kernel_ms(h: *mut crispy_rn, frame_kernel_ms: *mut c_float, total_ms: *mut c_float) -> c_int;
@@ -482,6 +492,61 @@ impl BatchDenoiser {
         // SAFETY: output holds n_streams rows of n_frames * channels f32; the call returns when output is complete.
         check(unsafe { crispy_rn_pull(self.h, n_frames as c_long, channels as c_int, CRISPY_PCM_F32, output.as_mut_ptr() as *mut c_void, row as c_long, &mut live) })?;
         Ok(live as usize)
+    }
+    /// `start_recording`: empty mic and app rings of `ring_samples` per stream (0 = the reference's ten seconds); from here on
+    /// every `push` that returns samples also feeds the mic ring that `record_drain` reads.
+    pub fn configure_recording(&mut self, ring_samples: usize) -> Result<(), CrispyError> {
+        check(unsafe { crispy_rn_record_configure(self.h, ring_samples as c_long) })
+    }
+    /// The app-audio capture handler (recording.rs:260-369): `n_frames` interleaved frames of `channels` samples per stream,
+    /// already at 48 kHz, downmixed on the device and appended to the app ring.  input: `n_streams` rows of `n_frames * channels`.
+    pub fn record_app_push(&mut self, input: &[f32], n_frames: usize, channels: usize) -> Result<(), CrispyError> {
+        let row = n_frames * channels;
+        if input.len() != row * self.n_streams {
+            return Err(CrispyError { code: CRISPY_ERR_INVALID_ARG, message: "BatchDenoiser::record_app_push: input length".into() });
+        }
+        // SAFETY: input holds n_streams rows of n_frames * channels samples; the call returns when they are in the ring.
+        check(unsafe { crispy_rn_record_app_push(self.h, input.as_ptr(), row as c_long, n_frames as c_long, channels as c_int) })
+    }
+    /// The capture callback's level meter (audio.rs:728-729, 779-781) over `n_in` samples of every stream: one rms per stream.
+    pub fn level(&mut self, input: &[f32], n_in: usize, rms: &mut Vec<f32>) -> Result<(), CrispyError> {
+        if input.len() != n_in * self.n_streams {
+            return Err(CrispyError { code: CRISPY_ERR_INVALID_ARG, message: "BatchDenoiser::level: input length".into() });
+        }
+        rms.resize(self.n_streams, 0.0);
+        // SAFETY: input holds n_streams rows of n_in samples, rms n_streams values; the call returns when rms is complete.
+        check(unsafe { crispy_rn_level(self.h, input.as_ptr(), n_in as c_long, n_in as c_long, rms.as_mut_ptr()) })
+    }
+    /// (mic, app): samples per stream in the two recording rings.
+    pub fn record_buffered(&self) -> Result<(usize, usize), CrispyError> {
+        let (mut mic, mut app): (c_long, c_long) = (0, 0);
+        check(unsafe { crispy_rn_record_buffered(self.h, &mut mic, &mut app) })?;
+        Ok((mic as usize, app as usize))
+    }
+    /// 1152-sample frames a drain without a limit would write now.
+    pub fn record_frames_ready(&self) -> Result<usize, CrispyError> {
+        let n = unsafe { crispy_rn_record_frames_ready(self.h) };
+        if n < 0 {
+            check(n as c_int)?;
+        }
+        Ok(n as usize)
+    }
+    /// The recording worker's loop body (commands/recording.rs:215-264) for at most `max_frames` frames: the WAV payload,
+    /// `n_streams` rows of `frames * 1152 * 2` interleaved s16 samples with L == R (output is resized here).  Returns the
+    /// frames written.  (f32 channel 0 for the transcriber, device pointers: the C entry points.)
+    pub fn record_drain(&mut self, max_frames: usize, output: &mut Vec<i16>) -> Result<usize, CrispyError> {
+        let n = self.record_frames_ready()?.min(max_frames);
+        let row = n * 1152 * 2;
+        output.resize(row * self.n_streams, 0);
+        if n == 0 {
+            return Ok(0);
+        }
+        let mut got: c_long = 0;
+        // SAFETY: output holds n_streams rows of n frames of 2304 i16 -- what the library announced; the call returns when
+        // output is complete.
+        check(unsafe { crispy_rn_record_drain(self.h, n as c_long, CRISPY_PCM_I16, output.as_mut_ptr() as *mut c_void, row as c_long, &mut got) })?;
+        debug_assert_eq!(got as usize, n);
+        Ok(got as usize)
     }
 }
 impl Drop for BatchDenoiser {

@@ -33,7 +33,11 @@ RN_SYMBOLS = (
     "crispy_rn_push_out_len", "crispy_rn_push_device", "crispy_rn_push", "crispy_rn_last_push_ms",
     "crispy_linear_resampler_count",
     "crispy_rn_playback_configure", "crispy_rn_playback_buffered", "crispy_rn_pull_device", "crispy_rn_pull",
+    "crispy_rn_record_configure", "crispy_rn_record_app_push_device", "crispy_rn_record_app_push",
+    "crispy_rn_level_device", "crispy_rn_level", "crispy_rn_record_buffered", "crispy_rn_record_frames_ready",
+    "crispy_rn_record_drain_device", "crispy_rn_record_drain", "crispy_record_worker_plan",
 )
+REC_FRAME = 1152                          # the recording worker's frame_size (commands/recording.rs:196)
 PCM_F32, PCM_I16, PCM_U16 = 0, 1, 2      # CRISPY_PCM_*
 
 
@@ -180,6 +184,19 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_rn_playback_buffered.restype = C.c_long
     L.crispy_rn_pull_device.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p]
     L.crispy_rn_pull.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    lp = C.POINTER(C.c_long)
+    L.crispy_rn_record_configure.argtypes = [C.c_void_p, C.c_long]
+    L.crispy_rn_record_app_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_void_p]
+    L.crispy_rn_record_app_push.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int]
+    L.crispy_rn_level_device.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p]
+    L.crispy_rn_level.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p]
+    L.crispy_rn_record_buffered.argtypes = [C.c_void_p, lp, lp]
+    L.crispy_rn_record_frames_ready.argtypes = [C.c_void_p]
+    L.crispy_rn_record_frames_ready.restype = C.c_long
+    L.crispy_rn_record_drain_device.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, lp, C.c_void_p]
+    L.crispy_rn_record_drain.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, lp]
+    L.crispy_record_worker_plan.argtypes = [C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p, lp, lp]
+    L.crispy_record_worker_plan.restype = C.c_long
     L.crispy_rn_debug_capture.argtypes = [C.c_void_p, C.c_int]
     L.crispy_rn_debug_read.argtypes = [C.c_void_p, C.c_int, f32p, C.c_size_t]
     L.crispy_mel_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]

@@ -211,6 +211,7 @@ void free_all(crispy_rn* h) {
     if (p) (void)hipFree(p);
   if (h->ad && h->ad_free) h->ad_free(h->ad);
   if (h->pb && h->pb_free) h->pb_free(h->pb);
+  if (h->rec && h->rec_free) h->rec_free(h->rec);
   for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ev_hp) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ev_fr) (void)hipEventDestroy(e);

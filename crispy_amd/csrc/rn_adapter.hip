@@ -5,7 +5,8 @@
 //                         x32768 into the staging rows the high-pass reads; the new remainder into the carry buffer
 //   (frame kernels)       the completed frames as one call through crispy_rn_process_device's enqueue path
 //   rn_adapt_out_kernel   clamp(y / 32768, -1, 1) x volume (audio.rs:270-273), first frame skipped (audio.rs:275-278)
-//   (ring append)         on a handle with playback configured: the returned samples into output_buf (rn_playback.hip)
+//   (ring append)         on a handle with playback configured: the returned samples into output_buf (rn_playback.hip);
+//                         on a handle that records: into the recording ring as well (rn_record.hip)
 // Both kernels are streaming passes: lanes run along the samples of one stream, a workgroup covers 1024 consecutive samples.
 #include <hip/hip_runtime.h>
 
@@ -439,6 +440,10 @@ int push_device_impl(crispy_rn* h, const float* d_in, long in_stride, long n_in,
     a->timed = timed;
     if (h->pb) {      // playback configured: what push_sample appends to output_buf (audio.rs:280-285)
       rc = rn_playback_append(h, d_out, out_stride, p.n_out, s);
+      if (rc != CRISPY_OK) return rc;
+    }
+    if (h->rec) {     // recording: what push_mono_to_buffers appends to the recording ring (audio.rs:701-726)
+      rc = rn_record_append_mic(h, d_out, out_stride, p.n_out, s);
       if (rc != CRISPY_OK) return rc;
     }
   }

@@ -1,6 +1,6 @@
 // rn_handle.h -- the RNNoise handle behind `crispy_rn` (include/crispy_hip.h), shared by the translation units that
 // implement its entry points: crispy_api.cpp (create / process / reset ...), rn_adapter.hip (crispy_rn_push*) and
-// rn_playback.hip (crispy_rn_pull*).
+// rn_playback.hip (crispy_rn_pull*), rn_record.hip (crispy_rn_record_*, crispy_rn_level*).
 #pragma once
 #include <cstddef>
 #include <vector>
@@ -11,6 +11,7 @@
 namespace crispy {
 struct RnAdapter;   // rn_adapter.hip
 struct RnPlayback;  // rn_playback.hip
+struct RnRecord;    // rn_record.hip
 }
 
 struct crispy_rn {
@@ -71,6 +72,9 @@ struct crispy_rn {
   // the playback ring (crispy_rn_playback_* / crispy_rn_pull*, rn_playback.hip): created by crispy_rn_playback_configure
   crispy::RnPlayback* pb = nullptr;
   void (*pb_free)(crispy::RnPlayback*) = nullptr;
+  // the recording rings (crispy_rn_record_*, rn_record.hip): created on first use, recording from crispy_rn_record_configure on
+  crispy::RnRecord* rec = nullptr;
+  void (*rec_free)(crispy::RnRecord*) = nullptr;
 };
 
 namespace crispy {
@@ -84,4 +88,10 @@ int rn_process_frames_device(crispy_rn* h, const float* d_in, float* d_out, floa
 // d_rows [B][stride] appended to the ring on s
 int rn_playback_adapter_configured(crispy_rn* h, float in_rate, const char* who);
 int rn_playback_append(crispy_rn* h, const float* d_rows, long stride, long n, hipStream_t s);
+// rn_playback.hip: its append kernel for any ring [B][cap] -- n <= cap samples per stream from src [B][src_stride] to ring
+// indices tail, tail + 1, ... modulo cap
+hipError_t rn_launch_ring_append(const float* src, long src_stride, float* ring, int cap, int tail, int n, int B, hipStream_t s);
+// rn_record.hip, a no-op on a handle that does not record: the n samples per stream a push has just written to d_rows
+// [B][stride] appended to the mic ring on s
+int rn_record_append_mic(crispy_rn* h, const float* d_rows, long stride, long n, hipStream_t s);
 }  // namespace crispy

@@ -177,7 +177,7 @@ __global__ __launch_bounds__(PB_THREADS) void rn_pull_kernel(RnPull a) {
 
 hipError_t launch_append(const RnRingAppend& a, hipStream_t s) {
   const long tiles = pb_tiles(a.n, PB_COPY_TILE);
-  const long per = PB_MAX_BLOCKS / tiles;              // streams per launch (tiles <= 47: cap is one second)
+  const long per = PB_MAX_BLOCKS / tiles;              // streams per launch (tiles <= 47 for a cap of one second, <= 2^18 for a recording ring)
   for (long b0 = 0; b0 < a.B; b0 += per) {
     RnRingAppend c = a;
     c.B = (int)(a.B - b0 < per ? a.B - b0 : per);
@@ -360,6 +360,19 @@ int pull_device_impl(crispy_rn* h, long n_frames, int channels, int format, void
 }
 
 }  // namespace
+
+// what rn_record.hip uses of this file (rn_handle.h): the append kernel on a ring of its own
+hipError_t rn_launch_ring_append(const float* src, long src_stride, float* ring, int cap, int tail, int n, int B, hipStream_t s) {
+  RnRingAppend a{};
+  a.src = src;
+  a.src_stride = src_stride;
+  a.ring = ring;
+  a.cap = cap;
+  a.tail = tail;
+  a.n = n;
+  a.B = B;
+  return launch_append(a, s);
+}
 
 // what rn_adapter.hip uses of this file (rn_handle.h)
 int rn_playback_adapter_configured(crispy_rn* h, float in_rate, const char* who) {

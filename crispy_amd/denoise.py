@@ -224,6 +224,77 @@ class DenoiseState:
                                               C.byref(live), stream or None), self._L)
         return int(live.value)
 
+    # -- the recording leg (rec ring, app ring, worker, s16 frames, level meter: crispy_rn_record_* / crispy_rn_level*) -----
+    REC_FRAME = N.REC_FRAME
+
+    def record_configure(self, ring_samples: int = 0):
+        """`start_recording`: empty mic and app rings of `ring_samples` per stream (0 = the reference's ten seconds); from
+        here on every push that returns samples feeds the mic ring.  Leaves denoiser, adapter and playback ring alone."""
+        N.check(self._L.crispy_rn_record_configure(self._h, int(ring_samples)), self._L)
+
+    def record_app_push(self, x: np.ndarray, channels: int = 1):
+        """`crispy_rn_record_app_push`: x [B, n_frames * channels] interleaved app audio at 48 kHz, downmixed on the device
+        and appended to the app ring."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[0] != self.n_streams or x.shape[1] % int(channels):
+            raise ValueError(f"record_app_push: x must be [{self.n_streams}, n_frames * channels]")
+        N.check(self._L.crispy_rn_record_app_push(self._h, x.ctypes.data, max(x.shape[1], 1), x.shape[1] // int(channels),
+                                                  int(channels)), self._L)
+
+    def record_app_push_device(self, d_in: int, in_stride: int, n_frames: int, channels: int = 1, stream: int = 0):
+        N.check(self._L.crispy_rn_record_app_push_device(self._h, d_in, int(in_stride), int(n_frames), int(channels),
+                                                         stream or None), self._L)
+
+    def level(self, x: np.ndarray) -> np.ndarray:
+        """`crispy_rn_level`: the callback's level meter over x [B, n], `(sum(mono * mono) / n).sqrt()` per stream with the
+        reference's f32 rounding; n == 0 gives zeros (the callback emits nothing then)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[0] != self.n_streams:
+            raise ValueError(f"level: x must be [{self.n_streams}, n]")
+        rms = np.zeros(self.n_streams, dtype=np.float32)
+        N.check(self._L.crispy_rn_level(self._h, x.ctypes.data, max(x.shape[1], 1), x.shape[1], rms.ctypes.data), self._L)
+        return rms
+
+    def level_device(self, d_in: int, in_stride: int, n_in: int, d_rms: int, stream: int = 0):
+        N.check(self._L.crispy_rn_level_device(self._h, d_in, int(in_stride), int(n_in), d_rms, stream or None), self._L)
+
+    def record_buffered(self):
+        """(mic, app): samples per stream in the two rings."""
+        mic, app = C.c_long(), C.c_long()
+        N.check(self._L.crispy_rn_record_buffered(self._h, C.byref(mic), C.byref(app)), self._L)
+        return int(mic.value), int(app.value)
+
+    def record_frames_ready(self) -> int:
+        """1152-sample frames a drain without a limit would write now."""
+        n = self._L.crispy_rn_record_frames_ready(self._h)
+        if n < 0:
+            N.check(int(n), self._L)
+        return int(n)
+
+    def record_drain(self, max_frames: Optional[int] = None, fmt: str = "i16") -> np.ndarray:
+        """`crispy_rn_record_drain`: the worker loop for at most max_frames frames (None: all that are ready).  'i16': the
+        WAV payload [B, n_frames * 1152 * 2] int16, L == R; 'f32': channel 0 as the transcriber reads it, [B, n_frames * 1152]."""
+        if fmt not in ("i16", "f32"):
+            raise ValueError("record_drain: fmt is 'i16' or 'f32'")
+        code, dtype = self.PCM[fmt]
+        ready = self.record_frames_ready()
+        n = ready if max_frames is None else min(ready, int(max_frames))
+        per = N.REC_FRAME * (2 if fmt == "i16" else 1)
+        out = np.empty((self.n_streams, max(n, 0) * per), dtype=dtype)
+        if n <= 0:
+            return out
+        got = C.c_long()
+        N.check(self._L.crispy_rn_record_drain(self._h, n, code, out.ctypes.data, n * per, C.byref(got)), self._L)
+        assert got.value == n
+        return out
+
+    def record_drain_device(self, max_frames: int, d_out: int, out_stride: int, fmt: str = "i16", stream: int = 0) -> int:
+        """`crispy_rn_record_drain_device` on a device pointer; returns the frames written (known on return)."""
+        got = C.c_long()
+        N.check(self._L.crispy_rn_record_drain_device(self._h, int(max_frames), self.PCM[fmt][0], d_out, int(out_stride),
+                                                      C.byref(got), stream or None), self._L)
+        return int(got.value)
+
     def stage_tansig_device(self, d_x: int, d_y: int, n: int, sigmoid: bool = False):
         """tansig_approx / sigmoid_approx as the frame kernel evaluates them (stage entry point for parity tests)."""
         N.check(self._L.crispy_rn_stage_tansig_device(self._h, d_x, d_y, int(n), int(sigmoid), None), self._L)
@@ -424,6 +495,24 @@ class CaptureBuffers:
                 self.rec_buffer.append(np.float32(o))
         self.sum = np.float32(self.sum + mono * mono)
         self.frames = np.float32(self.frames + np.float32(1.0))
+
+    # -- block form: one capture callback as one call, rings and level meter on the device ------------------------------
+    @staticmethod
+    def start_block(ns: "RnnNoiseProcessor", ring_samples: int = 0) -> None:
+        """`start_recording` for the block form: empty mic and app rings in the processor's handle (0 = ten seconds)."""
+        ns.denoise.record_configure(ring_samples)
+
+    @staticmethod
+    def push_mono_block(x: np.ndarray, ns: "RnnNoiseProcessor"):
+        """A capture callback over the columns of x [B, n] as `crispy_rn_push` + `crispy_rn_level`: the samples the
+        suppressor returned ([B, n_out], appended to the handle's recording ring on the device, which `drain_block` reads)
+        and the callback's rms per stream.  The RNNoise arm only: its recording resampler always passes through."""
+        return ns.push_block(x), ns.denoise.level(x)
+
+    @staticmethod
+    def drain_block(ns: "RnnNoiseProcessor", max_frames: Optional[int] = None, fmt: str = "i16") -> np.ndarray:
+        """The recording worker's loop body for the frames that are ready: see `DenoiseState.record_drain`."""
+        return ns.denoise.record_drain(max_frames, fmt)
 
     def rms(self) -> float:
         return float(np.sqrt(self.sum / self.frames)) if self.frames > 0 else 0.0

@@ -267,6 +267,73 @@ int crispy_rn_pull_device(crispy_rn *h, long n_frames, int channels, int format,
 /* the same with a HOST pointer; returns when out is complete */
 int crispy_rn_pull(crispy_rn *h, long n_frames, int channels, int format, void *out, long out_stride, long *n_live);
 
+/*
+ * The recording leg of the live path for all streams of a handle: the 48 kHz recording ring that push_mono_to_buffers
+ * appends push_sample's output to (audio.rs:701-726), the app-audio ring of the capture handlers, the recording worker that
+ * pops 1152-sample frames from both, keeps them within 50 ms of each other and adds them (commands/recording.rs:196-264),
+ * WavWriter::write_samples' quantisation to interleaved s16 (recording.rs:101-118), and the callback's level meter
+ * (audio.rs:728-729, 779-781).  Every result is bit for bit that of the per-sample loops.
+ *
+ * For the RNNoise arm the recording resampler always passes through (produced_rate_hz is within 1 Hz of 48000), so the mic
+ * ring receives exactly the bits a push returned: on a handle that records, every crispy_rn_push* that returns samples
+ * appends them to the mic ring on the same stream.  There is no entry point for it, and the bytes a push or a pull returns
+ * do not change.  Both rings are device buffers [n_streams][cap] f32 with the eviction of audio.rs:719-724 (the oldest
+ * sample goes for each one that does not fit; of a block of cap samples or more only the last cap survive).  Heads, lengths,
+ * the worker's trims and the frame count live on the host, the same for every stream.
+ *
+ * Push, app push and drain on one handle must be ordered by the caller: the same stream, or events.  A handle never
+ * configured for recording has no rings and pushes as before; app push and drain on it are CRISPY_ERR_INVALID_ARG, the
+ * buffered lengths and crispy_rn_record_frames_ready 0.
+ */
+/* start_recording: allocates both rings with cap = ring_samples (0 = the reference's 48000 * 10; otherwise 2 * 1152 ... 2^28)
+ * and empties them; again: empties them and, for another cap, replaces them -- the new ones are allocated before the old
+ * ones go, CRISPY_ERR_OOM leaves the handle as it was.  The default is 3.84 MB per stream for the two rings.  Touches
+ * neither the DenoiseState, the adapter state nor the playback ring; crispy_rn_adapter_configure (a model switch,
+ * audio.rs:955-965) and crispy_rn_reset leave the rings alone. */
+int crispy_rn_record_configure(crispy_rn *h, long ring_samples);
+/* The app-audio capture handlers (recording.rs:260-369): DEVICE pointer d_in [n_streams][in_stride], n_frames interleaved
+ * frames of `channels` (1...8) samples per stream, already at 48 kHz.  Downmix -- 1: the sample; 2: (f0 + f1) / 2.0; more:
+ * (0.0 + f0 + f1 + ...) / channels as f32, every add rounded, the division correctly rounded -- and append to the app ring.
+ * Enqueued on hip_stream (NULL = own stream).  n_frames == 0 is a no-op.  CRISPY_ERR_INVALID_ARG: recording not configured,
+ * n_frames < 0 or above 2^24, channels outside 1...8, in_stride < n_frames x channels, NULL h / d_in: the state is unchanged. */
+int crispy_rn_record_app_push_device(crispy_rn *h, const float *d_in, long in_stride, long n_frames, int channels,
+                                     void *hip_stream);
+/* the same with a HOST pointer; returns when the ring holds the frames */
+int crispy_rn_record_app_push(crispy_rn *h, const float *in, long in_stride, long n_frames, int channels);
+/* The capture callback's level meter, stateless: per stream sum = 0.0, then sum = sum + mono * mono in sample order over the
+ * n_in samples of d_in [n_streams][in_stride] (multiply and add rounded separately), d_rms[stream] = (sum / n_in as f32).sqrt().
+ * DEVICE pointers; enqueued on hip_stream (NULL = own stream).  n_in == 0 is a no-op that leaves d_rms untouched; n_in is at
+ * most 2^24, so the f32 count is exact.  Needs no recording configured. */
+int crispy_rn_level_device(crispy_rn *h, const float *d_in, long in_stride, long n_in, float *d_rms, void *hip_stream);
+/* the same with HOST pointers; returns when rms is complete */
+int crispy_rn_level(crispy_rn *h, const float *in, long in_stride, long n_in, float *rms);
+/* both ring lengths in samples per stream (either pointer may be NULL; 0 on a handle that does not record) */
+int crispy_rn_record_buffered(const crispy_rn *h, long *mic, long *app);
+/* how many 1152-sample frames a drain without a limit would write now, < 0 = error */
+long crispy_rn_record_frames_ready(const crispy_rn *h);
+/* The worker loop body (commands/recording.rs:215-264), while the mic ring holds 1152 samples and fewer than max_frames
+ * frames are done: align (a ring more than 2400 samples longer than the other loses the excess at its head), pop 1152 mic
+ * samples, pop 1152 app samples if there are as many, else take zeros and leave the app ring alone, mixed = mic + app,
+ * q = (mixed.clamp(-1, 1) * 32767.0) as i16 (truncated toward zero, a NaN is 0).  DEVICE pointer d_out
+ * [n_streams][out_stride] elements of `format`:
+ *   CRISPY_PCM_I16  the WAV payload: *n_frames x 1152 x 2 int16_t per stream, L and R equal
+ *   CRISPY_PCM_F32  channel 0 as run_transcription reads it back (commands/transcription.rs:306-313): q as f32 / 32768.0,
+ *                   *n_frames x 1152 floats per stream -- usable as d_in of crispy_resampler_process_device (scale 1, wav_s16 0)
+ * Nothing else is written; rows whose pointer and stride are 16-byte aligned are written with 16-byte stores.  *n_frames is
+ * known on return; the work is enqueued on hip_stream (NULL = own stream).  CRISPY_ERR_INVALID_ARG: recording not configured,
+ * max_frames < 0, an unknown format, NULL h / d_out / n_frames, out_stride shorter than the elements of this drain;
+ * CRISPY_ERR_OOM: the offset upload buffers could not grow -- in both cases the handle's state is as it was. */
+int crispy_rn_record_drain_device(crispy_rn *h, long max_frames, int format, void *d_out, long out_stride, long *n_frames,
+                                  void *hip_stream);
+/* the same with a HOST pointer; returns when out is complete */
+int crispy_rn_record_drain(crispy_rn *h, long max_frames, int format, void *out, long out_stride, long *n_frames);
+/* Pure, no device: the worker loop above on lengths alone.  Returns the number of frames (< 0 = error: a negative argument).
+ * Per frame f (arrays of at least min(max_frames, mic_len / 1152) entries, nullable): mic_off[f] = samples popped from the mic
+ * deque before the frame's own 1152, counted from its front at the start; app_off[f] likewise, or -1 for a frame whose app
+ * half is zeros.  mic_left / app_left (nullable): the lengths afterwards. */
+long crispy_record_worker_plan(long mic_len, long app_len, long max_frames, long *mic_off, long *app_off, long *mic_left,
+                               long *app_left);
+
 /* Block until everything enqueued on the handle's own stream has finished. */
 int crispy_rn_synchronize(crispy_rn *h);
 
