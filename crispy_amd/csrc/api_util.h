@@ -1,8 +1,10 @@
-// api_util.h -- error plumbing and the owner of a device allocation (DevBuf) shared by the extern "C" translation units.
+// api_util.h -- error plumbing and the owners of a device allocation (DevBuf) and of a list of events (EventList) shared by
+// the extern "C" translation units.
 #pragma once
 #include <cstddef>
 #include <cstdlib>
 #include <utility>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -56,6 +58,26 @@ struct DevBuf {
   hipError_t grow(size_t n) { return n <= bytes ? hipSuccess : alloc(n); }
   operator T*() const { return p; }
   template <class U> U* as() const { return reinterpret_cast<U*>(p); }      // the same bytes as another element type (the f16 caches)
+};
+
+// Events that belong to their holder: destroyed with it, never copied.  ensure(n, flags) creates what is missing up to n
+// (flags as for hipEventCreateWithFlags; 0: events that can be timed).  The holder's device must be current when one is let go.
+struct EventList {
+  std::vector<hipEvent_t> v;
+  EventList() = default;
+  EventList(const EventList&) = delete;
+  EventList& operator=(const EventList&) = delete;
+  ~EventList() { for (hipEvent_t e : v) (void)hipEventDestroy(e); }
+  hipError_t ensure(size_t n, unsigned flags) {
+    while (v.size() < n) {
+      hipEvent_t e;
+      const hipError_t rc = hipEventCreateWithFlags(&e, flags);
+      if (rc != hipSuccess) return rc;
+      v.push_back(e);
+    }
+    return hipSuccess;
+  }
+  hipEvent_t operator[](size_t i) const { return v[i]; }
 };
 
 }  // namespace crispy

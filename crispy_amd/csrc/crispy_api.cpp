@@ -3,7 +3,7 @@
 // Host side of the batched RNNoise path: owns the per-stream state tensors in HBM, the device
 // tables, the repacked weights and the workspace; enqueues high-pass -> frame -> history-roll
 // kernels per chunk of frames.  No CPU compute path exists here: without a gfx950 device every
-// constructor fails.  The handle is declared in rn_handle.h; the capture-rate adapter (crispy_rn_push*) is rn_adapter.hip.
+// constructor fails.  The handle is declared in rn_handle.h; push / pull / record (crispy_rn_push* ...) are rn_io.cpp.
 #include "../../include/crispy_hip.h"
 #include "api_util.h"
 #include "rn_common.h"
@@ -200,31 +200,6 @@ void pack_weights(std::vector<uint32_t>& out, const int8_t* w) {
 
 // (struct crispy_rn: rn_handle.h)
 
-void free_all(crispy_rn* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  void* ptrs[] = {h->d_tab, h->d_wpack, h->d_hp_mem, h->d_synth, h->d_ceps, h->d_lastg, h->d_rnn,
-                  h->d_last_gain, h->d_last_period, h->d_memid, h->d_xhp, h->d_dbg, h->d_stage_in,
-                  h->d_stage_out, h->d_stage_vad};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (h->ad && h->ad_free) h->ad_free(h->ad);
-  if (h->pb && h->pb_free) h->pb_free(h->pb);
-  if (h->rec && h->rec_free) h->rec_free(h->rec);
-  for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-  for (hipEvent_t e : h->ev_hp) (void)hipEventDestroy(e);
-  for (hipEvent_t e : h->ev_fr) (void)hipEventDestroy(e);
-  if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
-  for (hipEvent_t e : h->ev_in) (void)hipEventDestroy(e);
-  for (hipEvent_t e : h->ev_done) (void)hipEventDestroy(e);
-  if (h->h2d_stream) { (void)hipStreamSynchronize(h->h2d_stream); (void)hipStreamDestroy(h->h2d_stream); }
-  if (h->d2h_stream) { (void)hipStreamSynchronize(h->d2h_stream); (void)hipStreamDestroy(h->d2h_stream); }
-  if (h->hp_stream) { (void)hipStreamSynchronize(h->hp_stream); (void)hipStreamDestroy(h->hp_stream); }
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-}
-
 int zero_state(crispy_rn* h, int stream) {
   const int b0 = stream < 0 ? 0 : stream;
   const size_t n = stream < 0 ? (size_t)h->B : 1;
@@ -247,6 +222,18 @@ int zero_state(crispy_rn* h, int stream) {
 
 int process_device_impl(crispy_rn* h, const void* d_in, void* d_out, float* d_vad, float* d_taps, int n_frames,
                         long stride_t, long stride_b, hipStream_t s, bool s16 = false);
+// what crispy_rn_process_device and crispy_rn_process_s16_device check; with n_frames == 0 there is nothing to do
+int check_process_device(const crispy_rn* h, const void* d_in, const void* d_out, int n_frames, crispy_rn_layout layout, const char* who) {
+  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "%s: NULL handle", who);
+  if (n_frames < 0) return fail(CRISPY_ERR_INVALID_ARG, "%s: n_frames < 0", who);
+  if (n_frames == 0) return CRISPY_OK;
+  if (!d_in || !d_out) return fail(CRISPY_ERR_INVALID_ARG, "%s: NULL audio pointer", who);
+  if (layout != CRISPY_RN_LAYOUT_TBF && layout != CRISPY_RN_LAYOUT_BTF)
+    return fail(CRISPY_ERR_INVALID_ARG, "%s: unknown layout %d", who, (int)layout);
+  if (((uintptr_t)d_in | (uintptr_t)d_out) & 15)
+    return fail(CRISPY_ERR_INVALID_ARG, "%s: audio pointers must be 16-byte aligned", who);
+  return CRISPY_OK;
+}
 int process_host_impl(crispy_rn* h, const void* in, void* out, float* vad, int n_frames, crispy_rn_layout layout, bool s16);
 
 }  // namespace
@@ -393,7 +380,7 @@ int crispy_rn_create(const int8_t* weights, size_t nbytes, int n_streams, int de
   int rc = CRISPY_OK;
   auto body = [&]() -> int {
     HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&h->stream.s, hipStreamNonBlocking));
     {
       // The helper stream must not share a hardware queue with the main stream (the high-pass of the next
       // sub-chunks has to run *beside* the frame kernel): HIP multiplexes streams of one priority over a small pool
@@ -402,21 +389,21 @@ int crispy_rn_create(const int8_t* weights, size_t nbytes, int n_streams, int de
       // stream gets the highest one -- which also suits it: its kernels are short and gate the frame kernels.
       int least = 0, greatest = 0;
       HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-      HIP_TRY(hipStreamCreateWithPriority(&h->hp_stream, hipStreamNonBlocking, greatest));
+      HIP_TRY(hipStreamCreateWithPriority(&h->hp_stream.s, hipStreamNonBlocking, greatest));
     }
-    HIP_TRY(hipEventCreateWithFlags(&h->ev_begin, hipEventDisableTiming));
+    HIP_TRY(h->ev_begin.ensure(1, hipEventDisableTiming));
     const size_t B = (size_t)n_streams;
-    HIP_TRY(hipMalloc(&h->d_tab, sizeof(RnTables)));
-    HIP_TRY(hipMalloc(&h->d_wpack, sizeof(uint32_t) * RnPack8::END));
-    HIP_TRY(hipMalloc(&h->d_hp_mem, B * 2 * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_synth, B * 480 * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_ceps, B * 176 * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_lastg, B * RN_NB * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_rnn, B * 168 * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_last_gain, B * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_last_period, B * sizeof(int)));
-    HIP_TRY(hipMalloc(&h->d_memid, B * sizeof(int)));
-    HIP_TRY(hipMalloc(&h->d_xhp, B * h->xhp_stride * sizeof(float)));
+    HIP_TRY(h->d_tab.alloc(sizeof(RnTables)));
+    HIP_TRY(h->d_wpack.alloc(sizeof(uint32_t) * RnPack8::END));
+    HIP_TRY(h->d_hp_mem.alloc(B * 2 * sizeof(float)));
+    HIP_TRY(h->d_synth.alloc(B * 480 * sizeof(float)));
+    HIP_TRY(h->d_ceps.alloc(B * 176 * sizeof(float)));
+    HIP_TRY(h->d_lastg.alloc(B * RN_NB * sizeof(float)));
+    HIP_TRY(h->d_rnn.alloc(B * 168 * sizeof(float)));
+    HIP_TRY(h->d_last_gain.alloc(B * sizeof(float)));
+    HIP_TRY(h->d_last_period.alloc(B * sizeof(int)));
+    HIP_TRY(h->d_memid.alloc(B * sizeof(int)));
+    HIP_TRY(h->d_xhp.alloc(B * h->xhp_stride * sizeof(float)));
     {
       const char* hp = dev_env("CRISPY_RN_HP");
       h->hp_upfront = hp && std::strcmp(hp, "upfront") == 0;
@@ -447,14 +434,14 @@ int crispy_rn_create(const int8_t* weights, size_t nbytes, int n_streams, int de
   rc = body();
   if (rc != CRISPY_OK) {
     const std::string keep = last_error_cstr();
-    free_all(h);
+    delete h;
     return fail(rc, "%s", keep.c_str());
   }
   *out = h;
   return CRISPY_OK;
 } CRISPY_CATCH_RET("crispy_rn_create")
 
-void crispy_rn_destroy(crispy_rn* h) { free_all(h); }
+void crispy_rn_destroy(crispy_rn* h) { delete h; }     // ~crispy_rn (rn_handle.h) drains the streams first
 
 int crispy_rn_n_streams(const crispy_rn* h) { return h ? h->B : 0; }
 
@@ -478,14 +465,8 @@ int crispy_rn_reset(crispy_rn* h, int stream) try {
 
 int crispy_rn_process_device(crispy_rn* h, const float* d_in, float* d_out, float* d_vad, float* d_taps,
                              int n_frames, crispy_rn_layout layout, void* hip_stream) try {
-  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_process_device: NULL handle");
-  if (n_frames < 0) return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_process_device: n_frames < 0");
-  if (n_frames == 0) return CRISPY_OK;
-  if (!d_in || !d_out) return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_process_device: NULL audio pointer");
-  if (layout != CRISPY_RN_LAYOUT_TBF && layout != CRISPY_RN_LAYOUT_BTF)
-    return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_process_device: unknown layout %d", (int)layout);
-  if (((uintptr_t)d_in | (uintptr_t)d_out) & 15)
-    return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_process_device: audio pointers must be 16-byte aligned");
+  const int rc = check_process_device(h, d_in, d_out, n_frames, layout, "crispy_rn_process_device");
+  if (rc != CRISPY_OK || n_frames == 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
   const long stride_t = layout == CRISPY_RN_LAYOUT_TBF ? (long)h->B * RN_FRAME : (long)RN_FRAME;
@@ -495,14 +476,8 @@ int crispy_rn_process_device(crispy_rn* h, const float* d_in, float* d_out, floa
 
 int crispy_rn_process_s16_device(crispy_rn* h, const int16_t* d_in, int16_t* d_out, float* d_vad, int n_frames,
                                  crispy_rn_layout layout, void* hip_stream) try {
-  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_process_s16_device: NULL handle");
-  if (n_frames < 0) return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_process_s16_device: n_frames < 0");
-  if (n_frames == 0) return CRISPY_OK;
-  if (!d_in || !d_out) return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_process_s16_device: NULL audio pointer");
-  if (layout != CRISPY_RN_LAYOUT_TBF && layout != CRISPY_RN_LAYOUT_BTF)
-    return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_process_s16_device: unknown layout %d", (int)layout);
-  if (((uintptr_t)d_in | (uintptr_t)d_out) & 15)
-    return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_process_s16_device: audio pointers must be 16-byte aligned");
+  const int rc = check_process_device(h, d_in, d_out, n_frames, layout, "crispy_rn_process_s16_device");
+  if (rc != CRISPY_OK || n_frames == 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
   const long stride_t = layout == CRISPY_RN_LAYOUT_TBF ? (long)h->B * RN_FRAME : (long)RN_FRAME;
@@ -544,33 +519,21 @@ int process_device_impl(crispy_rn* h, const void* d_in_v, void* d_out_v, float* 
     const int T = (n_frames - t0) < kChunkFrames ? (n_frames - t0) : kChunkFrames;
     // The high-pass of this segment may start once everything already enqueued on `s` is done
     // (producer of d_in, previous segment's frame kernels and history roll).
-    HIP_TRY(hipEventRecord(h->ev_begin, s));
-    HIP_TRY(hipStreamWaitEvent(h->hp_stream, h->ev_begin, 0));
+    HIP_TRY(hipEventRecord(h->ev_begin[0], s));
+    HIP_TRY(hipStreamWaitEvent(h->hp_stream, h->ev_begin[0], 0));
     const int n_sub = count_subs(T);
-    while ((int)h->ev_hp.size() < n_sub) {
-      hipEvent_t ne;
-      HIP_TRY(hipEventCreateWithFlags(&ne, hipEventDisableTiming));
-      h->ev_hp.push_back(ne);
-    }
+    HIP_TRY(h->ev_hp.ensure((size_t)n_sub, hipEventDisableTiming));
     hipEvent_t* e = nullptr;
     if (h->timing) {
-      while (h->ev.size() < h->ev_used + 2 + 2 * (size_t)n_sub) {
-        hipEvent_t ne;
-        HIP_TRY(hipEventCreate(&ne));
-        h->ev.push_back(ne);
-      }
-      e = &h->ev[h->ev_used];
+      HIP_TRY(h->ev.ensure(h->ev_used + 2 + 2 * (size_t)n_sub, 0));
+      e = h->ev.v.data() + h->ev_used;
       h->ev_used += 2 + 2 * (size_t)n_sub;
       HIP_TRY(hipEventRecord(e[0], s));
     }
     // high-pass sub-chunks on the helper stream, enqueued up to `hp_ahead` sub-chunks in front of the frame kernels
     // (0: all of them back to back at once)
     int hp_next = 0, hp_ts = 0;
-    while ((int)h->ev_fr.size() < n_sub) {
-      hipEvent_t ne;
-      HIP_TRY(hipEventCreateWithFlags(&ne, hipEventDisableTiming));
-      h->ev_fr.push_back(ne);
-    }
+    HIP_TRY(h->ev_fr.ensure((size_t)n_sub, hipEventDisableTiming));
     auto enqueue_hp_until = [&](int last) -> int {
       for (; hp_next <= last && hp_next < n_sub; ++hp_next) {
         const int i = hp_next, ts = hp_ts;
@@ -661,29 +624,25 @@ int process_host_impl(crispy_rn* h, const void* in_v, void* out_v, float* vad, i
   char* out = static_cast<char*>(out_v);
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)n_frames * h->B * RN_FRAME;
-  if (h->stage_frames < (size_t)n_frames) {
-    if (h->d_stage_in) (void)hipFree(h->d_stage_in);
-    if (h->d_stage_out) (void)hipFree(h->d_stage_out);
-    if (h->d_stage_vad) (void)hipFree(h->d_stage_vad);
-    h->d_stage_in = h->d_stage_out = h->d_stage_vad = nullptr;
-    h->stage_frames = 0;
-    HIP_TRY(hipMalloc(&h->d_stage_in, n * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_stage_out, n * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->d_stage_vad, (size_t)n_frames * h->B * sizeof(float)));
-    h->stage_frames = (size_t)n_frames;
+  {
+    const int rc = h->stage_reserve(n * sizeof(float), n * sizeof(float), (size_t)n_frames * h->B * sizeof(float), "crispy_rn_process");
+    if (rc != CRISPY_OK) return rc;
   }
+  unsigned char* const d_stage_in = h->stage_in.p;
+  unsigned char* const d_stage_out = h->stage_out.p;
+  float* const d_stage_vad = h->stage_aux.p;
   const size_t B = (size_t)h->B;
   const size_t frame_bytes = B * RN_FRAME * esz;          // one frame of every stream
   if (n * esz < (size_t)(8u << 20)) {
     // small calls (the single-stream process_frame drop-in): one copy in, one call, one copy out
-    HIP_TRY(hipMemcpyAsync(h->d_stage_in, in, n * esz, hipMemcpyHostToDevice, h->stream));
-    int rc = process_device_impl(h, h->d_stage_in, h->d_stage_out, vad ? h->d_stage_vad : nullptr, nullptr, n_frames,
+    HIP_TRY(hipMemcpyAsync(d_stage_in, in, n * esz, hipMemcpyHostToDevice, h->stream));
+    int rc = process_device_impl(h, d_stage_in, d_stage_out, vad ? d_stage_vad : nullptr, nullptr, n_frames,
                                  layout == CRISPY_RN_LAYOUT_TBF ? (long)h->B * RN_FRAME : (long)RN_FRAME,
                                  layout == CRISPY_RN_LAYOUT_TBF ? (long)RN_FRAME : (long)n_frames * RN_FRAME, h->stream, s16);
     if (rc != CRISPY_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out, h->d_stage_out, n * esz, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(out, d_stage_out, n * esz, hipMemcpyDeviceToHost, h->stream));
     if (vad)
-      HIP_TRY(hipMemcpyAsync(vad, h->d_stage_vad, (size_t)n_frames * h->B * sizeof(float),
+      HIP_TRY(hipMemcpyAsync(vad, d_stage_vad, (size_t)n_frames * h->B * sizeof(float),
                              hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return CRISPY_OK;
@@ -703,16 +662,11 @@ int process_host_impl(crispy_rn* h, const void* in_v, void* out_v, float* vad, i
     // copy streams in the lowest-priority queue pool: never on the hardware queue of the main or the helper stream
     int least = 0, greatest = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    if (!h->h2d_stream) HIP_TRY(hipStreamCreateWithPriority(&h->h2d_stream, hipStreamNonBlocking, least));
-    if (!h->d2h_stream) HIP_TRY(hipStreamCreateWithPriority(&h->d2h_stream, hipStreamNonBlocking, least));
+    if (!h->h2d_stream) HIP_TRY(hipStreamCreateWithPriority(&h->h2d_stream.s, hipStreamNonBlocking, least));
+    if (!h->d2h_stream) HIP_TRY(hipStreamCreateWithPriority(&h->d2h_stream.s, hipStreamNonBlocking, least));
   }
-  while ((int)h->ev_in.size() < n_pieces) {
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-    h->ev_in.push_back(e0);
-    HIP_TRY(hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-    h->ev_done.push_back(e1);
-  }
+  HIP_TRY(h->ev_in.ensure((size_t)n_pieces, hipEventDisableTiming));
+  HIP_TRY(h->ev_done.ensure((size_t)n_pieces, hipEventDisableTiming));
   const bool tbf = layout == CRISPY_RN_LAYOUT_TBF;
   const long stride_t = tbf ? (long)B * RN_FRAME : (long)RN_FRAME;
   const long stride_b = tbf ? (long)RN_FRAME : (long)n_frames * RN_FRAME;
@@ -738,9 +692,9 @@ int process_host_impl(crispy_rn* h, const void* in_v, void* out_v, float* vad, i
       }
       const int t0 = i * P, T = (n_frames - t0) < P ? (n_frames - t0) : P;
       hipError_t e = hipStreamWaitEvent(h->d2h_stream, h->ev_done[i], 0);
-      if (e == hipSuccess) e = copy_piece(out, h->d_stage_out, t0, T, hipMemcpyDeviceToHost, h->d2h_stream);
+      if (e == hipSuccess) e = copy_piece(out, d_stage_out, t0, T, hipMemcpyDeviceToHost, h->d2h_stream);
       if (e == hipSuccess && vad)
-        e = hipMemcpyAsync(vad + (size_t)t0 * B, h->d_stage_vad + (size_t)t0 * B, (size_t)T * B * sizeof(float),
+        e = hipMemcpyAsync(vad + (size_t)t0 * B, d_stage_vad + (size_t)t0 * B, (size_t)T * B * sizeof(float),
                            hipMemcpyDeviceToHost, h->d2h_stream);
       if (e != hipSuccess) { drain_err = e; return; }
     }
@@ -759,13 +713,12 @@ int process_host_impl(crispy_rn* h, const void* in_v, void* out_v, float* vad, i
   hipError_t feed_err = hipSuccess;
   for (int i = 0; i < n_pieces && rc == CRISPY_OK && feed_err == hipSuccess; ++i) {
     const int t0 = i * P, T = (n_frames - t0) < P ? (n_frames - t0) : P;
-    feed_err = copy_piece(h->d_stage_in, in, t0, T, hipMemcpyHostToDevice, h->h2d_stream);
+    feed_err = copy_piece(d_stage_in, in, t0, T, hipMemcpyHostToDevice, h->h2d_stream);
     if (feed_err == hipSuccess) feed_err = hipEventRecord(h->ev_in[i], h->h2d_stream);
     if (feed_err == hipSuccess) feed_err = hipStreamWaitEvent(h->stream, h->ev_in[i], 0);
     if (feed_err != hipSuccess) break;
-    rc = process_device_impl(h, reinterpret_cast<const char*>(h->d_stage_in) + (size_t)t0 * stride_t * esz,
-                             reinterpret_cast<char*>(h->d_stage_out) + (size_t)t0 * stride_t * esz,
-                             vad ? h->d_stage_vad + (size_t)t0 * B : nullptr, nullptr, T, stride_t, stride_b, h->stream, s16);
+    rc = process_device_impl(h, d_stage_in + (size_t)t0 * stride_t * esz, d_stage_out + (size_t)t0 * stride_t * esz,
+                             vad ? d_stage_vad + (size_t)t0 * B : nullptr, nullptr, T, stride_t, stride_b, h->stream, s16);
     if (rc != CRISPY_OK) break;
     feed_err = hipEventRecord(h->ev_done[i], h->stream);
     if (feed_err == hipSuccess) recorded.store(i + 1, std::memory_order_release);
@@ -845,13 +798,12 @@ int crispy_rn_debug_capture(crispy_rn* h, int enable) try {
   if (!h) return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_debug_capture: NULL handle");
   HIP_TRY(hipSetDevice(h->device));
   if (enable && !h->d_dbg) {
-    HIP_TRY(hipMalloc(&h->d_dbg, (size_t)h->B * RN_DBG_FLOATS * sizeof(float)));
+    HIP_TRY(h->d_dbg.alloc((size_t)h->B * RN_DBG_FLOATS * sizeof(float)));
     HIP_TRY(hipMemset(h->d_dbg, 0, (size_t)h->B * RN_DBG_FLOATS * sizeof(float)));
     HIP_TRY(hipDeviceSynchronize());        // a NULL-stream memset is not ordered against the handle's non-blocking stream
   } else if (!enable && h->d_dbg) {
     HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipFree(h->d_dbg));
-    h->d_dbg = nullptr;
+    h->d_dbg = DevBuf<float>();
   }
   return CRISPY_OK;
 } CRISPY_CATCH_RET("crispy_rn_debug_capture")
@@ -870,7 +822,7 @@ int crispy_rn_debug_read(crispy_rn* h, int stream, float* dst, size_t n_floats) 
 
 }  // extern "C"
 
-// what rn_adapter.hip (crispy_rn_push*) uses of this file
+// what rn_io.cpp (crispy_rn_push*) uses of this file
 namespace crispy {
 int rn_zero_state(crispy_rn* h, int stream) { return zero_state(h, stream); }
 int rn_process_frames_device(crispy_rn* h, const float* d_in, float* d_out, float* d_vad, int n_frames, long stride_t, long stride_b,

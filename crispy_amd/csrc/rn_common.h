@@ -165,4 +165,81 @@ struct RnAdaptOut {
 hipError_t rn_launch_adapt_in(const RnAdaptIn& a, hipStream_t s);
 hipError_t rn_launch_adapt_out(const RnAdaptOut& a, hipStream_t s);
 
+// ---- crispy_rn_pull* (rn_playback.hip) and crispy_rn_record_* / crispy_rn_level* (rn_record.hip) ----
+struct RnRingAppend {
+  const float* src;    // [B][src_stride]: the rows the push has just written, from the first sample that is kept
+  long src_stride;
+  float* ring;         // [B][cap]
+  int cap;
+  int tail;            // where the first sample goes, < cap
+  int n;               // samples per stream, <= cap
+  int B;
+};
+
+struct RnPull {
+  const float* ring;   // [B][cap]
+  int cap;
+  int head;            // ring index of output_buf[0] at the start of the pull, < cap
+  const int* off;      // [n_frames]: samples popped since the start of the pull (< cap - 1); < 0: an underrun, the frame is 0.0
+  const float* frac;   // [n_frames]: resample_pos as f32
+  void* out;           // [B][out_stride] elements of the format
+  long out_stride;
+  unsigned n_frames;
+  unsigned n_elems;    // n_frames x channels, <= 2^27
+  unsigned channels;
+  int B;
+};
+
+constexpr int REC_FRAME = 1152;                     // the recording worker's frame_size
+
+struct RnRecApp {
+  const float* in;     // [B][in_stride]: frames of `channels` interleaved samples, from the first frame that is kept
+  long in_stride;
+  float* ring;         // [B][cap]
+  int cap;
+  int tail;            // where the first frame's sample goes, < cap
+  int n;               // frames per stream, <= cap
+  int channels;        // 1...8
+  int B;
+};
+
+struct RnRecDrain {
+  const float* mic;    // [B][cap]
+  const float* app;    // [B][cap]
+  int cap;
+  int mic_head;        // ring index of the deque's front at the start of the drain, < cap
+  int app_head;
+  const int* mic_off;  // [n_frames]: samples popped from the mic deque before this frame's 1152 (offset + 1152 <= cap)
+  const int* app_off;  // [n_frames]: the same for the app deque; < 0: fewer than 1152 were there, the frame's app samples are 0.0
+  void* out;           // [B][out_stride] elements of the format
+  long out_stride;
+  unsigned n_samples;  // n_frames x 1152
+  int B;
+};
+
+struct RnLevel {
+  const float* in;     // [B][in_stride]
+  long in_stride;
+  int n;               // samples per stream, 1...2^24
+  float* rms;          // [B]
+  int B;
+};
+
+// format: a crispy_pcm_format (include/crispy_hip.h) -- pull: f32 / i16 / u16; drain: i16 (stereo frames, L == R) / f32 (channel 0)
+hipError_t rn_launch_ring_append(const RnRingAppend& a, hipStream_t s);
+hipError_t rn_launch_pull(const RnPull& a, int format, hipStream_t s);
+hipError_t rn_launch_rec_app(const RnRecApp& a, hipStream_t s);
+hipError_t rn_launch_rec_drain(const RnRecDrain& a, int format, hipStream_t s);
+hipError_t rn_launch_level(const RnLevel& a, hipStream_t s);
+
+// A launch covers at most 2^23 workgroups (the runtime refuses 2^32 work-items per grid dimension and more): a handle of
+// several hundred thousand streams is covered in turns of streams, each turn with its own row pointers.
+// launch(b0, nb): the kernel for streams b0 ... b0 + nb - 1, `tiles` (<= RN_MAX_BLOCKS) workgroups each.
+constexpr long RN_MAX_BLOCKS = 1L << 23;
+template <class Launch>
+inline void rn_for_stream_groups(long B, long tiles, Launch launch) {
+  const long per = RN_MAX_BLOCKS / tiles;                  // streams per launch
+  for (long b0 = 0; b0 < B; b0 += per) launch(b0, (int)(B - b0 < per ? B - b0 : per));
+}
+
 }  // namespace crispy

@@ -1,40 +1,139 @@
-// rn_handle.h -- the RNNoise handle behind `crispy_rn` (include/crispy_hip.h), shared by the translation units that
-// implement its entry points: crispy_api.cpp (create / process / reset ...), rn_adapter.hip (crispy_rn_push*) and
-// rn_playback.hip (crispy_rn_pull*), rn_record.hip (crispy_rn_record_*, crispy_rn_level*).
+// rn_handle.h -- the RNNoise handle behind `crispy_rn` (include/crispy_hip.h) and the state of its three halves, shared by
+// the two translation units that implement its entry points: crispy_api.cpp (create / process / reset ...) and rn_io.cpp
+// (crispy_rn_push*, crispy_rn_pull*, crispy_rn_record_*, crispy_rn_level*).  Everything here owns what it holds: device
+// buffers are DevBuf, events EventList (api_util.h), streams Stream, the halves unique_ptr members -- deleting the handle
+// releases all of it, streams last.  The types are plain state; the logic that drives them is in the two .cpp files.
 #pragma once
 #include <cstddef>
+#include <memory>
 #include <vector>
 
 #include "../../include/crispy_hip.h"
+#include "api_util.h"
 #include "rn_common.h"
 
 namespace crispy {
-struct RnAdapter;   // rn_adapter.hip
-struct RnPlayback;  // rn_playback.hip
-struct RnRecord;    // rn_record.hip
-}
+
+// A stream the handle created: destroyed with it.
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  ~Stream() { if (s) (void)hipStreamDestroy(s); }
+  operator hipStream_t() const { return s; }
+};
+
+// A table of 32-bit words that a call works out on the host and its kernel reads: the device table, two pinned host slots
+// used in turns, and one event per slot -- the slot's copy has been read.  A slot is never rewritten before its previous
+// upload has been read, so a call does not wait for the one before it, only for the one before that.
+struct PinnedUpload {
+  // A pinned allocation, released through the deleter reserve() gives it (rn_io.cpp): this header and crispy_api.cpp, which
+  // deletes the handle, stay free of the pinned-memory API.
+  using Slot = std::unique_ptr<int, hipError_t (*)(void*)>;
+  DevBuf<int> dev;
+  Slot host[2] = {Slot(nullptr, nullptr), Slot(nullptr, nullptr)};
+  size_t host_words[2] = {0, 0};
+  EventList ev;
+  int slot = 0;
+  // Every allocation of an upload of `words` words (rn_io.cpp).  The table is scratch (DevBuf::grow); the slot is replaced only
+  // once the new one exists and the old one's upload has been read.
+  int reserve(size_t words, const char* who);
+  // fill(int* slot) writes the `words` reserved words; they are in `dev` once what is enqueued on s here has run.
+  template <class Fill>
+  int send(size_t words, hipStream_t s, Fill fill) {
+    HIP_TRY(hipEventSynchronize(ev[slot]));      // the upload that used this slot two calls ago (no-op before)
+    fill(host[slot].get());
+    HIP_TRY(hipMemcpyAsync(dev.p, host[slot].get(), words * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(ev[slot], s));
+    slot ^= 1;
+    return CRISPY_OK;
+  }
+};
+
+// A deque of the reference kept as a ring: where the front is and how many samples it holds.
+struct RingPos {
+  int head = 0;
+  int len = 0;
+};
+
+// LinearResampler::process_sample's position state (audio.rs:108-133); the same for every stream of a handle.
+struct LinResState {
+  bool has_last = false;
+  double input_pos = 0., next_pos = 0.;
+};
+
+// RnnNoiseProcessor's state around process_frame (audio.rs:202-213) for all streams of a handle, and the adapter's buffers.
+// Created with the defaults -- 48 kHz, volume 1 -- when a handle is first pushed to or configured.
+struct RnAdapter {
+  float rate = 48000.f;     // capture rate as configured; within 1 Hz of 48 kHz: no resampler
+  bool resample = false;
+  float volume = 1.f;
+  bool first = true;        // first_frame
+  LinResState rs;           // LinearResampler::has_last / input_pos / next_output_pos
+  int carry_len = 0;        // input_buf.len(), < 480 between pushes
+  int cur = 0;              // which half of the double-buffered per-stream state is current
+  DevBuf<float> carry;      // state [2][B][480]
+  DevBuf<float> last;       // state [2][B]: LinearResampler::last_sample
+  DevBuf<float> stage, y;   // scratch [B][frames * 480] each: frames into / out of the frame kernels
+  PinnedUpload pos;         // (idx[n], t[n]) of the current push
+  std::vector<int> idx;     // host scratch of one push
+  std::vector<float> t;
+  EventList ev;             // timing, four: around rn_adapt_in_kernel / rn_adapt_out_kernel
+  bool timed = false;
+};
+
+// NsState's playback side (audio.rs:208-212: output_buf, max_output_len, resample_pos, output_rate) for all streams of a
+// handle.  Created by crispy_rn_playback_configure; a handle without one has no ring and pushes as before.
+struct RnPlayback {
+  float out_rate = 48000.f;
+  float in_rate = 48000.f;   // effective input rate: 48000 with the input resampler, else the configured capture rate
+  int cap = 0;               // max_output_len = in_rate as usize
+  RingPos buf;               // output_buf
+  double pos = 0.;           // resample_pos
+  DevBuf<float> ring;        // state [B][cap]
+  PinnedUpload frames;       // (off[n], frac[n]) of the current pull
+  std::vector<int> off;      // host scratch of one pull
+  std::vector<float> frac;
+};
+
+// The recording state's two buffers (the mic ring that push_mono_to_buffers fills, the app ring of the capture handlers) for
+// all streams of a handle.  The object is created on first use; the rings exist, and the handle records, from
+// crispy_rn_record_configure on (cap > 0).
+struct RnRecord {
+  int cap = 0;
+  RingPos mic, app;
+  DevBuf<float> mic_ring;    // state [B][cap]
+  DevBuf<float> app_ring;
+  PinnedUpload offs;         // (mic_off[n], app_off[n]) of the current drain
+  std::vector<long> mic_off, app_off;     // host scratch of one drain
+};
+
+}  // namespace crispy
 
 struct crispy_rn {
   int device = 0;
   int B = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t hp_stream = nullptr;   // helper stream: the latency-bound high-pass runs beside the frame kernel
-  hipEvent_t ev_begin = nullptr;
-  std::vector<hipEvent_t> ev_hp;     // one per sub-chunk: high-pass done
+  // The streams come first: members go in reverse order, so every buffer and event is released before a stream is.
+  crispy::Stream stream;
+  crispy::Stream hp_stream;   // helper stream: the latency-bound high-pass runs beside the frame kernel
+  crispy::Stream h2d_stream, d2h_stream;   // pipelined host path: copy-in / copy-out beside the compute stream
+  crispy::EventList ev_begin;        // one
+  crispy::EventList ev_hp;           // one per sub-chunk: high-pass done
   // constants
-  crispy::RnTables* d_tab = nullptr;
-  uint32_t* d_wpack = nullptr;
+  crispy::DevBuf<crispy::RnTables> d_tab;
+  crispy::DevBuf<uint32_t> d_wpack;
   // state
-  float* d_hp_mem = nullptr;
-  float* d_synth = nullptr;       // overlap-add tails [B][480]
-  float* d_ceps = nullptr;
-  float* d_lastg = nullptr;
-  float* d_rnn = nullptr;
-  float* d_last_gain = nullptr;
-  int* d_last_period = nullptr;
-  int* d_memid = nullptr;
+  crispy::DevBuf<float> d_hp_mem;
+  crispy::DevBuf<float> d_synth;       // overlap-add tails [B][480]
+  crispy::DevBuf<float> d_ceps;
+  crispy::DevBuf<float> d_lastg;
+  crispy::DevBuf<float> d_rnn;
+  crispy::DevBuf<float> d_last_gain;
+  crispy::DevBuf<int> d_last_period;
+  crispy::DevBuf<int> d_memid;
   // workspace
-  float* d_xhp = nullptr;
+  crispy::DevBuf<float> d_xhp;
   long xhp_stride = 0;
   // Frames per high-pass launch.  A high-pass wave keeps the VALU of its SIMD ~35 % busy (nine dependent f64
   // operations per sample) and a frame-kernel launch lasts as long as its slowest wave, so a sub-chunk's high-pass as
@@ -48,50 +147,45 @@ struct crispy_rn {
   // Chosen at create time from the stream count; CRISPY_RN_WAVES=1|3 overrides (tests run both forms).
   int waves = 1;
   int hp_ahead = 0;          // > 0: the high-pass runs at most this many sub-chunks in front of the frame kernels
-  std::vector<hipEvent_t> ev_fr;   // one per sub-chunk: frame kernel done (only used with hp_ahead)
+  crispy::EventList ev_fr;   // one per sub-chunk: frame kernel done (only used with hp_ahead)
   bool hp_deep = false;      // the high-pass requests 32 samples ahead (80 registers): set where a wave of it fits beside the frame waves
   bool hp_upfront = false;   // diagnostic (CRISPY_RN_HP=upfront): every high-pass of a call segment first, on the main stream
-  float* d_dbg = nullptr;
-  // host-pointer staging
-  float* d_stage_in = nullptr;
-  float* d_stage_out = nullptr;
-  float* d_stage_vad = nullptr;
-  size_t stage_frames = 0;
-  // pipelined host path: copy-in / compute / copy-out streams and per-piece events
-  hipStream_t h2d_stream = nullptr;
-  hipStream_t d2h_stream = nullptr;
-  std::vector<hipEvent_t> ev_in, ev_done;
+  crispy::DevBuf<float> d_dbg;
+  // Host-pointer staging, one set for every entry point that takes host arrays (process, push, pull, app_push, level, drain):
+  // each of them synchronises before it returns, so a buffer is only live inside one call.  Scratch (DevBuf::grow).
+  crispy::DevBuf<unsigned char> stage_in;    // the call's input rows
+  crispy::DevBuf<unsigned char> stage_out;   // the call's output rows
+  crispy::DevBuf<float> stage_aux;           // per-frame or per-stream scalars: VAD, level
+  int stage_reserve(size_t in_bytes, size_t out_bytes, size_t aux_bytes, const char* who) {
+    if (stage_in.grow(in_bytes) != hipSuccess || stage_out.grow(out_bytes) != hipSuccess || stage_aux.grow(aux_bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return crispy::fail(CRISPY_ERR_OOM, "%s: staging allocation of %zu + %zu + %zu bytes failed", who, in_bytes, out_bytes, aux_bytes);
+    }
+    return CRISPY_OK;
+  }
+  crispy::EventList ev_in, ev_done;          // pipelined host path: per piece
   // timing
   bool timing = false;
-  std::vector<hipEvent_t> ev;  // per segment: begin, (frame_begin, frame_end) x sub-chunks, end
+  crispy::EventList ev;        // per segment: begin, (frame_begin, frame_end) x sub-chunks, end
   size_t ev_used = 0;
   std::vector<int> seg_subs;   // sub-chunks of every timed segment
-  // the capture-rate adapter (crispy_rn_push*, rn_adapter.hip): created on first use, released through its own hook
-  crispy::RnAdapter* ad = nullptr;
-  void (*ad_free)(crispy::RnAdapter*) = nullptr;
-  // the playback ring (crispy_rn_playback_* / crispy_rn_pull*, rn_playback.hip): created by crispy_rn_playback_configure
-  crispy::RnPlayback* pb = nullptr;
-  void (*pb_free)(crispy::RnPlayback*) = nullptr;
-  // the recording rings (crispy_rn_record_*, rn_record.hip): created on first use, recording from crispy_rn_record_configure on
-  crispy::RnRecord* rec = nullptr;
-  void (*rec_free)(crispy::RnRecord*) = nullptr;
+  std::unique_ptr<crispy::RnAdapter> ad;     // the capture-rate adapter (crispy_rn_push*): created on first use
+  std::unique_ptr<crispy::RnPlayback> pb;    // the playback ring (crispy_rn_pull*): created by crispy_rn_playback_configure
+  std::unique_ptr<crispy::RnRecord> rec;     // the recording rings (crispy_rn_record_*): created on first use
+
+  // Every stream the handle created is drained before anything it holds goes.
+  ~crispy_rn() {
+    (void)hipSetDevice(device);
+    for (hipStream_t s : {stream.s, hp_stream.s, h2d_stream.s, d2h_stream.s})
+      if (s) (void)hipStreamSynchronize(s);
+  }
 };
 
 namespace crispy {
-// crispy_api.cpp: zero the DenoiseState of one stream (>= 0) or all (-1) on the handle's stream; enqueue n_frames frames of
-// every stream with explicit element strides of (frame, stream) -- the path of crispy_rn_process_device
+// crispy_api.cpp, what rn_io.cpp uses of it: zero the DenoiseState of one stream (>= 0) or all (-1) on the handle's stream;
+// enqueue n_frames frames of every stream with explicit element strides of (frame, stream) -- the path of
+// crispy_rn_process_device
 int rn_zero_state(crispy_rn* h, int stream);
 int rn_process_frames_device(crispy_rn* h, const float* d_in, float* d_out, float* d_vad, int n_frames, long stride_t, long stride_b,
                              hipStream_t s);
-// rn_playback.hip, both no-ops on a handle without playback configured: a new processor at effective input rate in_rate
-// (empty ring of in_rate samples, resample_pos 0; the output rate stays); the n samples per stream a push has just written to
-// d_rows [B][stride] appended to the ring on s
-int rn_playback_adapter_configured(crispy_rn* h, float in_rate, const char* who);
-int rn_playback_append(crispy_rn* h, const float* d_rows, long stride, long n, hipStream_t s);
-// rn_playback.hip: its append kernel for any ring [B][cap] -- n <= cap samples per stream from src [B][src_stride] to ring
-// indices tail, tail + 1, ... modulo cap
-hipError_t rn_launch_ring_append(const float* src, long src_stride, float* ring, int cap, int tail, int n, int B, hipStream_t s);
-// rn_record.hip, a no-op on a handle that does not record: the n samples per stream a push has just written to d_rows
-// [B][stride] appended to the mic ring on s
-int rn_record_append_mic(crispy_rn* h, const float* d_rows, long stride, long n, hipStream_t s);
 }  // namespace crispy

@@ -9,49 +9,19 @@
 // same for all of them and do not depend on the samples.  The host runs the reference's f64 recurrence once per pull, frame by
 // frame, and uploads one (offset, fraction) pair per output frame.
 // Both kernels are streaming passes: lanes run along the samples of one stream, a workgroup covers consecutive ones.
+// Kernels and their launchers (declared in rn_common.h); the entry points that drive them are rn_io.cpp.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstdint>
-#include <cstring>
-#include <memory>
-#include <new>
-#include <vector>
 
-#include "api_util.h"
+#include "../../include/crispy_hip.h"
 #include "rn_common.h"
-#include "rn_handle.h"
 
 namespace crispy {
 namespace {
 
 constexpr int PB_THREADS = 256;
 constexpr int PB_COPY_TILE = PB_THREADS * 4;       // samples per workgroup of the append
-constexpr long PB_MAX_BLOCKS = 1L << 23;           // per launch: a handle of several hundred thousand streams goes in turns
-
-struct RnRingAppend {
-  const float* src;    // [B][src_stride]: the rows the push has just written, from the first sample that is kept
-  long src_stride;
-  float* ring;         // [B][cap]
-  int cap;
-  int tail;            // where the first sample goes, < cap
-  int n;               // samples per stream, <= cap
-  int B;
-};
-
-struct RnPull {
-  const float* ring;   // [B][cap]
-  int cap;
-  int head;            // ring index of output_buf[0] at the start of the pull, < cap
-  const int* off;      // [n_frames]: samples popped since the start of the pull (< cap - 1); < 0: an underrun, the frame is 0.0
-  const float* frac;   // [n_frames]: resample_pos as f32
-  void* out;           // [B][out_stride] elements of the format
-  long out_stride;
-  unsigned n_frames;
-  unsigned n_elems;    // n_frames x channels, <= 2^27
-  unsigned channels;
-  int B;
-};
 
 __host__ __device__ inline long pb_tiles(long n, long tile) { return n > 0 ? (n + tile - 1) / tile : 1; }
 
@@ -175,38 +145,41 @@ __global__ __launch_bounds__(PB_THREADS) void rn_pull_kernel(RnPull a) {
   }
 }
 
-hipError_t launch_append(const RnRingAppend& a, hipStream_t s) {
+}  // namespace
+
+// tiles <= 47 for a cap of one second, <= 2^18 for a recording ring
+hipError_t rn_launch_ring_append(const RnRingAppend& a, hipStream_t s) {
   const long tiles = pb_tiles(a.n, PB_COPY_TILE);
-  const long per = PB_MAX_BLOCKS / tiles;              // streams per launch (tiles <= 47 for a cap of one second, <= 2^18 for a recording ring)
-  for (long b0 = 0; b0 < a.B; b0 += per) {
+  rn_for_stream_groups(a.B, tiles, [&](long b0, int nb) {
     RnRingAppend c = a;
-    c.B = (int)(a.B - b0 < per ? a.B - b0 : per);
+    c.B = nb;
     c.src += b0 * a.src_stride;
     c.ring += b0 * a.cap;
     hipLaunchKernelGGL(rn_ring_append_kernel, dim3((unsigned)(c.B * tiles)), dim3(PB_THREADS), 0, s, c);
-  }
+  });
   return hipGetLastError();
 }
 
+namespace {
 template <int FMT>
 hipError_t launch_pull_fmt(const RnPull& a, hipStream_t s) {
   using T = typename Pcm<FMT>::T;
   const long tiles = pb_tiles(a.n_elems, PB_THREADS * (16 / (long)sizeof(T)));       // <= 2^17
-  const long per = PB_MAX_BLOCKS / tiles;
   const bool vec = (((uintptr_t)a.out | (uintptr_t)(a.out_stride * (long)sizeof(T))) & 15) == 0;
-  for (long b0 = 0; b0 < a.B; b0 += per) {
+  rn_for_stream_groups(a.B, tiles, [&](long b0, int nb) {
     RnPull c = a;
-    c.B = (int)(a.B - b0 < per ? a.B - b0 : per);
+    c.B = nb;
     c.ring += b0 * a.cap;
     c.out = reinterpret_cast<T*>(a.out) + b0 * a.out_stride;
     const dim3 grid((unsigned)(c.B * tiles));
     if (vec) hipLaunchKernelGGL((rn_pull_kernel<FMT, true>), grid, dim3(PB_THREADS), 0, s, c);
     else hipLaunchKernelGGL((rn_pull_kernel<FMT, false>), grid, dim3(PB_THREADS), 0, s, c);
-  }
+  });
   return hipGetLastError();
 }
+}  // namespace
 
-hipError_t launch_pull(const RnPull& a, int format, hipStream_t s) {
+hipError_t rn_launch_pull(const RnPull& a, int format, hipStream_t s) {
   switch (format) {
     case CRISPY_PCM_F32: return launch_pull_fmt<CRISPY_PCM_F32>(a, s);
     case CRISPY_PCM_I16: return launch_pull_fmt<CRISPY_PCM_I16>(a, s);
@@ -214,271 +187,4 @@ hipError_t launch_pull(const RnPull& a, int format, hipStream_t s) {
   }
 }
 
-constexpr long kPullMaxFrames = 1L << 24;     // output frames per pull
-inline size_t pcm_bytes(int format) { return format == CRISPY_PCM_F32 ? 4 : 2; }
-
-}  // namespace
-
-// NsState's playback side (audio.rs:208-212: output_buf, max_output_len, resample_pos, output_rate) for all streams of a
-// handle.  Created by crispy_rn_playback_configure; a handle without one has no ring and pushes as before.
-struct RnPlayback {
-  float out_rate = 48000.f;
-  float in_rate = 48000.f;   // effective input rate: 48000 with the input resampler, else the configured capture rate
-  int cap = 0;               // max_output_len = in_rate as usize
-  int head = 0;              // ring index of output_buf[0]
-  int len = 0;               // output_buf.len()
-  double pos = 0.;           // resample_pos
-  DevBuf<float> ring;        // [B][cap]
-  DevBuf<int> d_pos;         // (off[n], frac[n]) of the current pull
-  int* h_pos[2] = {nullptr, nullptr};     // pinned upload slots, used in turns; ev_pos: the slot's copy has been read
-  long h_pos_cap[2] = {0, 0};
-  hipEvent_t ev_pos[2] = {nullptr, nullptr};
-  int slot = 0;
-  std::vector<int> off;      // host scratch of one pull
-  std::vector<float> frac;
-  DevBuf<unsigned char> d_hout;   // crispy_rn_pull: device copy of the host array
-};
-
-namespace {
-
-// crispy_rn::pb_free (the caller has made the handle's device current and drained its stream)
-void playback_free(RnPlayback* p) {
-  for (int* q : p->h_pos)
-    if (q) (void)hipHostFree(q);
-  for (hipEvent_t e : p->ev_pos)
-    if (e) (void)hipEventDestroy(e);
-  delete p;
-}
-
-// A fresh output_buf of one second at in_rate and resample_pos = 0.  The ring is replaced only when its size changes, the new
-// one allocated before the old one goes: a failure leaves the handle as it was.
-int playback_fresh_ring(crispy_rn* h, RnPlayback* p, float in_rate, const char* who) {
-  const int cap = (int)(size_t)in_rate;      // `as usize`: 47999 or 48000 (a rate a whole hertz off 48 kHz is resampled to it)
-  if (cap < 2) return fail(CRISPY_ERR_INVALID_ARG, "%s: a ring of %d samples", who, cap);
-  if (cap != p->cap || !p->ring.p) {
-    DevBuf<float> fresh;
-    const size_t bytes = (size_t)h->B * cap * sizeof(float);
-    if (fresh.alloc(bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(CRISPY_ERR_OOM, "%s: ring allocation of %zu bytes failed", who, bytes);
-    }
-    p->ring = std::move(fresh);      // (the old one is freed with `fresh`; hipFree waits for the work that still reads it)
-  }
-  p->in_rate = in_rate;
-  p->cap = cap;
-  p->head = 0;
-  p->len = 0;
-  p->pos = 0.;
-  return CRISPY_OK;
-}
-
-// The arguments every pull checks, before anything is touched.
-int check_pull(const crispy_rn* h, long n_frames, int channels, int format, const void* out, long out_stride, const char* who) {
-  if (!h->pb) return fail(CRISPY_ERR_INVALID_ARG, "%s: playback not configured (crispy_rn_playback_configure)", who);
-  if (n_frames < 0) return fail(CRISPY_ERR_INVALID_ARG, "%s: n_frames < 0", who);
-  if (n_frames > kPullMaxFrames) return fail(CRISPY_ERR_INVALID_ARG, "%s: n_frames %ld above the limit of %ld frames per pull", who, n_frames, kPullMaxFrames);
-  if (channels < 1 || channels > 8) return fail(CRISPY_ERR_INVALID_ARG, "%s: channels %d outside 1...8", who, channels);
-  if (format != CRISPY_PCM_F32 && format != CRISPY_PCM_I16 && format != CRISPY_PCM_U16)
-    return fail(CRISPY_ERR_INVALID_ARG, "%s: unknown format %d", who, format);
-  if (n_frames == 0) return CRISPY_OK;
-  if (!out) return fail(CRISPY_ERR_INVALID_ARG, "%s: NULL output pointer", who);
-  if (out_stride < n_frames * channels)
-    return fail(CRISPY_ERR_INVALID_ARG, "%s: out_stride %ld shorter than the %ld elements of this pull", who, out_stride, n_frames * channels);
-  return CRISPY_OK;
-}
-
-// Arguments checked (check_pull), n_frames > 0, the handle's device current.
-int pull_device_impl(crispy_rn* h, long n_frames, int channels, int format, void* d_out, long out_stride, long* n_live, hipStream_t s,
-                     const char* who) {
-  RnPlayback* p = h->pb;
-  // next_sample (audio.rs:297-314), n_frames times, on copies of the state: the reference's own recurrence, never a closed form
-  const double step = (double)p->in_rate / (double)p->out_rate;
-  long len = p->len, pops = 0, live = 0;
-  double pos = p->pos;
-  p->off.resize((size_t)n_frames);
-  p->frac.resize((size_t)n_frames);
-  for (long f = 0; f < n_frames; ++f) {
-    p->off[f] = -1;
-    p->frac[f] = 0.f;
-    if (len < 2) continue;
-    while (pos >= 1.0 && len >= 2) {
-      ++pops;
-      --len;
-      pos -= 1.0;
-    }
-    if (len < 2) continue;         // ran dry while popping: 0.0, the pops and the decrements stay
-    p->off[f] = (int)pops;
-    p->frac[f] = (float)pos;
-    pos += step;
-    ++live;
-  }
-  // every allocation first: a failure from here on returns with the handle's state as it was
-  const size_t words = (size_t)2 * n_frames;
-  if (p->d_pos.grow(words * sizeof(int)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(CRISPY_ERR_OOM, "%s: position buffer of %zu bytes failed", who, words * sizeof(int));
-  }
-  const int slot = p->slot;
-  if (p->h_pos_cap[slot] < (long)words) {
-    int* fresh = nullptr;
-    if (hipHostMalloc(&fresh, words * sizeof(int), hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(CRISPY_ERR_OOM, "%s: pinned allocation of %zu bytes failed", who, words * sizeof(int));
-    }
-    if (p->ev_pos[slot]) HIP_TRY(hipEventSynchronize(p->ev_pos[slot]));
-    if (p->h_pos[slot]) (void)hipHostFree(p->h_pos[slot]);
-    p->h_pos[slot] = fresh;
-    p->h_pos_cap[slot] = (long)words;
-  }
-  if (!p->ev_pos[slot]) HIP_TRY(hipEventCreateWithFlags(&p->ev_pos[slot], hipEventDisableTiming));
-
-  // ---- enqueue ----
-  HIP_TRY(hipEventSynchronize(p->ev_pos[slot]));      // the upload that used this slot two pulls ago (no-op before)
-  std::memcpy(p->h_pos[slot], p->off.data(), (size_t)n_frames * sizeof(int));
-  std::memcpy(p->h_pos[slot] + n_frames, p->frac.data(), (size_t)n_frames * sizeof(float));
-  HIP_TRY(hipMemcpyAsync(p->d_pos.p, p->h_pos[slot], words * sizeof(int), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipEventRecord(p->ev_pos[slot], s));
-  p->slot = slot ^ 1;
-  RnPull a{};
-  a.ring = p->ring.p;
-  a.cap = p->cap;
-  a.head = p->head;
-  a.off = p->d_pos.p;
-  a.frac = reinterpret_cast<const float*>(p->d_pos.p + n_frames);
-  a.out = d_out;
-  a.out_stride = out_stride;
-  a.n_frames = (unsigned)n_frames;
-  a.n_elems = (unsigned)(n_frames * channels);
-  a.channels = (unsigned)channels;
-  a.B = h->B;
-  HIP_TRY(launch_pull(a, format, s));
-  p->head = (int)((p->head + pops) % p->cap);
-  p->len = (int)len;
-  p->pos = pos;
-  if (n_live) *n_live = live;
-  return CRISPY_OK;
-}
-
-}  // namespace
-
-// what rn_record.hip uses of this file (rn_handle.h): the append kernel on a ring of its own
-hipError_t rn_launch_ring_append(const float* src, long src_stride, float* ring, int cap, int tail, int n, int B, hipStream_t s) {
-  RnRingAppend a{};
-  a.src = src;
-  a.src_stride = src_stride;
-  a.ring = ring;
-  a.cap = cap;
-  a.tail = tail;
-  a.n = n;
-  a.B = B;
-  return launch_append(a, s);
-}
-
-// what rn_adapter.hip uses of this file (rn_handle.h)
-int rn_playback_adapter_configured(crispy_rn* h, float in_rate, const char* who) {
-  return h->pb ? playback_fresh_ring(h, h->pb, in_rate, who) : CRISPY_OK;
-}
-
-int rn_playback_append(crispy_rn* h, const float* d_rows, long stride, long n, hipStream_t s) {
-  RnPlayback* p = h->pb;
-  if (!p || n <= 0) return CRISPY_OK;
-  RnRingAppend a{};
-  a.src_stride = stride;
-  a.ring = p->ring.p;
-  a.cap = p->cap;
-  a.B = h->B;
-  int head = p->head, len = p->len;
-  if (n >= p->cap) {                 // everything that was there is evicted, and the front of this push with it
-    a.src = d_rows + (n - p->cap);
-    a.n = p->cap;
-    a.tail = 0;
-    head = 0;
-    len = p->cap;
-  } else {
-    a.src = d_rows;
-    a.n = (int)n;
-    a.tail = (head + len) % p->cap;
-    const long over = len + n - p->cap;      // push_sample pops the oldest sample for each one that does not fit
-    if (over > 0) {
-      head = (int)((head + over) % p->cap);
-      len = p->cap;
-    } else {
-      len += (int)n;
-    }
-  }
-  HIP_TRY(launch_append(a, s));
-  p->head = head;
-  p->len = len;
-  return CRISPY_OK;
-}
-
 }  // namespace crispy
-
-using namespace crispy;
-
-extern "C" {
-
-int crispy_rn_playback_configure(crispy_rn* h, float output_rate) try {
-  const char* who = "crispy_rn_playback_configure";
-  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "%s: NULL handle", who);
-  if (!(output_rate > 0.f) || !std::isfinite(output_rate))
-    return fail(CRISPY_ERR_INVALID_ARG, "%s: output_rate must be a positive number of Hz", who);
-  HIP_TRY(hipSetDevice(h->device));
-  float in_rate = 48000.f;
-  int rc = crispy_rn_adapter_produced_rate_hz(h, &in_rate);
-  if (rc != CRISPY_OK) return rc;
-  if (!h->pb) {
-    std::unique_ptr<RnPlayback> fresh(new RnPlayback());      // (std::bad_alloc: the guard makes it CRISPY_ERR_OOM)
-    rc = playback_fresh_ring(h, fresh.get(), in_rate, who);
-    if (rc != CRISPY_OK) return rc;
-    h->pb = fresh.release();
-    h->pb_free = playback_free;
-  } else {
-    rc = playback_fresh_ring(h, h->pb, in_rate, who);
-    if (rc != CRISPY_OK) return rc;
-  }
-  h->pb->out_rate = output_rate;
-  return CRISPY_OK;
-} CRISPY_CATCH_RET("crispy_rn_playback_configure")
-
-long crispy_rn_playback_buffered(const crispy_rn* h) try {
-  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_playback_buffered: NULL handle");
-  return h->pb ? h->pb->len : 0;
-} CRISPY_CATCH_RET("crispy_rn_playback_buffered")
-
-int crispy_rn_pull_device(crispy_rn* h, long n_frames, int channels, int format, void* d_out, long out_stride, long* n_live,
-                          void* hip_stream) try {
-  const char* who = "crispy_rn_pull_device";
-  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "%s: NULL handle", who);
-  const int rc = check_pull(h, n_frames, channels, format, d_out, out_stride, who);
-  if (rc != CRISPY_OK) return rc;
-  if (n_live) *n_live = 0;
-  if (n_frames == 0) return CRISPY_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  return pull_device_impl(h, n_frames, channels, format, d_out, out_stride, n_live, hip_stream ? (hipStream_t)hip_stream : h->stream, who);
-} CRISPY_CATCH_RET("crispy_rn_pull_device")
-
-int crispy_rn_pull(crispy_rn* h, long n_frames, int channels, int format, void* out, long out_stride, long* n_live) try {
-  const char* who = "crispy_rn_pull";
-  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "%s: NULL handle", who);
-  int rc = check_pull(h, n_frames, channels, format, out, out_stride, who);
-  if (rc != CRISPY_OK) return rc;
-  if (n_live) *n_live = 0;
-  if (n_frames == 0) return CRISPY_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  RnPlayback* p = h->pb;
-  const size_t row = (size_t)n_frames * channels * pcm_bytes(format);       // a multiple of 16 when it matters: rows stay aligned
-  const size_t pitch = (row + 15) & ~(size_t)15;
-  if (p->d_hout.grow((size_t)h->B * pitch) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(CRISPY_ERR_OOM, "%s: staging allocation of %zu bytes failed", who, (size_t)h->B * pitch);
-  }
-  hipStream_t s = h->stream;
-  rc = pull_device_impl(h, n_frames, channels, format, p->d_hout.p, (long)(pitch / pcm_bytes(format)), n_live, s, who);
-  if (rc != CRISPY_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride * pcm_bytes(format), p->d_hout.p, pitch, row, (size_t)h->B, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return CRISPY_OK;
-} CRISPY_CATCH_RET("crispy_rn_pull")
-
-}  // extern "C"

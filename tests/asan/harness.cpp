@@ -3,7 +3,7 @@
 // HIP stand-in of tests/asan/hip/hip_runtime.h; the kernel launchers they call are the no-ops below.  What runs for real:
 // the GGML reader (header, vocabulary, tensor table, f16 / quantised payloads, the resident loader's block bookkeeping),
 // finalize (row fusing, LayerNorm folding, conv reordering -- host loops over "device" buffers that ASan watches), the
-// rnnoise-nu text parser, whisper_full's decision logic (replay_decoder / score_decoder / window_segments / the variate
+// rnnoise-nu text parser, the RNNoise handle's push / pull / record host logic (rn_io.cpp), whisper_full's decision logic (replay_decoder / score_decoder / window_segments / the variate
 // generator), the language table.  Built and driven by tests/test_host_sanitizers.py; never linked into the product.
 //
 //   harness load <model.bin> [resident]                      one load + set_precision(1) + free; prints the status
@@ -15,6 +15,11 @@
 //                                                            with the k-th allocation failing: every run must return
 //                                                            CRISPY_ERR_OOM and leak nothing; exit status 0 if they all do
 //   harness rnnoise <model.txt>                              crispy_rn_weights_from_file; prints the status
+//   harness rn-oom-sweep                                     a handle of 3 streams through process, push, pull, app_push, level,
+//                                                            drain (host-pointer forms) and a timed push_device, once cleanly -- N
+//                                                            allocations -- and once per k = 1 .. N with the k-th one failing: the
+//                                                            step that meets it must return CRISPY_ERR_OOM, succeed when repeated,
+//                                                            and every length the API reports at the end must be the clean run's
 //   harness fuzz-rnnoise <model.txt> <n> <seed>
 //   harness decide                                           decision-logic cases on stdin, results on stdout (see below)
 #include <cinttypes>
@@ -30,6 +35,7 @@
 #include "../../crispy_amd/csrc/api_util.cpp"
 #include "../../crispy_amd/csrc/asr_api.cpp"
 #include "../../crispy_amd/csrc/crispy_api.cpp"
+#include "../../crispy_amd/csrc/rn_io.cpp"
 #include "../../crispy_amd/csrc/whisper_api.cpp"
 #include "../../crispy_amd/csrc/ggml_load.cpp"
 #include "../../crispy_amd/csrc/decode_steps.cpp"
@@ -79,6 +85,13 @@ hipError_t rn_launch_frames(const RnArgs&, hipStream_t, int) { return hipSuccess
 hipError_t rn_launch_highpass(const RnArgs&, hipStream_t, bool) { return hipSuccess; }
 hipError_t rn_launch_roll_history(const RnArgs&, hipStream_t) { return hipSuccess; }
 hipError_t rn_launch_tansig(const RnTables*, const float*, float*, long, int, hipStream_t) { return hipSuccess; }
+hipError_t rn_launch_adapt_in(const RnAdaptIn&, hipStream_t) { return hipSuccess; }
+hipError_t rn_launch_adapt_out(const RnAdaptOut&, hipStream_t) { return hipSuccess; }
+hipError_t rn_launch_ring_append(const RnRingAppend&, hipStream_t) { return hipSuccess; }
+hipError_t rn_launch_pull(const RnPull&, int, hipStream_t) { return hipSuccess; }
+hipError_t rn_launch_rec_app(const RnRecApp&, hipStream_t) { return hipSuccess; }
+hipError_t rn_launch_rec_drain(const RnRecDrain&, int, hipStream_t) { return hipSuccess; }
+hipError_t rn_launch_level(const RnLevel&, hipStream_t) { return hipSuccess; }
 }  // namespace crispy
 
 namespace {
@@ -147,6 +160,88 @@ int oom_sweep(const char* path, bool resident) {
   shim_malloc_fail_at = 0;
   printf("{\"allocations\": %ld, \"oom\": %ld, \"other\": [%s]}\n", n, oom, other.c_str());
   return oom == n ? 0 : 1;
+}
+
+// rn-oom-sweep: one run of the scenario.  fail_at > 0: the fail_at-th allocation fails; the step that returns CRISPY_ERR_OOM
+// is counted and repeated once with failing off.  Any other status, and a second failure, goes to `other` as [k, status].
+// lengths: every length the API reports, in call order.
+struct RnSweepRun {
+  long allocations = 0, oom = 0;
+  std::vector<long> lengths;
+  std::string other;
+};
+RnSweepRun rn_scenario(long fail_at) {
+  RnSweepRun run;
+  shim_malloc_calls = 0;
+  shim_malloc_fail_at = fail_at;
+  auto step = [&](auto&& call) {
+    int rc = call();
+    if (rc == CRISPY_ERR_OOM && shim_malloc_fail_at > 0 && shim_malloc_calls >= shim_malloc_fail_at) {
+      ++run.oom;
+      shim_malloc_fail_at = 0;
+      rc = call();
+    }
+    if (rc != CRISPY_OK) run.other += (run.other.empty() ? "[" : ", [") + std::to_string(fail_at) + ", " + std::to_string(rc) + "]";
+    return rc == CRISPY_OK;
+  };
+  const int B = 3;
+  std::vector<int8_t> w(CRISPY_RN_WEIGHT_BYTES, 1);
+  crispy_rn* h = nullptr;
+  if (!step([&] { return crispy_rn_create(w.data(), w.size(), B, 0, &h); })) return run;
+  std::vector<float> in((size_t)B * 1600, 0.25f), out((size_t)B * 3 * 480), vad((size_t)B * 8), rms(B);
+  std::vector<int16_t> pcm((size_t)B * 700 * 2);
+  std::vector<float> app((size_t)B * 1200 * 2, 0.125f);
+  std::vector<int16_t> wav((size_t)B * 4 * 2 * 1152);
+  long n = 0, mic = 0, apl = 0;
+  for (int frames : {1, 3}) step([&] { return crispy_rn_process(h, in.data(), out.data(), vad.data(), frames, CRISPY_RN_LAYOUT_TBF); });
+  step([&] { return crispy_rn_debug_capture(h, 1); });
+  step([&] { return crispy_rn_adapter_configure(h, 44100.f, 0.8f); });
+  step([&] { return crispy_rn_playback_configure(h, 32000.f); });
+  step([&] { return crispy_rn_record_configure(h, 2304); });
+  for (long n_in : {500L, 1500L}) {
+    step([&] { return crispy_rn_push(h, in.data(), n_in, n_in, out.data(), 3 * 480, vad.data(), &n); });
+    run.lengths.push_back(n);
+  }
+  for (long frames : {64L, 700L}) {
+    step([&] { return crispy_rn_pull(h, frames, 2, CRISPY_PCM_I16, pcm.data(), frames * 2, &n); });
+    run.lengths.push_back(n);
+  }
+  step([&] { return crispy_rn_record_app_push(h, app.data(), 1200 * 2, 1200, 2); });
+  step([&] { return crispy_rn_level(h, in.data(), 480, 480, rms.data()); });
+  step([&] { return crispy_rn_record_drain(h, 4, CRISPY_PCM_I16, wav.data(), 4 * 2 * 1152, &n); });
+  run.lengths.push_back(n);
+  step([&] { return crispy_rn_set_timing(h, 1); });
+  step([&] { return crispy_rn_push_device(h, in.data(), 500, 500, out.data(), 3 * 480, nullptr, 0, nullptr, &n, nullptr); });
+  run.lengths.push_back(n);
+  run.lengths.push_back(crispy_rn_push_out_len(h, 1000));
+  run.lengths.push_back(crispy_rn_playback_buffered(h));
+  (void)crispy_rn_record_buffered(h, &mic, &apl);
+  run.lengths.push_back(mic);
+  run.lengths.push_back(apl);
+  run.lengths.push_back(crispy_rn_record_frames_ready(h));
+  crispy_rn_destroy(h);
+  run.allocations = shim_malloc_calls;
+  shim_malloc_fail_at = 0;
+  return run;
+}
+
+int rn_oom_sweep() {
+  const RnSweepRun clean = rn_scenario(0);
+  if (!clean.other.empty()) { printf("{\"fatal\": \"the clean run returned %s: %s\"}\n", clean.other.c_str(), crispy_last_error()); return 2; }
+  long oom = 0;
+  std::string other, differ;
+  for (long k = 1; k <= clean.allocations; ++k) {
+    const RnSweepRun run = rn_scenario(k);
+    oom += run.oom;
+    if (!run.other.empty()) other += (other.empty() ? "" : ", ") + run.other;
+    if (run.oom != 1 && run.other.empty()) other += (other.empty() ? "[" : ", [") + std::to_string(k) + ", " + std::to_string(CRISPY_OK) + "]";
+    if (run.lengths != clean.lengths) differ += (differ.empty() ? "" : ", ") + std::to_string(k);
+  }
+  printf("{\"allocations\": %ld, \"oom\": %ld, \"other\": [%s], \"lengths_differ\": [%s], \"lengths\": [", clean.allocations, oom, other.c_str(),
+         differ.c_str());
+  for (size_t i = 0; i < clean.lengths.size(); ++i) printf("%s%ld", i ? ", " : "", clean.lengths[i]);
+  printf("]}\n");
+  return oom == clean.allocations && other.empty() && differ.empty() ? 0 : 1;
 }
 
 std::vector<long> read_offsets(const char* path) {
@@ -345,6 +440,7 @@ int main(int argc, char** argv) {
     return fuzz_ggml(argv[2], atoi(argv[3]), (unsigned)atoi(argv[4]), argv[5], argc > 6 && !strcmp(argv[6], "resident"));
   if (argc >= 3 && !strcmp(argv[1], "oom-sweep")) return oom_sweep(argv[2], argc > 3 && !strcmp(argv[3], "resident"));
   if (argc >= 3 && !strcmp(argv[1], "rnnoise")) return rnnoise_once(argv[2], true) == CRISPY_OK ? 0 : 1;
+  if (argc >= 2 && !strcmp(argv[1], "rn-oom-sweep")) return rn_oom_sweep();
   if (argc >= 5 && !strcmp(argv[1], "fuzz-rnnoise")) return fuzz_rnnoise(argv[2], atoi(argv[3]), (unsigned)atoi(argv[4]));
   if (argc >= 2 && !strcmp(argv[1], "decide")) return decide();
   fprintf(stderr, "usage: see the head of tests/asan/harness.cpp\n");

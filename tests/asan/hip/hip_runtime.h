@@ -28,7 +28,7 @@ typedef struct shim_graph_exec* hipGraphExec_t;
 typedef enum hipMemcpyKind { hipMemcpyHostToHost = 0, hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3, hipMemcpyDefault = 4 } hipMemcpyKind;
 typedef enum hipStreamCaptureMode { hipStreamCaptureModeGlobal = 0, hipStreamCaptureModeThreadLocal = 1, hipStreamCaptureModeRelaxed = 2 } hipStreamCaptureMode;
 typedef enum hipDeviceAttribute_t { hipDeviceAttributeMultiprocessorCount = 63 } hipDeviceAttribute_t;
-enum { hipStreamNonBlocking = 1, hipEventDisableTiming = 2, hipHostRegisterDefault = 0 };
+enum { hipStreamNonBlocking = 1, hipEventDisableTiming = 2, hipHostRegisterDefault = 0, hipHostMallocDefault = 0 };
 struct hipDeviceProp_t { char name[256]; char gcnArchName[256]; int multiProcessorCount; size_t totalGlobalMem; };
 struct float2 { float x, y; };
 struct float4 { float x, y, z, w; };
@@ -37,8 +37,8 @@ struct dim3 { unsigned x, y, z; dim3(unsigned a = 1, unsigned b = 1, unsigned c 
 // a cap on one allocation: a corrupt header that asks for terabytes must come back as an out-of-memory status, not take the box down
 static const size_t SHIM_MAX_ALLOC = (size_t)3 << 30;
 
-// the allocation-failure sweep of tests/asan/harness.cpp (oom-sweep): hipMalloc calls so far, and the call (counted from 1)
-// that reports out of memory instead of allocating; 0: none
+// the allocation-failure sweeps of tests/asan/harness.cpp (oom-sweep, rn-oom-sweep): hipMalloc and hipHostMalloc calls so far,
+// and the call (counted from 1) that reports out of memory instead of allocating; 0: none
 inline long shim_malloc_calls = 0;
 inline long shim_malloc_fail_at = 0;
 
@@ -48,6 +48,9 @@ template <class T> static inline hipError_t hipMalloc(T** p, size_t n) {
   return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 static inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
+// pinned host memory is host memory; counted with the device allocations
+template <class T> static inline hipError_t hipHostMalloc(T** p, size_t n, unsigned) { return hipMalloc(p, n); }
+static inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t = nullptr) { if (n) memmove(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpy2DAsync(void* d, size_t dp, const void* s, size_t sp, size_t w, size_t h, hipMemcpyKind, hipStream_t = nullptr) {

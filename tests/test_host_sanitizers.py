@@ -2,7 +2,8 @@
 next #6).  The library parses untrusted model files -- whisper.cpp GGML containers, rnnoise-nu text models -- inside a host
 built with `panic = "abort"` (src-tauri/Cargo.toml:10-20: there is nothing to catch a crash), and the corrupt-file tests of
 tests/test_boundary_robustness.py check status codes, not memory safety.  Here the product's own translation units
-(api_util.cpp, asr_api.cpp, crispy_api.cpp, whisper_api.cpp) are compiled unmodified by tests/asan/harness.cpp against a
+(api_util.cpp, asr_api.cpp, crispy_api.cpp, rn_io.cpp, whisper_api.cpp, ggml_load.cpp, decode_steps.cpp, whisper_full.cpp)
+are compiled unmodified by tests/asan/harness.cpp against a
 host-memory stand-in for the HIP runtime (tests/asan/hip/hip_runtime.h: "device" buffers are malloc'd, so every copy the
 loaders make is bounds-checked; kernel launchers are no-ops), with -fsanitize=address,undefined, and fed:
 
@@ -13,6 +14,9 @@ loaders make is bounds-checked; kernel launchers are no-ops), with -fsanitize=ad
   * an allocation-failure sweep: the load, set_precision(1), the calls that grow the encoder / log-mel / resampler workspaces,
     once per device allocation with that allocation failing -- every run an out-of-memory status, nothing leaked or freed twice;
   * >= 2 000 seeded mutations of a valid rnnoise-nu text model;
+  * an allocation-failure sweep of the RNNoise handle's live path (rn_io.cpp: push, pull, record, level, with process and a
+    timed push_device around them): every failing allocation an out-of-memory status from the step that met it, that step
+    good when repeated, and every length the API reports afterwards the one of a run without failures;
   * whisper_full's decision logic -- replay_decoder / score_decoder / window_segments and the std::mt19937 variate -- on
     sequences produced by the oracle's decode_temperature over scripted decoders, compared field by field (a CPU parity test
     of the C++ the GPU tests otherwise only reach through a device).
@@ -186,6 +190,29 @@ def test_seeded_mutations_of_an_rnnoise_nu_model(harness, tmp_path):
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert out["mutations"] == N_MUT and out["rejected"] >= N_MUT // 2 and out["parsed"] >= 1, out
     print(out)
+
+
+def test_every_failing_allocation_of_the_rnnoise_live_path_leaves_the_handle_as_it_was(harness):
+    """`harness rn-oom-sweep`: a handle of 3 streams -- create, process of 1 and 3 frames, debug capture, a 44.1 kHz adapter,
+    32 kHz playback, a recording ring of 2304, push of 500 and 1500 samples with VAD, pull of 64 and 700 two-channel i16 frames,
+    app_push of 1200 x 2, level of 480, drain, a timed push_device, destroy -- run once cleanly (N device and pinned allocations)
+    and N times with the k-th one failing.  In every run the step that meets the failure returns CRISPY_ERR_OOM and nothing else,
+    returns CRISPY_OK when repeated, and at the end each push's n_out, each pull's n_live, the drain's n_frames,
+    push_out_len(1000), playback_buffered, record_buffered and frames_ready equal the clean run's: "every allocation first: a
+    failure returns with the handle's state as it was" (rn_io.cpp), checked.  No sanitizer report (_run asserts that).
+
+    N is at least the number of distinct buffers the scenario cannot do without, 30: crispy_rn_create 11 (tables, weights,
+    eight state arrays, the high-pass workspace); the staging set 3; debug capture 1; the adapter's carry and last-sample
+    state 2 and its two workspaces 2; the push's position table and both pinned slots (two resampled pushes, one slot each)
+    3; the playback ring 1; the pull's table and both slots 3; the two recording rings 2; the drain's table and one slot
+    (one drain) 2.  What a clean run allocates beyond that is regrowth: staging and workspaces for the larger second calls."""
+    r = _run(harness, ["rn-oom-sweep"])
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    print(out)
+    assert out.get("allocations", 0) >= 30, out
+    assert out["oom"] == out["allocations"] and out["other"] == [] and out["lengths_differ"] == [], out
+    assert out["lengths"][:5] == [0, 1440, 64, 700, 1], out        # the pushes, the pulls (nothing runs dry) and the drain did something
+    assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
 
 
 def test_decision_logic_of_the_library_equals_the_oracles_on_scripted_decoders(harness):
