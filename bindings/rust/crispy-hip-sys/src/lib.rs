@@ -229,6 +229,12 @@ extern "C" {
     pub fn crispy_rn_record_drain_device(h: *mut crispy_rn, max_frames: c_long, format: c_int, d_out: *mut c_void, out_stride: c_long, n_frames: *mut c_long, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_rn_record_drain(h: *mut crispy_rn, max_frames: c_long, format: c_int, out: *mut c_void, out_stride: c_long, n_frames: *mut c_long) -> c_int;
     pub fn crispy_record_worker_plan(mic_len: c_long, app_len: c_long, max_frames: c_long, mic_off: *mut c_long, app_off: *mut c_long, mic_left: *mut c_long, app_left: *mut c_long) -> c_long;
+    pub fn crispy_rn_bypass_configure(h: *mut crispy_rn, raw_input_rate: c_float) -> c_int;
+    pub fn crispy_rn_capture_out_len(h: *const crispy_rn, n_frames: c_long) -> c_long;
+    pub fn crispy_rn_capture_device(h: *mut crispy_rn, d_in: *const c_void, in_stride: c_long, n_frames: c_long, channels: c_int, format: c_int, d_out: *mut c_float, out_stride: c_long, d_mono: *mut c_float, mono_stride: c_long, d_rms: *mut c_float, n_out: *mut c_long, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_rn_capture(h: *mut crispy_rn, input: *const c_void, in_stride: c_long, n_frames: c_long, channels: c_int, format: c_int, out: *mut c_float, out_stride: c_long, rms: *mut c_float, n_out: *mut c_long) -> c_int;
+    pub fn crispy_rn_record_app_push_at_device(h: *mut crispy_rn, d_in: *const c_float, in_stride: c_long, n_frames: c_long, channels: c_int, from_rate: c_int, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_rn_record_app_push_at(h: *mut crispy_rn, input: *const c_float, in_stride: c_long, n_frames: c_long, channels: c_int, from_rate: c_int) -> c_int;
     pub fn crispy_rn_synchronize(h: *mut crispy_rn) -> c_int;
     pub fn crispy_rn_set_timing(h: *mut crispy_rn, enable: c_int) -> c_int;
     pub fn crispy_rn_last_kernel_ms(h: *mut crispy_rn, frame_kernel_ms: *mut c_float, total_ms: *mut c_float) -> c_int;
@@ -516,6 +522,58 @@ impl BatchDenoiser {
         rms.resize(self.n_streams, 0.0);
         // SAFETY: input holds n_streams rows of n_in samples, rms n_streams values; the call returns when rms is complete.
         check(unsafe { crispy_rn_level(self.h, input.as_ptr(), n_in as c_long, n_in as c_long, rms.as_mut_ptr()) })
+    }
+    /// `record_app_push` for a stream at its own rate (the macOS handler's `resample_audio`, recording.rs:13-39): downmix,
+    /// resampling to 48 kHz and the ring append on the device.  `from_rate` 8000...384000; 48000 is `record_app_push`.
+    pub fn record_app_push_at(&mut self, input: &[f32], n_frames: usize, channels: usize, from_rate: u32) -> Result<(), CrispyError> {
+        let row = n_frames * channels;
+        if input.len() != row * self.n_streams {
+            return Err(CrispyError { code: CRISPY_ERR_INVALID_ARG, message: "BatchDenoiser::record_app_push_at: input length".into() });
+        }
+        // SAFETY: input holds n_streams rows of n_frames * channels samples; the call returns when they are in the ring.
+        check(unsafe { crispy_rn_record_app_push_at(self.h, input.as_ptr(), row as c_long, n_frames as c_long, channels as c_int, from_rate as c_int) })
+    }
+    /// Noise suppression off, recording on (the `shared == None` arm, audio.rs:545, 697-714): from here on `capture_i16` /
+    /// `capture_f32` resample the raw mono to 48 kHz instead of denoising it.  0 returns to the RNNoise arm.
+    pub fn configure_bypass(&mut self, raw_input_rate: f32) -> Result<(), CrispyError> {
+        check(unsafe { crispy_rn_bypass_configure(self.h, raw_input_rate) })
+    }
+    /// Samples per stream the next capture of `n_frames` frames returns.
+    pub fn capture_out_len(&self, n_frames: usize) -> Result<usize, CrispyError> {
+        let n = unsafe { crispy_rn_capture_out_len(self.h, n_frames as c_long) };
+        if n < 0 {
+            check(n as c_int)?;
+        }
+        Ok(n as usize)
+    }
+    fn capture_raw(&mut self, input: *const c_void, n_frames: usize, channels: usize, format: c_int, output: &mut Vec<f32>, rms: &mut Vec<f32>) -> Result<usize, CrispyError> {
+        let want = self.capture_out_len(n_frames)?;
+        output.resize(want * self.n_streams, 0.0);
+        rms.resize(self.n_streams, 0.0);
+        let mut got: c_long = 0;
+        // SAFETY: the callers checked that input holds n_streams rows of n_frames * channels elements of `format`; output holds
+        // n_streams rows of `want` samples -- what the library announced --, rms n_streams values; the call returns when both
+        // are complete.
+        check(unsafe { crispy_rn_capture(self.h, input, (n_frames * channels) as c_long, n_frames as c_long, channels as c_int, format, output.as_mut_ptr(), want.max(1) as c_long, rms.as_mut_ptr(), &mut got) })?;
+        debug_assert_eq!(got as usize, want);
+        Ok(got as usize)
+    }
+    /// The whole body of one i16 capture callback (build_input_stream_i16 + push_mono_to_buffers, audio.rs:682-730, 794-855):
+    /// `s as f32 / 32768.0`, the downmix of `channels` interleaved samples per frame, the level meter and the handle's arm,
+    /// from the device's own samples.  input: `n_streams` rows of `n_frames * channels`; output (resized here): what the arm
+    /// returned per stream; rms (resized here): one level per stream.  Returns the samples per stream.
+    pub fn capture_i16(&mut self, input: &[i16], n_frames: usize, channels: usize, output: &mut Vec<f32>, rms: &mut Vec<f32>) -> Result<usize, CrispyError> {
+        if input.len() != n_frames * channels * self.n_streams {
+            return Err(CrispyError { code: CRISPY_ERR_INVALID_ARG, message: "BatchDenoiser::capture_i16: input length".into() });
+        }
+        self.capture_raw(input.as_ptr() as *const c_void, n_frames, channels, CRISPY_PCM_I16, output, rms)
+    }
+    /// `capture_i16` for an f32 device (build_input_stream_f32, audio.rs:732-792).  (u16: the C entry point.)
+    pub fn capture_f32(&mut self, input: &[f32], n_frames: usize, channels: usize, output: &mut Vec<f32>, rms: &mut Vec<f32>) -> Result<usize, CrispyError> {
+        if input.len() != n_frames * channels * self.n_streams {
+            return Err(CrispyError { code: CRISPY_ERR_INVALID_ARG, message: "BatchDenoiser::capture_f32: input length".into() });
+        }
+        self.capture_raw(input.as_ptr() as *const c_void, n_frames, channels, CRISPY_PCM_F32, output, rms)
     }
     /// (mic, app): samples per stream in the two recording rings.
     pub fn record_buffered(&self) -> Result<(usize, usize), CrispyError> {

@@ -36,6 +36,8 @@ RN_SYMBOLS = (
     "crispy_rn_record_configure", "crispy_rn_record_app_push_device", "crispy_rn_record_app_push",
     "crispy_rn_level_device", "crispy_rn_level", "crispy_rn_record_buffered", "crispy_rn_record_frames_ready",
     "crispy_rn_record_drain_device", "crispy_rn_record_drain", "crispy_record_worker_plan",
+    "crispy_rn_bypass_configure", "crispy_rn_capture_out_len", "crispy_rn_capture_device", "crispy_rn_capture",
+    "crispy_rn_record_app_push_at_device", "crispy_rn_record_app_push_at",
 )
 REC_FRAME = 1152                          # the recording worker's frame_size (commands/recording.rs:196)
 PCM_F32, PCM_I16, PCM_U16 = 0, 1, 2      # CRISPY_PCM_*
@@ -197,6 +199,15 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_rn_record_drain.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, lp]
     L.crispy_record_worker_plan.argtypes = [C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p, lp, lp]
     L.crispy_record_worker_plan.restype = C.c_long
+    L.crispy_rn_bypass_configure.argtypes = [C.c_void_p, C.c_float]
+    L.crispy_rn_capture_out_len.argtypes = [C.c_void_p, C.c_long]
+    L.crispy_rn_capture_out_len.restype = C.c_long
+    L.crispy_rn_capture_device.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_long,
+                                           C.c_void_p, C.c_long, C.c_void_p, lp, C.c_void_p]
+    L.crispy_rn_capture.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_long,
+                                    C.c_void_p, lp]
+    L.crispy_rn_record_app_push_at_device.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_void_p]
+    L.crispy_rn_record_app_push_at.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int]
     L.crispy_rn_debug_capture.argtypes = [C.c_void_p, C.c_int]
     L.crispy_rn_debug_read.argtypes = [C.c_void_p, C.c_int, f32p, C.c_size_t]
     L.crispy_mel_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]

@@ -232,6 +232,56 @@ hipError_t rn_launch_rec_app(const RnRecApp& a, hipStream_t s);
 hipError_t rn_launch_rec_drain(const RnRecDrain& a, int format, hipStream_t s);
 hipError_t rn_launch_level(const RnLevel& a, hipStream_t s);
 
+// ---- crispy_rn_capture* / crispy_rn_record_app_push_at* (rn_capture.hip) ----
+// The capture callbacks' first statement (audio.rs:754-755, 816-818, 880-883): per frame, the samples converted to f32 and
+// `iter().sum::<f32>() / input_channels as f32`.
+struct RnCapture {
+  const void* in;      // [B][in_stride] elements of the format: frames of `channels` interleaved samples
+  long in_stride;
+  int n;               // frames per stream, 1...2^24
+  int channels;        // 1...8
+  float* mono;         // [B][mono_stride]
+  long mono_stride;
+  int B;
+};
+
+// The bypass arm's LinearResampler (audio.rs:108-133, 711-714) over the mono of one capture: output r interpolates mono samples
+// idx[r] - 1 and idx[r] (idx[r] == 0: the previous capture's last sample) at t[r]; idx == nullptr: the resampler passes
+// through, out = mono.  Both arrays are the same for every stream of the handle.
+struct RnCaptureResample {
+  const float* mono;       // [B][mono_stride]
+  long mono_stride;
+  int n_in;                // mono samples per stream, >= 1
+  const int* idx;          // [n_out] or null
+  const float* t;          // [n_out]
+  const float* last_old;   // [B]
+  float* last_new;         // [B]: mono[b][n_in - 1]
+  float* out;              // [B][out_stride]
+  long out_stride;
+  long n_out;              // may be 0 (the capture that primes the resampler)
+  int B;
+};
+
+// resample_audio (src-tauri/src/recording.rs:13-39) of the downmixed frames + append to the app ring: kept output j is output
+// skip + j of the buffer, at src_pos = (skip + j) as f64 * ratio.
+struct RnRecAppAt {
+  const float* in;     // [B][in_stride]: n_in frames of `channels` interleaved samples
+  long in_stride;
+  int n_in;            // frames per stream, 1...2^24
+  int channels;        // 1...8
+  double ratio;        // from_rate as f64 / 48000 as f64
+  long skip;           // outputs of this buffer that the ring's eviction drops at the front
+  float* ring;         // [B][cap]
+  int cap;
+  int tail;            // where the first kept output goes, < cap
+  int n;               // outputs kept per stream, 1...cap; floor((skip + n - 1) * ratio) < n_in
+  int B;
+};
+
+hipError_t rn_launch_capture(const RnCapture& a, int format, hipStream_t s);       // format: f32 / i16 / u16
+hipError_t rn_launch_capture_resample(const RnCaptureResample& a, hipStream_t s);
+hipError_t rn_launch_rec_app_at(const RnRecAppAt& a, hipStream_t s);
+
 // A launch covers at most 2^23 workgroups (the runtime refuses 2^32 work-items per grid dimension and more): a handle of
 // several hundred thousand streams is covered in turns of streams, each turn with its own row pointers.
 // launch(b0, nb): the kernel for streams b0 ... b0 + nb - 1, `tiles` (<= RN_MAX_BLOCKS) workgroups each.

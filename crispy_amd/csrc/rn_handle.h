@@ -1,8 +1,9 @@
 // rn_handle.h -- the RNNoise handle behind `crispy_rn` (include/crispy_hip.h) and the state of its three halves, shared by
-// the two translation units that implement its entry points: crispy_api.cpp (create / process / reset ...) and rn_io.cpp
-// (crispy_rn_push*, crispy_rn_pull*, crispy_rn_record_*, crispy_rn_level*).  Everything here owns what it holds: device
+// the translation units that implement its entry points: crispy_api.cpp (create / process / reset ...), rn_io.cpp
+// (crispy_rn_push*, crispy_rn_pull*, crispy_rn_record_*, crispy_rn_level*) and rn_capture_io.cpp (crispy_rn_capture*,
+// crispy_rn_bypass_configure, crispy_rn_record_app_push_at*).  Everything here owns what it holds: device
 // buffers are DevBuf, events EventList (api_util.h), streams Stream, the halves unique_ptr members -- deleting the handle
-// releases all of it, streams last.  The types are plain state; the logic that drives them is in the two .cpp files.
+// releases all of it, streams last.  The types are plain state; the logic that drives them is in the .cpp files.
 #pragma once
 #include <cstddef>
 #include <memory>
@@ -109,6 +110,21 @@ struct RnRecord {
   std::vector<long> mic_off, app_off;     // host scratch of one drain
 };
 
+// The capture callback in front of push_sample (crispy_rn_capture*): the mono row of the current capture and, for the
+// `shared == None` arm of push_mono_to_buffers (audio.rs:697-714), the callback's own LinearResampler(input_rate, 48000).
+// Created on first use; a handle without one captures into the RNNoise arm.
+struct RnCaptureState {
+  float bypass_rate = 0.f;  // > 0: noise suppression off, the raw capture rate; 0: the RNNoise arm
+  bool resample = false;    // the bypass resampler is in: the rate is 1 Hz or more off 48 kHz
+  LinResState rs;           // its has_last / input_pos / next_output_pos
+  int cur = 0;              // which half of `last` is current
+  DevBuf<float> last;       // state [2][B]: its last_sample
+  PinnedUpload pos;         // (idx[n], t[n]) of the current capture
+  std::vector<int> idx;     // host scratch of one capture
+  std::vector<float> t;
+  DevBuf<float> mono;       // scratch [B][mono_stride]: the mono of a capture whose caller does not ask for it
+};
+
 }  // namespace crispy
 
 struct crispy_rn {
@@ -172,6 +188,7 @@ struct crispy_rn {
   std::unique_ptr<crispy::RnAdapter> ad;     // the capture-rate adapter (crispy_rn_push*): created on first use
   std::unique_ptr<crispy::RnPlayback> pb;    // the playback ring (crispy_rn_pull*): created by crispy_rn_playback_configure
   std::unique_ptr<crispy::RnRecord> rec;     // the recording rings (crispy_rn_record_*): created on first use
+  std::unique_ptr<crispy::RnCaptureState> cap;   // the capture callback's state (crispy_rn_capture*): created on first use
 
   // Every stream the handle created is drained before anything it holds goes.
   ~crispy_rn() {
@@ -188,4 +205,42 @@ namespace crispy {
 int rn_zero_state(crispy_rn* h, int stream);
 int rn_process_frames_device(crispy_rn* h, const float* d_in, float* d_out, float* d_vad, int n_frames, long stride_t, long stride_b,
                              hipStream_t s);
+
+// rn_io.cpp, what rn_capture_io.cpp uses of it.
+// Appending n samples to a ring of cap (audio.rs:280-285, 719-724: the oldest sample is dropped for each one that does not
+// fit): how many of the n are skipped at the front, where the first one kept goes, and the ring's position afterwards.
+struct AppendPlan {
+  long skip = 0;
+  int n = 0;
+  int tail = 0;
+  RingPos after;
+};
+AppendPlan plan_append(const RingPos& r, int cap, long n);
+// The n > 0 samples per stream a call has just written to d_rows [B][stride], appended to ring [B][cap] at pos on s.
+int ring_append(float* ring, RingPos& pos, int cap, const float* d_rows, long stride, long n, int B, hipStream_t s);
+// LinearResampler::process_sample's position recurrence over n_in samples (see the definition).
+long linres_advance(LinResState& st, double step, long n_in, long limit, std::vector<int>* idx, std::vector<float>* t);
+constexpr long kPushMaxNew = 1L << 28;      // 48 kHz samples per stream and push (or bypassed capture)
+// the handle's adapter, created with the defaults when there is none; of a const handle: the defaults themselves
+RnAdapter* adapter_of(crispy_rn* h);
+const RnAdapter* adapter_of(const crispy_rn* h);
+inline bool recording(const crispy_rn* h) { return h->rec && h->rec->cap > 0; }
+// What a push of n_in samples will do, worked out on the host without touching the handle.
+struct PushPlan {
+  LinResState rs;      // resampler state behind the push
+  long n_new = 0;      // 48 kHz samples the push adds per stream
+  int frames = 0;      // frames completed: (carry + n_new) / 480
+  int carry_len = 0;   // remainder behind the push
+  long n_out = 0;      // samples returned: 480 x (frames, minus the dropped first one)
+};
+// who: the entry point named in the error message.  idx / t: where a push records its positions; null: count only.
+int plan_push(const RnAdapter* a, long n_in, std::vector<int>* idx, std::vector<float>* t, PushPlan* p, const char* who);
+// crispy_rn_push_device behind its NULL checks, the handle's device current
+int push_device_impl(crispy_rn* h, const float* d_in, long in_stride, long n_in, float* d_out, long out_stride, float* d_frames48,
+                     long frames_stride, float* d_vad, long* n_out, hipStream_t s, const char* who);
+// crispy_rn_record_app_push*: the argument checks, and the enqueue behind them (n_frames > 0, the handle's device current)
+int check_app_push(const crispy_rn* h, const float* in, long in_stride, long n_frames, int channels, const char* who);
+int app_push_device_impl(crispy_rn* h, const float* d_in, long in_stride, long n_frames, int channels, hipStream_t s);
+// crispy_rn_level_device behind its checks
+int level_device_impl(crispy_rn* h, const float* d_in, long in_stride, long n_in, float* d_rms, hipStream_t s);
 }  // namespace crispy

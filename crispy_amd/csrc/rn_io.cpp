@@ -45,7 +45,6 @@ int PinnedUpload::reserve(size_t words, const char* who) {
 namespace {
 
 constexpr long kPushMaxIn = 1L << 24;       // capture samples per stream and push
-constexpr long kPushMaxNew = 1L << 28;      // 48 kHz samples per stream and push
 constexpr long kPullMaxFrames = 1L << 24;   // output frames per pull
 constexpr long kLevelMaxIn = 1L << 24;      // samples per stream and call: the f32 count is exact
 constexpr long REC_MAX_DESYNC = 2400;       // (SAMPLE_RATE / 20).max(frame_size): 50 ms at 48 kHz
@@ -55,16 +54,14 @@ constexpr long REC_MAX_CAP = 1L << 28;      // ring indices and the elements of 
 inline size_t pcm_bytes(int format) { return format == CRISPY_PCM_F32 ? 4 : 2; }
 inline long rec_elems_per_frame(int format) { return format == CRISPY_PCM_F32 ? REC_FRAME : 2L * REC_FRAME; }
 
+}  // namespace
+
+// What rn_capture_io.cpp uses as well is declared in rn_handle.h and defined in namespace crispy; the rest stays local.
+
 // ---- rings ------------------------------------------------------------------------------------------------------------
 
-// Appending n samples to a ring of cap (audio.rs:280-285, 719-724: the oldest sample is dropped for each one that does not
-// fit): how many of the n are skipped at the front, where the first one kept goes, and the ring's position afterwards.
-struct AppendPlan {
-  long skip = 0;
-  int n = 0;
-  int tail = 0;
-  RingPos after;
-};
+namespace crispy {
+
 AppendPlan plan_append(const RingPos& r, int cap, long n) {
   AppendPlan p;
   if (n >= cap) {                    // everything that was there is evicted, and the front of this block with it
@@ -88,7 +85,6 @@ AppendPlan plan_append(const RingPos& r, int cap, long n) {
   return p;
 }
 
-// The n > 0 samples per stream a push has just written to d_rows [B][stride], appended to ring [B][cap] at pos on s.
 int ring_append(float* ring, RingPos& pos, int cap, const float* d_rows, long stride, long n, int B, hipStream_t s) {
   const AppendPlan p = plan_append(pos, cap, n);
   RnRingAppend a{};
@@ -137,48 +133,13 @@ long linres_advance(LinResState& st, double step, long n_in, long limit, std::ve
   return n;
 }
 
-RnAdapter* adapter_of(crispy_rn* h) {
-  if (!h->ad) h->ad.reset(new RnAdapter());       // (std::bad_alloc: the entry point's guard makes it CRISPY_ERR_OOM)
-  return h->ad.get();
-}
-const RnAdapter* adapter_of(const crispy_rn* h) {
-  static const RnAdapter fresh;
-  return h->ad ? h->ad.get() : &fresh;
-}
+}  // namespace crispy
+
+namespace {
 
 RnRecord* record_of(crispy_rn* h) {
-  if (!h->rec) h->rec.reset(new RnRecord());      // (std::bad_alloc: as above)
+  if (!h->rec) h->rec.reset(new RnRecord());      // (std::bad_alloc: the entry point's guard makes it CRISPY_ERR_OOM)
   return h->rec.get();
-}
-inline bool recording(const crispy_rn* h) { return h->rec && h->rec->cap > 0; }
-
-// What a push of n_in samples will do, worked out on the host without touching the handle.
-struct PushPlan {
-  LinResState rs;      // resampler state behind the push
-  long n_new = 0;      // 48 kHz samples the push adds per stream
-  int frames = 0;      // frames completed: (carry + n_new) / 480
-  int carry_len = 0;   // remainder behind the push
-  long n_out = 0;      // samples returned: 480 x (frames, minus the dropped first one)
-};
-
-// who: the entry point named in the error message.  idx / t: where a push records its positions; null: count only.
-int plan_push(const RnAdapter* a, long n_in, std::vector<int>* idx, std::vector<float>* t, PushPlan* p, const char* who) {
-  if (n_in < 0) return fail(CRISPY_ERR_INVALID_ARG, "%s: n_in < 0", who);
-  if (n_in > kPushMaxIn) return fail(CRISPY_ERR_INVALID_ARG, "%s: n_in %ld above the limit of %ld samples per push", who, n_in, kPushMaxIn);
-  p->rs = a->rs;
-  if (a->resample) {
-    if (idx) { idx->clear(); t->clear(); }
-    const double step = (double)(a->rate / 48000.f);
-    p->n_new = linres_advance(p->rs, step, n_in, kPushMaxNew, idx, t);
-    if (p->n_new < 0) return fail(CRISPY_ERR_INVALID_ARG, "%s: more than %ld resampled samples per push", who, kPushMaxNew);
-  } else {
-    p->n_new = n_in;
-  }
-  const long total = a->carry_len + p->n_new;
-  p->frames = (int)(total / RN_FRAME);
-  p->carry_len = (int)(total % RN_FRAME);
-  p->n_out = (long)(p->frames - (a->first && p->frames > 0 ? 1 : 0)) * RN_FRAME;
-  return CRISPY_OK;
 }
 
 // The carry and last-sample halves are state: both new buffers exist before either is installed.
@@ -195,6 +156,38 @@ int ensure_adapter_state(crispy_rn* h, RnAdapter* a, const char* who) {
   HIP_TRY(hipMemset(a->carry.p, 0, 2 * B * RN_FRAME * sizeof(float)));
   HIP_TRY(hipMemset(a->last.p, 0, 2 * B * sizeof(float)));
   HIP_TRY(hipDeviceSynchronize());
+  return CRISPY_OK;
+}
+
+}  // namespace
+
+namespace crispy {
+
+RnAdapter* adapter_of(crispy_rn* h) {
+  if (!h->ad) h->ad.reset(new RnAdapter());       // (std::bad_alloc: the entry point's guard makes it CRISPY_ERR_OOM)
+  return h->ad.get();
+}
+const RnAdapter* adapter_of(const crispy_rn* h) {
+  static const RnAdapter fresh;
+  return h->ad ? h->ad.get() : &fresh;
+}
+
+int plan_push(const RnAdapter* a, long n_in, std::vector<int>* idx, std::vector<float>* t, PushPlan* p, const char* who) {
+  if (n_in < 0) return fail(CRISPY_ERR_INVALID_ARG, "%s: n_in < 0", who);
+  if (n_in > kPushMaxIn) return fail(CRISPY_ERR_INVALID_ARG, "%s: n_in %ld above the limit of %ld samples per push", who, n_in, kPushMaxIn);
+  p->rs = a->rs;
+  if (a->resample) {
+    if (idx) { idx->clear(); t->clear(); }
+    const double step = (double)(a->rate / 48000.f);
+    p->n_new = linres_advance(p->rs, step, n_in, kPushMaxNew, idx, t);
+    if (p->n_new < 0) return fail(CRISPY_ERR_INVALID_ARG, "%s: more than %ld resampled samples per push", who, kPushMaxNew);
+  } else {
+    p->n_new = n_in;
+  }
+  const long total = a->carry_len + p->n_new;
+  p->frames = (int)(total / RN_FRAME);
+  p->carry_len = (int)(total % RN_FRAME);
+  p->n_out = (long)(p->frames - (a->first && p->frames > 0 ? 1 : 0)) * RN_FRAME;
   return CRISPY_OK;
 }
 
@@ -299,6 +292,10 @@ int push_device_impl(crispy_rn* h, const float* d_in, long in_stride, long n_in,
   return CRISPY_OK;
 }
 
+}  // namespace crispy
+
+namespace {
+
 // ---- pull -------------------------------------------------------------------------------------------------------------
 
 // A fresh output_buf of one second at in_rate and resample_pos = 0.  The ring is state: it is replaced only when its size
@@ -393,7 +390,11 @@ int pull_device_impl(crispy_rn* h, long n_frames, int channels, int format, void
   return CRISPY_OK;
 }
 
+}  // namespace
+
 // ---- record -----------------------------------------------------------------------------------------------------------
+
+namespace crispy {
 
 int check_app_push(const crispy_rn* h, const float* in, long in_stride, long n_frames, int channels, const char* who) {
   if (!recording(h)) return fail(CRISPY_ERR_INVALID_ARG, "%s: recording not configured (crispy_rn_record_configure)", who);
@@ -425,6 +426,10 @@ int app_push_device_impl(crispy_rn* h, const float* d_in, long in_stride, long n
   return CRISPY_OK;
 }
 
+}  // namespace crispy
+
+namespace {
+
 int check_level(const float* in, long in_stride, long n_in, const float* rms, const char* who) {
   if (n_in < 0) return fail(CRISPY_ERR_INVALID_ARG, "%s: n_in < 0", who);
   if (n_in > kLevelMaxIn) return fail(CRISPY_ERR_INVALID_ARG, "%s: n_in %ld above the limit of %ld samples per call", who, n_in, kLevelMaxIn);
@@ -434,7 +439,9 @@ int check_level(const float* in, long in_stride, long n_in, const float* rms, co
   return CRISPY_OK;
 }
 
-int level_device_impl(crispy_rn* h, const float* d_in, long in_stride, long n_in, float* d_rms, hipStream_t s) {
+}  // namespace
+
+int crispy::level_device_impl(crispy_rn* h, const float* d_in, long in_stride, long n_in, float* d_rms, hipStream_t s) {
   RnLevel a{};
   a.in = d_in;
   a.in_stride = in_stride;
@@ -444,6 +451,8 @@ int level_device_impl(crispy_rn* h, const float* d_in, long in_stride, long n_in
   HIP_TRY(rn_launch_level(a, s));
   return CRISPY_OK;
 }
+
+namespace {
 
 // The arguments every drain checks before it plans.
 int check_drain(const crispy_rn* h, long max_frames, int format, const void* out, const long* n_frames, const char* who) {

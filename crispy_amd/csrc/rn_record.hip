@@ -22,6 +22,7 @@
 
 #include "../../include/crispy_hip.h"
 #include "rn_common.h"
+#include "rn_downmix.h"      // app_downmix: the capture handlers' downmix
 
 #pragma clang fp contract(off)
 
@@ -37,16 +38,6 @@ constexpr int LV_PITCH = LV_SAMPLES + 1;            // LDS row pitch: lanes that
 constexpr int LV_ROWS_PER_THREAD = LV_STREAMS * LV_SAMPLES / LV_THREADS;      // 32
 
 __host__ __device__ inline long rec_tiles(long n, long tile) { return n > 0 ? (n + tile - 1) / tile : 1; }
-
-// The capture handlers' downmix.  1 channel: the sample itself; 2: (f0 + f1) / 2.0; more: `iter().sum::<f32>()`, which starts
-// from 0.0 and adds in order, then `/ channels as f32`.  Every add rounds on its own and the division is correctly rounded.
-__device__ __forceinline__ float app_downmix(const float* f, int channels) {
-  if (channels == 1) return f[0];
-  if (channels == 2) return (f[0] + f[1]) / 2.0f;
-  float acc = 0.0f;
-  for (int c = 0; c < channels; ++c) acc = acc + f[c];
-  return acc / (float)channels;
-}
 
 // A lane's four frames are 256 apart, so that every store of a wave covers consecutive ring addresses wherever the tail stands.
 __global__ __launch_bounds__(REC_THREADS) void rn_rec_app_kernel(RnRecApp a) {

@@ -232,18 +232,71 @@ class DenoiseState:
         here on every push that returns samples feeds the mic ring.  Leaves denoiser, adapter and playback ring alone."""
         N.check(self._L.crispy_rn_record_configure(self._h, int(ring_samples)), self._L)
 
-    def record_app_push(self, x: np.ndarray, channels: int = 1):
+    def record_app_push(self, x: np.ndarray, channels: int = 1, from_rate: Optional[int] = None):
         """`crispy_rn_record_app_push`: x [B, n_frames * channels] interleaved app audio at 48 kHz, downmixed on the device
-        and appended to the app ring."""
+        and appended to the app ring.  With from_rate (`crispy_rn_record_app_push_at`): audio at that rate, resampled to
+        48 kHz as the handler's `resample_audio` does (recording.rs:13-39), buffer by buffer, in the same kernel."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         if x.ndim != 2 or x.shape[0] != self.n_streams or x.shape[1] % int(channels):
             raise ValueError(f"record_app_push: x must be [{self.n_streams}, n_frames * channels]")
-        N.check(self._L.crispy_rn_record_app_push(self._h, x.ctypes.data, max(x.shape[1], 1), x.shape[1] // int(channels),
-                                                  int(channels)), self._L)
+        if from_rate is None:
+            N.check(self._L.crispy_rn_record_app_push(self._h, x.ctypes.data, max(x.shape[1], 1), x.shape[1] // int(channels),
+                                                      int(channels)), self._L)
+        else:
+            N.check(self._L.crispy_rn_record_app_push_at(self._h, x.ctypes.data, max(x.shape[1], 1), x.shape[1] // int(channels),
+                                                         int(channels), int(from_rate)), self._L)
 
-    def record_app_push_device(self, d_in: int, in_stride: int, n_frames: int, channels: int = 1, stream: int = 0):
-        N.check(self._L.crispy_rn_record_app_push_device(self._h, d_in, int(in_stride), int(n_frames), int(channels),
-                                                         stream or None), self._L)
+    def record_app_push_device(self, d_in: int, in_stride: int, n_frames: int, channels: int = 1, stream: int = 0,
+                               from_rate: Optional[int] = None):
+        if from_rate is None:
+            N.check(self._L.crispy_rn_record_app_push_device(self._h, d_in, int(in_stride), int(n_frames), int(channels),
+                                                             stream or None), self._L)
+        else:
+            N.check(self._L.crispy_rn_record_app_push_at_device(self._h, d_in, int(in_stride), int(n_frames), int(channels),
+                                                                int(from_rate), stream or None), self._L)
+
+    # -- the capture callback itself (format, downmix, level, arm: crispy_rn_capture* / crispy_rn_bypass_configure) -----
+    def bypass_configure(self, raw_input_rate: float):
+        """Noise suppression off, recording on -- the `shared == None` arm of push_mono_to_buffers (audio.rs:697-714) with a
+        fresh `LinearResampler(raw_input_rate, 48000)`: from here on `capture` resamples the raw mono instead of denoising it.
+        0 returns to the RNNoise arm.  Pushes, pulls, the denoiser and the playback ring are not affected."""
+        N.check(self._L.crispy_rn_bypass_configure(self._h, float(raw_input_rate)), self._L)
+
+    def capture_out_len(self, n_frames: int) -> int:
+        """Samples per stream the NEXT capture of n_frames frames returns."""
+        n = self._L.crispy_rn_capture_out_len(self._h, int(n_frames))
+        if n < 0:
+            N.check(int(n), self._L)
+        return int(n)
+
+    def capture(self, x: np.ndarray, channels: int = 1):
+        """`crispy_rn_capture`, one capture callback: x [B, n_frames * channels] interleaved frames as the device hands them
+        out -- float32, int16 or uint16, uploaded as they are -- -> (out [B, n_out], rms [B]): conversion, the mic downmix
+        (`iter().sum::<f32>() / channels`), the level meter and the handle's arm, all on the device."""
+        fmt = {np.dtype(np.float32): N.PCM_F32, np.dtype(np.int16): N.PCM_I16, np.dtype(np.uint16): N.PCM_U16}.get(x.dtype)
+        if fmt is None:
+            raise ValueError("capture: x must be float32, int16 or uint16")
+        x = np.ascontiguousarray(x)
+        if x.ndim != 2 or x.shape[0] != self.n_streams or x.shape[1] % int(channels):
+            raise ValueError(f"capture: x must be [{self.n_streams}, n_frames * channels]")
+        n_frames = x.shape[1] // int(channels)
+        n_out = self.capture_out_len(n_frames)
+        out = np.empty((self.n_streams, n_out), dtype=np.float32)
+        rms = np.zeros(self.n_streams, dtype=np.float32)
+        got = C.c_long()
+        N.check(self._L.crispy_rn_capture(self._h, x.ctypes.data, max(x.shape[1], 1), n_frames, int(channels), fmt,
+                                          out.ctypes.data, max(n_out, 1), rms.ctypes.data, C.byref(got)), self._L)
+        assert got.value == n_out
+        return out, rms
+
+    def capture_device(self, d_in: int, in_stride: int, n_frames: int, channels: int, fmt: str, d_out: int, out_stride: int,
+                       d_mono: int = 0, mono_stride: int = 0, d_rms: int = 0, stream: int = 0) -> int:
+        """`crispy_rn_capture_device` on device pointers; returns n_out (known on return, the work is only enqueued)."""
+        got = C.c_long()
+        N.check(self._L.crispy_rn_capture_device(self._h, d_in, int(in_stride), int(n_frames), int(channels), self.PCM[fmt][0],
+                                                 d_out, int(out_stride), d_mono or None, int(mono_stride), d_rms or None,
+                                                 C.byref(got), stream or None), self._L)
+        return int(got.value)
 
     def level(self, x: np.ndarray) -> np.ndarray:
         """`crispy_rn_level`: the callback's level meter over x [B, n], `(sum(mono * mono) / n).sqrt()` per stream with the
@@ -508,6 +561,13 @@ class CaptureBuffers:
         suppressor returned ([B, n_out], appended to the handle's recording ring on the device, which `drain_block` reads)
         and the callback's rms per stream.  The RNNoise arm only: its recording resampler always passes through."""
         return ns.push_block(x), ns.denoise.level(x)
+
+    @staticmethod
+    def capture_block(x: np.ndarray, ns: "RnnNoiseProcessor", channels: int = 1):
+        """The whole capture callback as one `crispy_rn_capture`: x [B, n_frames * channels] in the device's own format
+        (float32 / int16 / uint16) -> what `push_mono_block` returns for the mono of these frames.  After
+        `ns.denoise.bypass_configure(rate)` it is the `ns=None` arm of `push_mono` instead: the raw mono resampled to 48 kHz."""
+        return ns.denoise.capture(x, channels)
 
     @staticmethod
     def drain_block(ns: "RnnNoiseProcessor", max_frames: Optional[int] = None, fmt: str = "i16") -> np.ndarray:

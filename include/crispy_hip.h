@@ -334,6 +334,68 @@ int crispy_rn_record_drain(crispy_rn *h, long max_frames, int format, void *out,
 long crispy_record_worker_plan(long mic_len, long app_len, long max_frames, long *mic_off, long *app_off, long *mic_left,
                                long *app_left);
 
+/*
+ * The capture callbacks themselves, for all streams of a handle: build_input_stream_f32 / _i16 / _u16 (audio.rs:732-921) and
+ * push_mono_to_buffers (audio.rs:682-730).  One crispy_rn_capture per capture callback is the whole callback, from the
+ * device's bytes to the rings; every result is bit for bit that of the per-sample loops.  Three steps, in order, on one stream:
+ *   1. mono      per frame of `channels` interleaved samples of `format`: each sample converted -- f32: s; i16:
+ *                s as f32 / 32768.0 (audio.rs:817); u16: (s as f32 - 32768.0) / 32768.0 (audio.rs:882) --, then
+ *                iter().sum::<f32>() / input_channels as f32: the sum starts from 0.0 and adds in channel order, every add
+ *                rounded, the division correctly rounded.  For EVERY channel count: the mic path has no special case for one
+ *                or two channels (the app handlers have), so a -0.0 in a mono f32 stream becomes +0.0.
+ *   2. level     the callback's level meter over the mono: crispy_rn_level_device.
+ *   3. the arm   a property of the handle (crispy_rn_bypass_configure):
+ *      RNNoise arm (default, `Some(shared)`): exactly crispy_rn_push_device on the mono -- d_out and *n_out are the push's, the
+ *                playback and recording rings are fed as a push feeds them, and every later call on the handle behaves as if
+ *                the caller had converted on the host and called crispy_rn_level and crispy_rn_push.
+ *      bypass arm (`shared == None`, noise suppression off, audio.rs:545, 697-699): the mono goes through the callback's own
+ *                LinearResampler(raw_input_rate, 48000); d_out / *n_out receive the 48 kHz samples it emitted (the `out`
+ *                vector of audio.rs:711-714: unscaled, no clamp, no volume); on a handle that records the same samples are
+ *                appended to the mic ring with the ring's eviction (audio.rs:716-725).  It is the only arm in which the
+ *                recording resampler does not pass through.  Positions are the reference's f64 recurrence, run on the host
+ *                and carried across captures; the interpolation last + (sample - last) * t is three separately rounded f32
+ *                operations; the last capture sample per stream stays on the device.
+ */
+/* Enters the bypass arm with a fresh LinearResampler(raw_input_rate, 48000) -- it passes through when the rate is within
+ * 1 Hz of 48000 --, or, with 0, leaves it.  Only crispy_rn_capture* consults the arm: crispy_rn_push*, crispy_rn_pull*, the
+ * DenoiseState, the adapter's carry and the playback ring are never touched by a bypassed capture, and pushes on a bypassed
+ * handle run as before.  crispy_rn_record_configure and crispy_rn_reset leave this resampler alone; every
+ * crispy_rn_bypass_configure resets it.  CRISPY_ERR_INVALID_ARG: a negative rate, a NaN, an infinity; CRISPY_ERR_OOM: the
+ * state (2 x n_streams floats) could not be allocated -- in both cases the handle is as it was. */
+int crispy_rn_bypass_configure(crispy_rn *h, float raw_input_rate);
+/* samples the NEXT capture of n_frames frames will return per stream: crispy_rn_push_out_len in the RNNoise arm, the
+ * resampler's count in the bypass arm; < 0 = error */
+long crispy_rn_capture_out_len(const crispy_rn *h, long n_frames);
+/* DEVICE pointers.  d_in [n_streams][in_stride] elements of `format` (CRISPY_PCM_F32 / _I16 / _U16): n_frames interleaved
+ * frames of `channels` (1...8) samples per stream, at most 2^24 frames per call.  Rows whose pointer and byte stride are
+ * 16-byte aligned and whose frame divides 16 bytes are read with 16-byte loads; the bits do not depend on it.  d_out
+ * [n_streams][out_stride] receives *n_out samples per stream (see the arms above; known on return).  d_mono (nullable)
+ * [n_streams][mono_stride] receives the n_frames mono samples; without it they go to a workspace of the handle.  d_rms
+ * (nullable) [n_streams]: the level meter.  Enqueued on hip_stream (NULL = own stream).  n_frames == 0 is a no-op.
+ * CRISPY_ERR_INVALID_ARG: n_frames < 0 or above 2^24, channels outside 1...8, an unknown format, a stride shorter than its
+ * data, NULL h / d_in / d_out / n_out, d_out overlapping d_mono, and whatever the push rejects; CRISPY_ERR_OOM: a workspace or
+ * an upload buffer could not grow -- in both cases the handle's state is as it was (after CRISPY_ERR_OOM d_mono and d_rms
+ * may have been written). */
+int crispy_rn_capture_device(crispy_rn *h, const void *d_in, long in_stride, long n_frames, int channels, int format,
+                             float *d_out, long out_stride, float *d_mono, long mono_stride, float *d_rms, long *n_out,
+                             void *hip_stream);
+/* the same with HOST pointers: uploads the raw bytes as they are (an i16 mono microphone is half the bytes crispy_rn_push
+ * takes), downloads out and rms (nullable); returns when they are complete */
+int crispy_rn_capture(crispy_rn *h, const void *in, long in_stride, long n_frames, int channels, int format, float *out,
+                      long out_stride, float *rms, long *n_out);
+/* crispy_rn_record_app_push_device for a stream at its own rate (the macOS handler, recording.rs:13-39, 260-369): downmix as
+ * there (1: the sample; 2: (f0 + f1) / 2.0; more: the sum from 0.0 / channels), resample_audio(mono, from_rate, 48000) and the
+ * ring append in one kernel.  resample_audio is stateless per buffer and a closed form in the reference itself: ratio =
+ * from_rate as f64 / 48000 as f64, output_len = ceil(n as f64 / ratio), output i at src_pos = i as f64 * ratio with idx =
+ * floor(src_pos), frac = (src_pos - idx) as f32: s[idx] + (s[idx + 1] - s[idx]) * frac (three rounded f32 operations) while
+ * idx + 1 < n, s[idx] while idx < n, else nothing.  The discontinuity at buffer boundaries is the reference's.  from_rate ==
+ * 48000 is crispy_rn_record_app_push_device.  CRISPY_ERR_INVALID_ARG: what that one rejects, from_rate outside 8000...384000,
+ * more than 2^24 resampled samples: the state is unchanged. */
+int crispy_rn_record_app_push_at_device(crispy_rn *h, const float *d_in, long in_stride, long n_frames, int channels,
+                                        int from_rate, void *hip_stream);
+/* the same with a HOST pointer; returns when the ring holds the samples */
+int crispy_rn_record_app_push_at(crispy_rn *h, const float *in, long in_stride, long n_frames, int channels, int from_rate);
+
 /* Block until everything enqueued on the handle's own stream has finished. */
 int crispy_rn_synchronize(crispy_rn *h);
 
