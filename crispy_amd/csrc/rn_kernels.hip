@@ -73,6 +73,19 @@ __device__ __forceinline__ float dpp_add(float v) {
   asm volatile("" : "+v"(r));
   return r;
 }
+// v's lane `l` (a constant) := the wave-uniform s; the other lanes keep their value.  One v_writelane_b32 (the compiler has no
+// builtin for it); s comes from an SGPR -- a v_readlane result or scalar arithmetic -- and the lane select is an immediate.
+template <class V>
+__device__ __forceinline__ void lane_put(V& v, V s, int l) {
+  static_assert(sizeof(V) == 4, "one dword");
+  asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(s), "n"(l));
+}
+// base[idx] with the BYTE offset formed in 32 bits: `base[idx]` scales a (sign- or zero-) extended index in 64 bits, and the
+// load takes a 64-bit VGPR address (a shift-add pair per load); a 32-bit byte offset sits next to the SGPR base.
+template <class T>
+__device__ __forceinline__ T ld_u32(const T* __restrict__ base, unsigned idx) {
+  return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + idx * (unsigned)sizeof(T));
+}
 // sum over the 64 lanes, result uniform (read from lane 63 into an SGPR)
 __device__ __forceinline__ float wave_sum(float v) {
   v += dpp_mov<0xB1>(v);        // quad_perm [1,0,3,2]
@@ -196,33 +209,42 @@ __device__ __forceinline__ int fft_wr(int j, int r) {
   const int k = j % NS;
   return (j / NS) * NS * R + k + r * NS;
 }
-template <int NW, int R, int NS>
-__device__ __forceinline__ void fft_pass(float2* buf, const float2* __restrict__ w960, int lane) {
+// NSIG independent signals (buffers at constant distances inside one LDS struct: analysis spectrum X and pitch spectrum P)
+// go through a pass TOGETHER: the twiddles are loaded once, every butterfly index and LDS address is computed once (the
+// second buffer is an immediate offset of the same ds_ instruction), the butterflies of a trip run back to back and
+// the pass has one barrier pair.  Per signal the arithmetic is that of the single form.
+template <int NW, int R, int NS, int NSIG>
+__device__ __forceinline__ void fft_pass_n(float2* const (&bufs)[NSIG], const float2* __restrict__ w960, int lane) {
   constexpr int M = 480 / R;
   constexpr int NBF = (M + WAVE - 1) / WAVE;
-  float2 o[NBF][R];
+  float2 o[NSIG][NBF][R];
   // twiddles of every trip first (clamped butterfly index): one exposed table round trip per pass, not one per trip
-  float2 tw[NBF][R];
+  // (Where NS divides the wave, k = j % NS is the same in every trip and so are the twiddles: one set.)
+  constexpr int NTW = (NS > 1 && WAVE % NS == 0) ? 1 : NBF;
+  float2 tw[NTW][R];
   if (NS > 1) {
 #pragma unroll
-    for (int nb = 0; nb < NBF; ++nb) {
-      const int k = min(lane + WAVE * nb, M - 1) % NS;
+    for (int nb = 0; nb < NTW; ++nb) {
+      const unsigned k = (unsigned)min(lane + WAVE * nb, M - 1) % NS;
 #pragma unroll
-      for (int r = 1; r < R; ++r) tw[nb][r] = w960[k * r * (960 / (NS * R))];
+      for (int r = 1; r < R; ++r) tw[nb][r] = ld_u32(w960, k * (unsigned)(r * (960 / (NS * R))));
     }
   }
 #pragma unroll
   for (int nb = 0; nb < NBF; ++nb) {
     const int j = lane + WAVE * nb;
     if (j < M) {
-      float2 v[R];
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
-        float2 x = buf[fft_rd<R, NS>(j, r)];
-        if (NS > 1 && r > 0) x = cmul(x, tw[nb][r]);
-        v[r] = x;
+      for (int g = 0; g < NSIG; ++g) {
+        float2 v[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          float2 x = bufs[g][fft_rd<R, NS>(j, r)];
+          if (NS > 1 && r > 0) x = cmul(x, tw[NTW == 1 ? 0 : nb][r]);
+          v[r] = x;
+        }
+        butterfly<R>(v, o[g][nb]);
       }
-      butterfly<R>(v, o[nb]);
     }
   }
   rn_sync<NW>();
@@ -231,10 +253,18 @@ __device__ __forceinline__ void fft_pass(float2* buf, const float2* __restrict__
     const int j = lane + WAVE * nb;
     if (j < M) {
 #pragma unroll
-      for (int r = 0; r < R; ++r) buf[fft_wr<R, NS>(j, r)] = o[nb][r];
+      for (int g = 0; g < NSIG; ++g) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) bufs[g][fft_wr<R, NS>(j, r)] = o[g][nb][r];
+      }
     }
   }
   rn_sync<NW>();
+}
+template <int NW, int R, int NS>
+__device__ __forceinline__ void fft_pass(float2* buf, const float2* __restrict__ w960, int lane) {
+  float2* const bufs[1] = {buf};
+  fft_pass_n<NW, R, NS, 1>(bufs, w960, lane);
 }
 
 // forward DFT of the 480 complex points in buf (unscaled, natural order); caller synchronised
@@ -246,21 +276,24 @@ __device__ __forceinline__ void fft480(float2* buf, const float2* __restrict__ w
   fft_pass<NW, 5, 96>(buf, w960, lane);
 }
 
-// The same transform with the first pass (radix 4, stride 1) fed by a loader instead of LDS: in(j, r) returns point
-// j + 120 r.  The analysis transforms window their input straight from global memory this way, which saves the
-// separate "window -> LDS -> barrier -> read back" phase.  buf must be free (caller synchronised).
-template <int NW, class In>
-__device__ __forceinline__ void fft480_from(float2* buf, In in, const float2* __restrict__ w960, int lane) {
+// The same transform with the first pass (radix 4, stride 1) fed by a loader instead of LDS: in(g, j, r) returns point
+// j + 120 r of signal g.  The analysis transforms window their input straight from global memory this way, which saves the
+// separate "window -> LDS -> barrier -> read back" phase.  The buffers must be free (caller synchronised).
+template <int NW, int NSIG, class In>
+__device__ __forceinline__ void fft480_from(float2* const (&bufs)[NSIG], In in, const float2* __restrict__ w960, int lane) {
   {
-    float2 o[2][4];
+    float2 o[NSIG][2][4];
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
       const int j = lane + WAVE * nb;
       if (j < 120) {
-        float2 v[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = in(j, r);
-        butterfly<4>(v, o[nb]);
+        for (int g = 0; g < NSIG; ++g) {
+          float2 v[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = in(g, j, r);
+          butterfly<4>(v, o[g][nb]);
+        }
       }
     }
 #pragma unroll
@@ -268,48 +301,56 @@ __device__ __forceinline__ void fft480_from(float2* buf, In in, const float2* __
       const int j = lane + WAVE * nb;
       if (j < 120) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) buf[fft_wr<4, 1>(j, r)] = o[nb][r];
+        for (int g = 0; g < NSIG; ++g) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) bufs[g][fft_wr<4, 1>(j, r)] = o[g][nb][r];
+        }
       }
     }
     rn_sync<NW>();
   }
-  fft_pass<NW, 8, 4>(buf, w960, lane);
-  fft_pass<NW, 3, 32>(buf, w960, lane);
-  fft_pass<NW, 5, 96>(buf, w960, lane);
+  fft_pass_n<NW, 8, 4, NSIG>(bufs, w960, lane);
+  fft_pass_n<NW, 3, 32, NSIG>(bufs, w960, lane);
+  fft_pass_n<NW, 5, 96, NSIG>(bufs, w960, lane);
 }
 
-// buf holds Z = FFT480(x[2n] + i x[2n+1]); turn it into X[0..480] = DFT960(x)/960 in place.
-template <int NW>
-__device__ __forceinline__ void real_fwd_post(float2* buf, const float2* __restrict__ w960, int lane) {
+// each buf holds Z = FFT480(x[2n] + i x[2n+1]); turn it into X[0..480] = DFT960(x)/960 in place (one set of table values
+// and one barrier for all NSIG buffers).
+template <int NW, int NSIG>
+__device__ __forceinline__ void real_fwd_post(float2* const (&bufs)[NSIG], const float2* __restrict__ w960, int lane) {
   const float scale = 1.0f / 960.0f;
   // table loads of all four trips first (clamped index): inside the `k <= 240` bodies each of them was a load - wait
   float2 wk[4], wn[4];
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
-    const int k = min(lane + WAVE * m, 240);
-    wk[m] = w960[k];
-    wn[m] = w960[480 - k];
+    const unsigned k = (unsigned)min(lane + WAVE * m, 240);
+    wk[m] = ld_u32(w960, k);
+    wn[m] = ld_u32(w960, 480u - k);
   }
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     const int k = lane + WAVE * m;
     if (k <= 240) {
-      const float2 zk = buf[k];
-      const float2 zn = (k == 0) ? zk : buf[480 - k];
-      // X[k]
-      float2 zc = cconj(zn);
-      float2 fe = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y + zc.y));
-      float2 d = make_float2(0.5f * (zk.x - zc.x), 0.5f * (zk.y - zc.y));
-      float2 t = cmul(wk[m], make_float2(d.y, -d.x));
-      const float2 xk = make_float2((fe.x + t.x) * scale, (fe.y + t.y) * scale);
-      // X[480-k]
-      zc = cconj(zk);
-      fe = make_float2(0.5f * (zn.x + zc.x), 0.5f * (zn.y + zc.y));
-      d = make_float2(0.5f * (zn.x - zc.x), 0.5f * (zn.y - zc.y));
-      t = cmul(wn[m], make_float2(d.y, -d.x));
-      const float2 xn = make_float2((fe.x + t.x) * scale, (fe.y + t.y) * scale);
-      buf[k] = xk;
-      buf[480 - k] = xn;
+#pragma unroll
+      for (int g = 0; g < NSIG; ++g) {
+        float2* buf = bufs[g];
+        const float2 zk = buf[k];
+        const float2 zn = (k == 0) ? zk : buf[480 - k];
+        // X[k]
+        float2 zc = cconj(zn);
+        float2 fe = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y + zc.y));
+        float2 d = make_float2(0.5f * (zk.x - zc.x), 0.5f * (zk.y - zc.y));
+        float2 t = cmul(wk[m], make_float2(d.y, -d.x));
+        const float2 xk = make_float2((fe.x + t.x) * scale, (fe.y + t.y) * scale);
+        // X[480-k]
+        zc = cconj(zk);
+        fe = make_float2(0.5f * (zn.x + zc.x), 0.5f * (zn.y + zc.y));
+        d = make_float2(0.5f * (zn.x - zc.x), 0.5f * (zn.y - zc.y));
+        t = cmul(wn[m], make_float2(d.y, -d.x));
+        const float2 xn = make_float2((fe.x + t.x) * scale, (fe.y + t.y) * scale);
+        buf[k] = xk;
+        buf[480 - k] = xn;
+      }
     }
   }
   rn_sync<NW>();
@@ -322,9 +363,9 @@ __device__ __forceinline__ void real_inv_pre(float2* buf, const float2* __restri
   float2 wk[4], wn[4];
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
-    const int k = min(lane + WAVE * m, 240);
-    wk[m] = w960[k];
-    wn[m] = w960[480 - k];
+    const unsigned k = (unsigned)min(lane + WAVE * m, 240);
+    wk[m] = ld_u32(w960, k);
+    wn[m] = ld_u32(w960, 480u - k);
   }
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
@@ -400,14 +441,17 @@ __device__ __forceinline__ float band_sum(const float* part_lo, const float* par
 // the band correlation Re(X P*) against a second spectrum and parks S in global memory from the registers.
 //   E[band]  of S            -> Eout
 //   C[band]  of (Xc, S)      -> Cout   (CORR)
-template <int NW, bool CORR>
+//   E[band]  of Xc           -> Xout   (CORR && XE: the one sweep yields Ex, Ep and Exp -- Xc is read and the band
+//                                       fractions are formed once; the three band sums take turns in `part`)
+template <int NW, bool CORR, bool XE = false>
 __device__ __forceinline__ void band_pairs(const float2* S, const float2* Xc, float* part, float* Eout, float* Cout,
-                                           float2* park, const RnTables* __restrict__ tab, const BandEdges& be,
-                                           int lane) {
+                                           float* Xout, float2* park, const RnTables* __restrict__ tab,
+                                           const BandEdges& be, int lane) {
   float clo[4], chi[4];
+  float xlo[4], xhi[4];
   float2 fr[4];
 #pragma unroll
-  for (int m = 0; m < 4; ++m) fr[m] = *reinterpret_cast<const float2*>(tab->bin_frac + 2 * min(lane + WAVE * m, 199));
+  for (int m = 0; m < 4; ++m) fr[m] = ld_u32(reinterpret_cast<const float2*>(tab->bin_frac), (unsigned)min(lane + WAVE * m, 199));
   // the spectrum pairs of all four trips first (clamped index): inside the `pidx < 200` bodies every trip was an LDS
   // read - wait - use round trip
   float4 svq[4];
@@ -435,6 +479,27 @@ __device__ __forceinline__ void band_pairs(const float2* S, const float2* Xc, fl
         float h2 = f.x * c0 + f.y * c1;
         clo[m] = dpp_add<0xB1>(l2);
         chi[m] = dpp_add<0xB1>(h2);
+        if (XE) {
+          // Every sum of two products here is one rounded product and one fused multiply-add; WHICH of the two is fused
+          // is the compiler's choice under fp-contract, and it decides the last bit of Ex.  When X had a sweep of its
+          // own, the first product was the rounded one in trip 0 and the second one in trips 1 - 3 (the trips with a
+          // clamped index); spelled out, so that the band energies -- and everything behind them -- keep their bits
+          // (tests/test_gpu_rn_frame_bits.py).
+          float x0, x1, l3, h3;
+          if (m == 0) {
+            x0 = fmaf(xv.y, xv.y, xv.x * xv.x);
+            x1 = fmaf(xv.w, xv.w, xv.z * xv.z);
+            l3 = fmaf(1.f - f.y, x1, (1.f - f.x) * x0);
+            h3 = fmaf(f.y, x1, f.x * x0);
+          } else {
+            x0 = fmaf(xv.x, xv.x, xv.y * xv.y);
+            x1 = fmaf(xv.z, xv.z, xv.w * xv.w);
+            l3 = fmaf(1.f - f.x, x0, (1.f - f.y) * x1);
+            h3 = fmaf(f.x, x0, f.y * x1);
+          }
+          xlo[m] = dpp_add<0xB1>(l3);
+          xhi[m] = dpp_add<0xB1>(h3);
+        }
         if (park) *reinterpret_cast<float4*>(park + 2 * pidx) = sv;
       }
     }
@@ -453,6 +518,14 @@ __device__ __forceinline__ void band_pairs(const float2* S, const float2* Xc, fl
       if (pidx < 200 && (lane & 1) == 0) { part[pidx >> 1] = clo[m]; part[100 + (pidx >> 1)] = chi[m]; }
     }
     band_total(Cout);
+    if (XE) {
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        const int pidx = lane + WAVE * m;
+        if (pidx < 200 && (lane & 1) == 0) { part[pidx >> 1] = xlo[m]; part[100 + (pidx >> 1)] = xhi[m]; }
+      }
+      band_total(Xout);
+    }
   }
 }
 
@@ -468,7 +541,7 @@ struct TansigTab {
   float t[4];
   __device__ __forceinline__ void load(const float* __restrict__ table, int lane) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) t[q] = table[min(64 * q + lane, 200)];
+    for (int q = 0; q < 4; ++q) t[q] = ld_u32(table, (unsigned)min(64 * q + lane, 200));
   }
   __device__ __forceinline__ float at(int i) const {
     const int addr = (i & 63) << 2;
@@ -717,7 +790,7 @@ __device__ __forceinline__ void gru_layer_i(__amdgpu_buffer_rsrc_t rs, int w_off
 #pragma unroll
     for (int r = 0; r < NRZ; ++r) {
       rows[r] = min(lane + WAVE * r, 2 * N - 1);
-      acc[r] = bias[rows[r]];
+      acc[r] = ld_u32(bias, (unsigned)rows[r]);
     }
     dotn_i<MK16, NK16, ROWS, NRZ>(rs, w_off, u_off, rows, in_img, st_img, toff, sin, sst.dn, acc);
 #pragma unroll
@@ -737,7 +810,7 @@ __device__ __forceinline__ void gru_layer_i(__amdgpu_buffer_rsrc_t rs, int w_off
 #pragma unroll
     for (int r = 0; r < NRC; ++r) {
       rows[r] = 2 * N + min(lane + WAVE * r, N - 1);
-      acc[r] = bias[rows[r]];
+      acc[r] = ld_u32(bias, (unsigned)rows[r]);
     }
     dotn_i<MK16, NK16, ROWS, NRC>(rs, w_off, u_off, rows, in_img, st_img, toff, sin, sst.dn, acc);
 #pragma unroll
@@ -830,17 +903,22 @@ __device__ __forceinline__ Cand wave_best(Cand c) {
 }
 
 // Inner products of x[0, 480) with NL lagged windows of the same LDS buffer, reduced over the wave:
-// sxy[q] = sum_j x[j] y_q[j], and with SQ also syy[q] = sum_j y_q[j]^2.  xr / yr[q] already include the lane
+// sxy[q] = sum_j x[j] y_q[j], and with SQ also syy[q] = sum_j y_q[j]^2.  xv / yr[q] already include the lane
 // offset, so every read is one ds_read_b32 with an immediate offset (64 m); the NL (or 2 NL) accumulation chains
 // and their DPP reductions are independent, which is what hides the LDS and cross-lane latencies -- the loops
 // these replace did one dependent wave reduction per lag.
 typedef float rn_f2 __attribute__((ext_vector_type(2)));
-template <int NL, bool SQ>
-__device__ __forceinline__ void lag_dots(const float* xr, const float* const (&yr)[NL], int lane, float (&sxy)[NL],
-                                         float (&syy)[NL]) {
-  float xv[8];
+// The x window is the same for every call of a frame (fine search and remove_doubling: x = lp + 384), so the caller
+// loads it once (lag_window) and hands the registers to each call: 8 LDS reads per frame instead of 8 per call.
+__device__ __forceinline__ void lag_window(const float* xr, int lane, float (&xv)[8]) {
 #pragma unroll
   for (int m = 0; m < 7; ++m) xv[m] = xr[WAVE * m];
+  xv[7] = 0.f;
+  if (lane < 32) xv[7] = xr[WAVE * 7];   // j = 448 + lane < 480
+}
+template <int NL, bool SQ>
+__device__ __forceinline__ void lag_dots(const float (&xv)[8], const float* const (&yr)[NL], int lane, float (&sxy)[NL],
+                                         float (&syy)[NL]) {
 #pragma unroll
   for (int q = 0; q < NL; ++q) { sxy[q] = 0.f; syy[q] = 0.f; }
 #pragma unroll
@@ -853,7 +931,6 @@ __device__ __forceinline__ void lag_dots(const float* xr, const float* const (&y
     }
   }
   if (lane < 32) {   // j = 448 + lane < 480
-    xv[7] = xr[WAVE * 7];
 #pragma unroll
     for (int q = 0; q < NL; ++q) {
       const float y = yr[q][WAVE * 7];
@@ -993,13 +1070,16 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
       {
         // all 14 x 2 window loads of a lane are requested before the first one is used (a `for (i = lane; ...)` loop
         // with the bound test in it compiled to load - wait - load - wait per trip: 27 exposed round trips per frame)
+        // (one per-lane base, the trips as immediate offsets -- 512 bytes apart; only the last trip needs its clamp:
+        // lane + 64 k <= 863 for k < 13)
         float2 v[14];
         float x0[14];
+        const float* pbl = pb + 2u * (unsigned)lane;
   #pragma unroll
         for (int k = 0; k < 14; ++k) {
-          const int i = min(lane + WAVE * k, 863);
-          v[k] = *reinterpret_cast<const float2*>(pb + 2 * i);
-          x0[k] = pb[2 * i - 1];                      // i = 0 reads the (valid) sample before the buffer, zeroed below
+          const float* pk = k < 13 ? pbl + 2 * WAVE * k : pb + 2u * (unsigned)min(lane + WAVE * k, 863);
+          v[k] = *reinterpret_cast<const float2*>(pk);
+          x0[k] = pk[-1];                             // i = 0 reads the (valid) sample before the buffer, zeroed below
         }
   #pragma unroll
         for (int k = 0; k < 14; ++k) {
@@ -1194,11 +1274,17 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
         else if (total_valid == 1) { best0 = w0.idx; best1 = 0; }
         else { best0 = w0.idx; best1 = w1.idx; }
       }
+      // wave_best hands every lane the same winners, but through ds_bpermute: as vector values the ten fine lags, their
+      // range tests and later T0 and the candidate lags of remove_doubling were computed in every lane.  From here the
+      // lag arithmetic runs on the scalar unit; per lag only `lane + scalar offset` is left.
+      best0 = __builtin_amdgcn_readfirstlane(best0);
+      best1 = __builtin_amdgcn_readfirstlane(best1);
       rn_sync<NW>();
       STAMP(2)
 
       // ---- 3. fine search at half rate around the two coarse candidates ----
       float* fine = Sa;  // 294 (+2 guard) correlation values, zero where not evaluated
+      float xwin[8];     // x[lane + 64 m] of x = lp + 384: the fixed operand of every lag product of stages 3 and 4
       for (int i = lane; i < 296; i += WAVE) fine[i] = 0.f;
       rn_sync<NW>();
       {
@@ -1218,7 +1304,8 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
           yr[q] = lp + lagi[q] + lane;
         }
         float sxy[10], syy[10];
-        lag_dots<10, true>(lp + 384 + lane, yr, lane, sxy, syy);
+        lag_window(lp + 384 + lane, lane, xwin);
+        lag_dots<10, true>(xwin, yr, lane, sxy, syy);
   #pragma unroll
         for (int q = 0; q < 10; ++q) {
           if (use[q]) {
@@ -1240,7 +1327,7 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
           if ((fc - fa) > .7f * (fb - fa)) offset = 1;
           else if ((fa - fc) > .7f * (fb - fc)) offset = -1;
         }
-        pitch_index = 768 - (2 * bp - offset);
+        pitch_index = __builtin_amdgcn_readfirstlane(768 - (2 * bp - offset));   // (offset comes from LDS reads: uniform, but a vector value)
       }
       rn_sync<NW>();
       STAMP(3)
@@ -1264,7 +1351,7 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
         {
           const float* yr[2] = {x + lane, x - T0 + lane};
           float sa[2], sb[2];
-          lag_dots<2, false>(x + lane, yr, lane, sa, sb);
+          lag_dots<2, false>(xwin, yr, lane, sa, sb);
           xx = sa[0];
           xy = sa[1];
         }
@@ -1300,10 +1387,17 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
         // (eight lags) with independent accumulation chains and reductions; T1 falls with k, so the reference's
         // `break` at T1 < 30 is a prefix: a chunk is skipped when its first k is already out, and the sequential
         // threshold logic below runs on the stored sums.
-        float xyk_[14], yyk_[14];
-        int T1_[14];
+        // Candidate k belongs to lane k - 2 (see below).  Its two lag products and its two lags are wave-uniform scalars
+        // when a chunk has reduced them, so they are dropped into that lane with v_writelane -- four per candidate --
+        // and the lane forms xy, yy and reads yy_lookup itself.  (As 14 x 3 uniform values picked with a
+        // `lane == k - 2 ? ... : ...` chain this was 42 selects, 14 compares and 28 scalar-addressed LDS reads.)
+        // Lanes that no chunk wrote keep lag 0, which fails the T1 >= 30 test.
+        int t1v = 0, t1bv = 0;
+        float xya = 0.f, xyb = 0.f;
+        // (k = 14, 15 can never pass: T0 <= 383 gives (2 T0 + 14) / 28 <= 27 < 30, the reference's `break` -- no fourth chunk)
+        static_assert((2 * 383 + 14) / (2 * 14) < 30, "candidates k >= 14 are out of range for every T0");
   #pragma unroll
-        for (int c = 0; c < 4; ++c) {
+        for (int c = 0; c < 3; ++c) {
           const int k0 = 2 + 4 * c;
           if ((2 * T0 + k0) / (2 * k0) >= 30) {
             constexpr int NKC = 4;
@@ -1313,31 +1407,25 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
             for (int q = 0; q < NKC; ++q) {
               const int k = k0 + q;
               t1[q] = 0; t1b[q] = 0;
-              if (k <= 15) {
-                const int T1 = (2 * T0 + k) / (2 * k);
-                if (T1 >= 30) {
-                  t1[q] = T1;
-                  if (k == 2) t1b[q] = (T1 + T0 > 384) ? T0 : T0 + T1;
-                  else t1b[q] = (2 * c_second_check[k] * T0 + k) / (2 * k);
-                }
+              const int T1 = (2 * T0 + k) / (2 * k);
+              if (T1 >= 30) {
+                t1[q] = T1;
+                if (k == 2) t1b[q] = (T1 + T0 > 384) ? T0 : T0 + T1;
+                else t1b[q] = (2 * c_second_check[k] * T0 + k) / (2 * k);
               }
               yr[2 * q] = x - t1[q] + lane;
               yr[2 * q + 1] = x - t1b[q] + lane;
             }
             float sa[2 * NKC], sb[2 * NKC];
-            lag_dots<2 * NKC, false>(x + lane, yr, lane, sa, sb);
+            lag_dots<2 * NKC, false>(xwin, yr, lane, sa, sb);
   #pragma unroll
             for (int q = 0; q < NKC; ++q) {
-              if (k0 + q <= 15) {
-                T1_[k0 + q - 2] = t1[q];
-                xyk_[k0 + q - 2] = .5f * (sa[2 * q] + sa[2 * q + 1]);
-                yyk_[k0 + q - 2] = .5f * (yyl[t1[q]] + yyl[t1b[q]]);
-              }
+              const int l = k0 + q - 2;
+              lane_put(t1v, t1[q], l);
+              lane_put(t1bv, t1b[q], l);
+              lane_put(xya, sa[2 * q], l);
+              lane_put(xyb, sa[2 * q + 1], l);
             }
-          } else {
-  #pragma unroll
-            for (int q = 0; q < 4; ++q)
-              if (k0 + q <= 15) { T1_[k0 + q - 2] = 0; xyk_[k0 + q - 2] = 0.f; yyk_[k0 + q - 2] = 0.f; }
           }
         }
         // The threshold test of candidate k depends on k, T0, g0 and the previous frame only, never on the running best,
@@ -1345,15 +1433,9 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
         // and one division per lane instead of fourteen of each in every lane, one after the other) and the highest
         // passing lane wins.  Same operations per candidate, bit-identical decisions.
         {
-          int T1 = 0;
-          float xyk = 0.f, yyk = 0.f;
-  #pragma unroll
-          for (int k = 2; k <= 15; ++k) {
-            const bool mine = lane == k - 2;
-            T1 = mine ? T1_[k - 2] : T1;
-            xyk = mine ? xyk_[k - 2] : xyk;
-            yyk = mine ? yyk_[k - 2] : yyk;
-          }
+          const int T1 = t1v;
+          const float xyk = .5f * (xya + xyb);
+          const float yyk = .5f * (yyl[t1v] + yyl[t1bv]);
           const int k = lane + 2;
           const float g1 = xyk / sqrtf(1.f + xx * yyk);
           float cont;
@@ -1378,7 +1460,7 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
         {
           const float* yr[3] = {x - (T - 1) + lane, x - T + lane, x - (T + 1) + lane};
           float sb[3];
-          lag_dots<3, false>(x + lane, yr, lane, xc3, sb);
+          lag_dots<3, false>(xwin, yr, lane, xc3, sb);
         }
         int offset = 0;
         if ((xc3[2] - xc3[0]) > .7f * (xc3[1] - xc3[0])) offset = 1;
@@ -1405,50 +1487,37 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
       asm volatile("" : "+v"(lane));
       RN_LANE_RANGE(5);
 
-      // ---- 5. frame_analysis: window, 960-point real FFT (in A), band energies (partials in Bb) ----
+      // ---- 5. frame_analysis and pitch frame together: window, two 960-point real FFTs (X in A, P in Bb) ----
+      // pitch_index is known before X's transform starts, A and Bb are different buffers, and lp and the pitch scratch are
+      // dead by now: nothing orders the two transforms, so they share every pass (fft_pass_n).
       // complex point n = (x[2n], x[2n+1]) times the window; points >= 240 sit in the mirrored half of the window
-      fft480_from<NW>(SL.A, [&](int j, int r) {
-        const int n = j + 120 * r;
-        const float2 v = *reinterpret_cast<const float2*>(xw + 2 * n);
-        const float w0 = r < 2 ? hw[2 * n] : hw[959 - 2 * n];
-        const float w1 = r < 2 ? hw[2 * n + 1] : hw[958 - 2 * n];
-        return make_float2(v.x * w0, v.y * w1);
-      }, w960, lane);
-      real_fwd_post<NW>(SL.A, w960, lane);
-      STAMP(5)
-      band_pairs<NW, false>(SL.A, nullptr, Rb, SL.Ex, nullptr, nullptr, tab, be, lane);
-      STAMP(6)
-      lane = lane0;
-      asm volatile("" : "+v"(lane));
-      RN_LANE_RANGE(6);
-      if (DBG && a.dbg && t == a.T - 1) {
-        float* D = a.dbg + (long)b * RN_DBG_FLOATS;
-        for (int i = lane; i < 962; i += WAVE) D[0 + i] = Xf[i];
-        if (lane < RN_NB) D[962 + lane] = SL.Ex[lane];
-      }
-
-      // ---- 6. pitch frame: window, FFT (in Bb), band energy / correlation (partials in U) ----
       {
         const float* pp = pb + (768 - pitch_index);
-        fft480_from<NW>(SL.Bb, [&](int j, int r) {
+        float2* const xp[2] = {SL.A, SL.Bb};
+        fft480_from<NW, 2>(xp, [&](int g, int j, int r) {
           const int n = j + 120 * r;
           const float w0 = r < 2 ? hw[2 * n] : hw[959 - 2 * n];
           const float w1 = r < 2 ? hw[2 * n + 1] : hw[958 - 2 * n];
-          return make_float2(pp[2 * n] * w0, pp[2 * n + 1] * w1);
+          if (g == 0) {
+            const float2 v = *reinterpret_cast<const float2*>(xw + 2 * n);
+            return make_float2(v.x * w0, v.y * w1);
+          }
+          return make_float2(pp[2 * n] * w0, pp[2 * n + 1] * w1);     // (pp is only 4-byte aligned)
         }, w960, lane);
+        real_fwd_post<NW, 2>(xp, w960, lane);
       }
-      real_fwd_post<NW>(SL.Bb, w960, lane);
-      STAMP(7)
-      // band energy of P, band correlation with X, and P parked in L2 from the same registers (read back by the comb
-      // filter, which needs bins < 400 only); Bb becomes the RNN workspace
-      band_pairs<NW, true>(SL.Bb, SL.A, SL.U, SL.Ep, SL.Exp, nullptr, tab, be, lane);
+      STAMP(5)
+      // ---- 6. band energies of X and P and their band correlation from one sweep (partials in U) ----
+      // Bb becomes the RNN workspace afterwards: the comb filter needs P's bins < 400 only
+      band_pairs<NW, true, true>(SL.Bb, SL.A, SL.U, SL.Ep, SL.Exp, SL.Ex, nullptr, tab, be, lane);
       if (DBG && a.dbg && t == a.T - 1) {
         float* D = a.dbg + (long)b * RN_DBG_FLOATS;
         const float* Pf = reinterpret_cast<const float*>(SL.Bb);
-        for (int i = lane; i < 962; i += WAVE) D[1856 + i] = Pf[i];
+        for (int i = lane; i < 962; i += WAVE) { D[0 + i] = Xf[i]; D[1856 + i] = Pf[i]; }
+        if (lane < RN_NB) D[962 + lane] = SL.Ex[lane];
       }
       rn_sync<NW>();
-      STAMP(8)
+      STAMP(6)
       lane = lane0;
       asm volatile("" : "+v"(lane));
       RN_LANE_RANGE(7);
@@ -1550,7 +1619,7 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
           if (lane == 0) Rb[KB_FEAT + 41] = sv / 8.f - 2.1f;
         }
         rn_sync<NW>();
-        STAMP(9)
+        STAMP(7)
       }
       if constexpr (NW > 1) {
         if (lane == 0) { SL.pitch_index = pitch_index; SL.pitch_gain = pitch_gain; SL.silence = silence ? 1 : 0; }
@@ -1603,10 +1672,10 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
           return i < 24 ? dense[i] : (i < 48 ? L.rnn_state[i - 24] : (i < 90 ? feat[i - 48] : 0.f)); });
         rn_sync<NW>();
         vad_prob = SL.U[U_VAD];
-        STAMP(10)
+        STAMP(8)
         gru_layer_i<NW, 90, 48>(wrs, RnPack8::NG_W, RnPack8::NG_R, wpf + RnPack::NG_B, in_img, sc.dn,
                             L.rnn_state + 24, zbuf, st_img, toff, tansig, lane);
-        STAMP(11)
+        STAMP(9)
         sc = image_i8<128>(in_img, lane, [&](int i) { return i < 72 ? L.rnn_state[i] : (i < 114 ? feat[i - 72] : 0.f); });
         rn_sync<NW>();
         gru_layer_i<NW, 114, 96>(wrs, RnPack8::DG_W, RnPack8::DG_R, wpf + RnPack::DG_B, in_img, sc.dn,
@@ -1620,7 +1689,7 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
           if (lane < RN_NB) SL.U[U_G + lane] = gv;
         }
         rn_sync<NW>();
-        STAMP(12)
+        STAMP(10)
 
         lane = lane0;
         asm volatile("" : "+v"(lane));
@@ -1636,10 +1705,10 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
           float4 pq[4];
   #pragma unroll
           for (int m = 0; m < 4; ++m) {       // parked pitch spectrum and the per-bin tables: issued before r is ready
-            const int pidx = min(lane + WAVE * m, 199);
+            const unsigned pidx = (unsigned)min(lane + WAVE * m, 199);
             pq[m] = *reinterpret_cast<const float4*>(SL.Bb + 2 * pidx);
-            fq[m] = *reinterpret_cast<const float2*>(tab->bin_frac + 2 * pidx);
-            bq[m] = tab->bin_band[2 * pidx];
+            fq[m] = ld_u32(reinterpret_cast<const float2*>(tab->bin_frac), pidx);
+            bq[m] = ld_u32(tab->bin_band, 2 * pidx);
           }
           if (lane < RN_NB) {
             const float ex = SL.Exp[lane], gg = SL.U[U_G + lane];
@@ -1717,7 +1786,7 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
         for (int i = 400 + lane; i < RN_NFREQ; i += WAVE) SL.A[i] = make_float2(0.f, 0.f);   // above 20 kHz
         rn_sync<NW>();
       }
-      STAMP(13)
+      STAMP(11)
 
       // ---- taps / debug ----
       if (DBG && a.taps) {
@@ -1745,15 +1814,15 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
       // ---- 10. frame_synthesis: inverse FFT, window, overlap-add ----
       real_inv_pre<NW>(SL.A, w960, lane);
       fft480<NW>(SL.A, w960, lane);
-      STAMP(14)
+      STAMP(12)
       {
         float* o = a.out + (long)t * a.stride_t + (long)b * a.stride_b;
         float2 hwa[4], hwb[4];                  // window values of all four trips, requested together
   #pragma unroll
         for (int m = 0; m < 4; ++m) {
-          const int n = min(lane + WAVE * m, 239);
-          hwa[m] = *reinterpret_cast<const float2*>(hw + 2 * n);          // hw[i0], hw[i1]
-          hwb[m] = *reinterpret_cast<const float2*>(hw + 478 - 2 * n);    // hw[479 - i1], hw[479 - i0]
+          const unsigned n = (unsigned)min(lane + WAVE * m, 239);
+          hwa[m] = ld_u32(reinterpret_cast<const float2*>(hw), n);          // hw[i0], hw[i1]
+          hwb[m] = ld_u32(reinterpret_cast<const float2*>(hw), 239u - n);   // hw[479 - i1], hw[479 - i0]
         }
   #pragma unroll
         for (int m = 0; m < 4; ++m) {
@@ -1783,7 +1852,7 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
         }
       }
       rn_sync<NW>();
-      STAMP(15)
+      STAMP(13)
     }
     }      // this wave has a frame in this tick
     if constexpr (NW > 1) __syncthreads();

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/lds_stage
 mkdir -p $out
-for k in 0 1 2 3 4 5 6 7 8 9 10 11 12 13 14 full; do
+for k in 0 1 2 3 4 5 6 7 8 9 10 11 12 full; do
   lib=$PWD/crispy_amd/csrc/build/variants/lib_stop$k.so
   [ "$k" = full ] && lib=$PWD/crispy_amd/libcrispy_hip.so
   i=0
@@ -20,11 +20,11 @@ python3 - "$out" <<'PY'
 import csv, glob, os, sys
 out = sys.argv[1]
 names = ["0 downsample+lpc+fir", "1 pack+coarse xcorr", "2 Syy prefix+top2", "3 fine search", "4 remove_doubling",
-         "5 X window+fft+post", "6 band Ex", "7 P window+fft+post", "8 band Ep/Exp", "9 features",
-         "10 dense+vad gru", "11 noise gru", "12 denoise gru+out", "13 pitch filter+gains", "14 inverse fft", "15 OLA+store"]
+         "5 X, P window+fft+post", "6 bands Ex/Ep/Exp", "7 features",
+         "8 dense+vad gru", "9 noise gru", "10 denoise gru+out", "11 pitch filter+gains", "12 inverse fft", "13 OLA+store"]
 n_sf = 4096 * 25 * 2
 tot = {}
-for k in list(range(15)) + ["full"]:
+for k in list(range(13)) + ["full"]:
     acc = {}
     for f in glob.glob(os.path.join(out, f"s{k}_*", "**", "*counter_collection.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
@@ -35,7 +35,7 @@ cs = ["SQ_INSTS_VALU", "SQ_INSTS_LDS", "SQ_ACTIVE_INST_LDS", "SQ_LDS_BANK_CONFLI
 print("per stream-frame; LDS-active / conflicts / waits / wave cycles in quad-cycles")
 print(f"{'stage':26s} " + " ".join(f"{c[3:]:>18s}" for c in cs))
 prev = {c: 0.0 for c in cs}
-for i, k in enumerate(list(range(15)) + ["full"]):
+for i, k in enumerate(list(range(13)) + ["full"]):
     cur = tot.get(k, {})
     print(f"{names[i]:26s} " + " ".join(f"{cur.get(c, 0) - prev[c]:18.1f}" for c in cs))
     prev = {c: cur.get(c, 0) for c in cs}

@@ -9,8 +9,8 @@ from crispy_amd import synthetic_weights, synth_audio
 from crispy_amd.denoise import DenoiseState
 B = int(os.environ.get("B", 1024)); T = int(os.environ.get("T", 50))
 names = ["0 downsample+lpc+fir", "1 pack+coarse xcorr", "2 Syy prefix+top2", "3 fine search", "4 remove_doubling",
-         "5 X window+fft+post", "6 band Ex", "7 P window+fft+post", "8 band Ep/Exp+park P", "9 features",
-         "10 dense+vad gru", "11 noise gru", "12 denoise gru+out", "13 pitch filter+gains", "14 taps+inverse fft", "15 OLA+store"]
+         "5 X, P window+fft+post", "6 bands Ex/Ep/Exp", "7 features",
+         "8 dense+vad gru", "9 noise gru", "10 denoise gru+out", "11 pitch filter+gains", "12 taps+inverse fft", "13 OLA+store"]
 ds = DenoiseState(synthetic_weights(0), B, 0)
 ds.debug_capture(True)
 x = synth_audio.batch_torch(B, T, torch.device("cuda:0")); y = torch.empty_like(x)
