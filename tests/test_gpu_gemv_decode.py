@@ -9,7 +9,8 @@ LayerNorm computed in the consumer, 8 launches per layer instead of 11 (VERDICT 
  * a resident quantised engine == the same file inflated at load, ids and picked-logit BYTES (same instructions behind the
    weight fetch), for every ggml type the catalog uses;
  * a row's bits do not depend on the rows it shares a step with: 1 row == row 2 of 3, and == the row in batches of 6, 37 and
-   130 (wide steps take the rows four at a time through the same kernels)."""
+   130 (wide steps take the rows four at a time through the same kernels).
+Contexts beyond these 14 positions (every key class up to position 447) and rows with unequal prompts: tests/test_gpu_gemv_long.py."""
 import numpy as np
 import pytest
 
