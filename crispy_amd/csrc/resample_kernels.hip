@@ -17,6 +17,15 @@
 namespace crispy {
 namespace {
 
+// The hand-off in front of the operator, as the reference computes it: wav_s16 >= 1 `f32::clamp(-1, 1)` (audio.rs:272: a NaN
+// stays a NaN), wav_s16 >= 2 `(x.clamp(-1.0, 1.0) * 32767.0) as i16` read back / 32768 (recording.rs:109-110: Rust's `as`
+// truncates toward zero and makes a NaN 0).  fminf / fmaxf would turn a NaN into -1: a full-scale click.
+__device__ __forceinline__ float rs_handoff(float v, int wav_s16) {
+  if (wav_s16 >= 1) v = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);
+  if (wav_s16 >= 2) v = v != v ? 0.f : truncf(v * 32767.f) / 32768.f;
+  return v;
+}
+
 __global__ __launch_bounds__(256) void rs_prep_kernel(const float* __restrict__ in, long in_stride, long n_in,
                                                       float scale, int wav_s16, float* __restrict__ A, int n_blk) {
   const long row = blockIdx.x;            // b * n_blk + blk
@@ -26,9 +35,7 @@ __global__ __launch_bounds__(256) void rs_prep_kernel(const float* __restrict__ 
   for (int j = threadIdx.x; j < RS_K; j += 256) {
     float v = 0.f;
     if (j < RS_FFT_IN && (long)blk * RS_FFT_IN + j < n_in) {
-      v = x[j] * scale;
-      if (wav_s16 >= 1) v = fminf(1.f, fmaxf(-1.f, v));          // adapter clamp (audio.rs:272)
-      if (wav_s16 >= 2) v = truncf(v * 32767.f) / 32768.f;        // WavWriter s16 truncation, read back /32768
+      v = rs_handoff(x[j] * scale, wav_s16);
     }
     a[j] = v;
   }
@@ -70,9 +77,7 @@ __global__ __launch_bounds__(256) void rs_prep_split_kernel(const float* __restr
     const int j = j0 + e;
     float v = 0.f;
     if (blk >= 0 && j < RS_FFT_IN && (long)blk * RS_FFT_IN + j < n_in) {
-      v = x[j] * scale;
-      if (wav_s16 >= 1) v = fminf(1.f, fmaxf(-1.f, v));
-      if (wav_s16 >= 2) v = truncf(v * 32767.f) / 32768.f;
+      v = rs_handoff(x[j] * scale, wav_s16);
     }
     const _Float16 h = (_Float16)v;
     hi[e] = h;

@@ -825,6 +825,8 @@ long crispy_resampler_out_len(long n_in);
 /* DEVICE pointers: d_in [batch][in_stride] (n_in valid samples each), d_out [batch][out_stride].
  * Every input sample is multiplied by `scale` first (1/32768 after the denoiser).  wav_s16: 0 = nothing
  * else, 1 = clamp(-1,1) (audio.rs:272), 2 = clamp, x32767 truncated to s16, /32768 (the WAV hand-off).
+ * A NaN sample is treated as the reference treats it: mode 2 reads it as 0 (Rust's `as i16`), modes 0 and 1 keep it
+ * (f32::clamp), and it makes NaN of the 684 outputs its 1026-sample block feeds (its own 342 and the next block's 342).
  * Enqueued on hip_stream (NULL = own stream). */
 int crispy_resampler_process_device(crispy_resampler *h, const float *d_in, long in_stride, long n_in,
                                     int batch, float scale, int wav_s16, float *d_out,

@@ -35,14 +35,31 @@ def filter_spectrum() -> np.ndarray:
     return np.fft.rfft(ft)
 
 
+def operator_g() -> np.ndarray:
+    """The block operator as a circulant, float64: output n of a block's 684 (342 own + 342 of overlap) is
+    sum_j g[(3 n - j) mod 2052] x[j] -- the inverse transform of the 342 kept bins of filter_spectrum() on the 2052 circle."""
+    F = filter_spectrum()
+    k = np.arange(1, FFT_OUT)
+    m = np.arange(2 * FFT_IN)
+    return F[0].real + 2 * np.real((F[1:FFT_OUT][None, :] * np.exp(2j * np.pi * np.outer(m, k) / (2 * FFT_IN))).sum(1))
+
+
 def wav_s16_roundtrip(x: np.ndarray) -> np.ndarray:
-    """f32 in +-1 -> s16 as WavWriter stores it (truncation toward zero) -> f32 as run_transcription reads it."""
-    q = np.trunc(np.clip(x.astype(np.float32), -1.0, 1.0) * np.float32(32767.0)).astype(np.int16)
+    """f32 in +-1 -> s16 as WavWriter stores it (truncation toward zero; Rust's `as i16` makes a NaN 0) -> f32 as
+    run_transcription reads it."""
+    x = np.asarray(x, dtype=np.float32)
+    nan = np.isnan(x)
+    q = np.trunc(np.clip(np.where(nan, np.float32(0.0), x), -1.0, 1.0) * np.float32(32767.0)).astype(np.int16)
     return q.astype(np.float32) / np.float32(32768.0)
 
 
 def resample_48k_to_16k(x: np.ndarray) -> np.ndarray:
     """One stream: 48 kHz f32 -> 16 kHz f32 exactly as the reference's chunk loop would produce it."""
+    return resample_48k_to_16k_f64(x).astype(np.float32)
+
+
+def resample_48k_to_16k_f64(x: np.ndarray) -> np.ndarray:
+    """resample_48k_to_16k before its final rounding: the float64 result, for comparisons finer than an f32 ulp."""
     x = np.asarray(x, dtype=np.float64)
     n_pad = -(-x.size // CHUNK) * CHUNK          # last chunk zero-padded to 1024
     xp = np.zeros(n_pad)
@@ -60,4 +77,4 @@ def resample_48k_to_16k(x: np.ndarray) -> np.ndarray:
         y = np.fft.irfft(o, 2 * FFT_OUT) * (2 * FFT_OUT)      # realfft's inverse is unnormalised
         out[b * FFT_OUT:(b + 1) * FFT_OUT] = y[:FFT_OUT] + overlap
         overlap = y[FFT_OUT:]
-    return out.astype(np.float32)
+    return out

@@ -22,9 +22,8 @@ def test_fft_block_equals_circulant_operator():
     """The GPU applies each block as a GEMM with g[(3n - j) mod 2052]; same operator as the FFT route."""
     from oracle import resample_oracle as R
     F = R.filter_spectrum()
-    k = np.arange(1, 342)
-    m = np.arange(2052)
-    g = F[0].real + 2 * np.real((F[1:342][None, :] * np.exp(2j * np.pi * np.outer(m, k) / 2052)).sum(1))
+    g = R.operator_g()
+    assert g.shape == (2052,) and g.dtype == np.float64
     blk = np.random.default_rng(0).standard_normal(1026)
     M = g[(3 * np.arange(684)[:, None] - np.arange(1026)[None, :]) % 2052]
     buf = np.zeros(2052)
@@ -100,3 +99,119 @@ def test_out_len_formula_matches_the_chunk_loop():
         assert N.lib().crispy_resampler_out_len(n) == want
         if n <= 48000:
             assert R.resample_48k_to_16k(np.zeros(n, np.float32)).size == want
+
+
+def test_operator_g_columns_are_the_fft_routes_impulse_responses():
+    """operator_g against the FFT route at 1e-12, coefficient by coefficient: column j of the circulant is what the FFT
+    route makes of a unit impulse at j -- first, last and middle columns, and through the whole chunk loop (own-block rows,
+    overlap rows, the never-flushed tail) as tests/resample_cases.py builds its impulse expectations."""
+    from oracle import resample_oracle as R
+    from tests import resample_cases as RC
+    g = R.operator_g()
+    F = R.filter_spectrum()
+    for j in (0, 1, 341, 342, 512, 513, 1023, 1025):
+        buf = np.zeros(2052)
+        buf[j] = 1.0
+        o = np.zeros(343, complex)
+        o[:342] = (np.fft.rfft(buf) * F)[:342]
+        assert np.abs(g[(3 * np.arange(684) - j) % 2052] - np.fft.irfft(o, 684) * 684).max() < 1e-12, j
+    for pos in RC.IMPULSE_POS:
+        x = np.zeros(RC.IMPULSE_N_IN)
+        x[pos] = 1.0
+        assert np.abs(RC.impulse_expected(pos) - R.resample_48k_to_16k_f64(x)).max() < 1e-12, pos
+    # what the one absolute bar of the other oracle comparisons cannot see (the figures the edge tests were written for)
+    assert abs(np.abs(g).max() - 0.3285) < 1e-4 and 0.15 < (np.abs(g) < 1e-5).mean() < 0.18
+    assert 0.75 < (np.abs(g) < 2.0 ** -14).mean() < 0.80
+
+
+def test_float64_path_rounds_to_the_float32_output_bit_for_bit():
+    """resample_48k_to_16k_f64 is resample_48k_to_16k before its rounding.  The loop below is the float32 function as it
+    stood before the float64 path existed, restated, so that the default return cannot drift."""
+    from oracle import resample_oracle as R
+
+    def before(x):
+        x = np.asarray(x, dtype=np.float64)
+        n_pad = -(-x.size // 1024) * 1024
+        xp = np.zeros(n_pad)
+        xp[:x.size] = x
+        n_blk = n_pad // 1026
+        F = R.filter_spectrum()
+        out = np.zeros(n_blk * 342)
+        overlap = np.zeros(342)
+        for b in range(n_blk):
+            buf = np.zeros(2052)
+            buf[:1026] = xp[b * 1026:(b + 1) * 1026]
+            o = np.zeros(343, dtype=complex)
+            o[:342] = (np.fft.rfft(buf) * F)[:342]
+            y = np.fft.irfft(o, 684) * 684
+            out[b * 342:(b + 1) * 342] = y[:342] + overlap
+            overlap = y[342:]
+        return out.astype(np.float32)
+
+    rng = np.random.default_rng(8)
+    for n in (1, 1025, 4096, 48000 + 777):
+        x = (0.3 * rng.standard_normal(n)).astype(np.float32)
+        y32, y64 = R.resample_48k_to_16k(x), R.resample_48k_to_16k_f64(x)
+        assert y32.dtype == np.float32 and y64.dtype == np.float64 and y32.shape == y64.shape
+        assert y32.tobytes() == before(x).tobytes() == y64.astype(np.float32).tobytes(), n
+
+
+def test_wav_s16_roundtrip_reads_a_nan_as_zero():
+    """recording.rs:109-110: `(x.clamp(-1.0, 1.0) * 32767.0) as i16` -- f32::clamp keeps a NaN, `as i16` makes it 0."""
+    from oracle import resample_oracle as R
+    x = np.array([np.nan, 0.25, -np.nan, np.inf, -np.inf, -0.0], np.float32)
+    with np.errstate(all="raise"):                 # no undefined NaN -> int16 cast on the way
+        y = R.wav_s16_roundtrip(x)
+    assert y.dtype == np.float32
+    assert (y * 32768).astype(np.int32).tolist() == [0, 8191, 0, 32767, -32767, 0]
+
+
+def test_edge_case_builder_keeps_its_own_conditions():
+    """tests/resample_cases.py: the row counts of the table, impulse positions in range, no dense case near zero, the
+    quiet reference above 1e-5, every form on the output stride that selects it."""
+    from tests import resample_cases as RC
+    assert [(n, b, RC.pair_rows(b, n)) for n, b, _ in RC.ROW_TABLE] == list(RC.ROW_TABLE)
+    assert [(c.n_in, c.batch, c.rows) for c in RC.case_set("rows")] == list(RC.ROW_TABLE)
+    assert sorted(m for _, _, m in RC.ROW_TABLE) == [1, 127, 129, 387, 512, 1023, 1025, 1025, 1539]
+    assert 1539 == 8 * 192 + 3 == 6 * 256 + 3
+    assert all(0 <= p < RC.IMPULSE_N_IN for p in RC.IMPULSE_POS) and len(set(RC.IMPULSE_POS)) == 15
+    assert RC.out_len(RC.IMPULSE_N_IN) == 1026
+    imp = {c.name: c for c in RC.case_set("impulse")}
+    assert imp["impulse_hd_pair"].rows == 59 and imp["impulse_hd2_pair"].rows >= RC.HD2_FROM_ROWS
+    for c in imp.values():
+        assert c.bar == 2.0 ** -24 and c.out_stride % 2 == (c.form == "f32")
+        never = [i for i in range(c.batch) if RC.IMPULSE_POS[i % 15] >= 3078]
+        assert list(c.exact_zero) == never and len(never) == 2 * c.batch // 15
+        assert all(np.all(c.want[i] == 0.0) for i in never)
+        for i in range(c.batch):
+            p = RC.IMPULSE_POS[i % 15]
+            if p + 513 < 3078:                     # group delay 513: the main lobe is in the output (0.27 between two output samples)
+                assert np.abs(c.want[i]).max() > 0.25, p
+            elif p < 3078:                         # only the tail in front of the lobe: the small coefficients alone
+                assert 0.0 < np.abs(c.want[i]).max() < 1e-3, p
+    names = set()
+    for name in RC.SETS:
+        for c in RC.case_set(name):
+            names.add(c.name)
+            assert (c.out_stride % 2 == 0) == (c.form == "pair"), c.name
+            if c.dense:
+                assert c.out_len > 0 and np.nanmax(np.abs(c.want), axis=1).min() > 0.05, c.name
+            if name != "handoff":
+                assert np.all(np.isfinite(c.x[:, :c.n_in])) and np.all(np.isfinite(c.want)), c.name
+    assert len(names) == sum(len(RC.case_set(n)) for n in RC.SETS if n != "tile")                 # one name, one case
+    assert {c.name for c in RC.case_set("tile")} <= names
+    assert all(c.form == "pair" and (c.rows >= RC.HD2_FROM_ROWS or c.n_in == 4096) for c in RC.case_set("tile"))
+    for c in RC.case_set("lengths"):
+        assert c.x.shape == (3, c.n_in + 37) and np.all(np.isnan(c.x[:, c.n_in:])) and c.out_pad == (2 if c.form == "pair" else 3)
+        assert (c.out_len == 0) == (c.n_in <= 1024)
+    v = RC.crafted_values()
+    assert np.isinf(v).sum() == 2 and (v == 0).sum() == 2 and np.signbit(v[v == 0]).sum() == 1 and not np.isnan(v).any()
+    q = {c.name: c for c in RC.case_set("quiet")}
+    assert np.abs(q["quiet_lsb_pair"].want).max() > 1e-5
+    x = q["quiet_lsb_pair"].x
+    assert set(np.unique(x * 32768).tolist()) == {-1.0, 0.0, 1.0}
+    assert np.array_equal(x.astype(np.float16).astype(np.float32), x)                             # exact subnormal halves
+    for name in ("nan_m0_pair", "nan_m1_f32"):
+        c = {k.name: k for k in RC.case_set("handoff")}[name]
+        assert np.isnan(c.x).sum() == 1 and np.isnan(c.want).sum() == 684 and np.all(np.isnan(c.want[1, 342:1026]))
+    assert not np.isnan({k.name: k for k in RC.case_set("handoff")}["nan_m2_pair"].want).any()
