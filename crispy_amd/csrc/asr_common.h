@@ -23,6 +23,14 @@ __device__ __forceinline__ float gelu_ggml(float x) {
   yh = x <= -10.0f ? 0.0f : yh;
   return x >= 10.0f ? x : yh;
 }
+// GELU in its exact erf form (precision mode 0)
+__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
+
+// Registers of the 32 x 32 f32 matrix instructions as whisper_gemm.hip and whisper_attn.hip hold them
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+// row index of accumulator register r for this lane (32x32 MFMA C/D layout)
+__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 constexpr int MEL_FRAMES = 3000;   // frames the encoder consumes (30 s)
 constexpr int MEL_TILE = 64;
@@ -92,6 +100,7 @@ struct GemmArgs {
   int wq_type, wq_rows;
   const float* wq_gamma;
 };
+// ---- f32-activation products and LayerNorm (whisper_gemm.hip) ----
 constexpr int SKINNY_MAX_M = 512;   // decode steps with up to this many clips use the skinny kernel (row blocks of 32)
 hipError_t gemm_f32_nt(const GemmArgs& g, int batch, hipStream_t s);
 // decode-step projection straight from resident ggml blocks (GemmArgs::wq): de-quantised in registers
@@ -141,8 +150,8 @@ hipError_t vocab_f16(const void* x, long ldx, const void* Ep, float* C, long ldc
 struct FusedIn;
 constexpr int VOCAB_FUSE_ROWS = 4;
 hipError_t vocab_f16_fused(const FusedIn& in, const void* Ep, float* C, long ldc, int M, int N, int K, hipStream_t s);
-hipError_t layernorm_f32(const float* x, const float* gamma, const float* beta, float* y, long rows, int D, hipStream_t s);
-hipError_t attn_encoder_f32(const float* qkv, float* out, int B, int T, int D, int heads, hipStream_t s);
+hipError_t layernorm_f32(const float* x, const float* gamma, const float* beta, float* y, long rows, int D, hipStream_t s);      // whisper_gemm.hip
+hipError_t attn_encoder_f32(const float* qkv, float* out, int B, int T, int D, int heads, hipStream_t s);      // whisper_attn.hip, as the two below
 // Rows of a decode step: one query row per clip, or -- the batched prompt step -- G consecutive rows per clip (row =
 // clip * G + j, G = AttnRows::group): row b reads the K|V of clip b / G.  key_step = 1: row j sees n_keys_base + j keys
 // (causal self-attention over the positions the step itself writes).  One workgroup per (row, head) either way; the rows
@@ -250,6 +259,7 @@ hipError_t fused_self(const FusedSelfArgs& a, bool first_layer, hipStream_t s); 
 hipError_t fused_cross(const FusedCrossArgs& a, hipStream_t s);
 hipError_t fused_mlp(const FusedMlpArgs& a, hipStream_t s);
 hipError_t fused_finish(const FusedFinishArgs& a, hipStream_t s);
+// ---- both ends of a decode step (whisper_pick.hip): embed_tokens_f32 here; ts_pick, beam_*, softmax_prob_f32, argmax_f32 below ----
 // x[r][:] = tok_emb[tokens[r]] + pos_emb[pos + r % rows_per_clip] for B rows (rows_per_clip > 1: the batched prompt step)
 hipError_t embed_tokens_f32(const int* tokens, const float* tok_emb, const float* pos_emb, int pos, const int* pos_dev,
                             float* x, int B, int D, hipStream_t s, int rows_per_clip = 1, const int* row_off = nullptr);

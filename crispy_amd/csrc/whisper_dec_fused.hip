@@ -171,7 +171,7 @@ struct HeadOut {
 
 // One query against the f16 keys / values of ONE head held in registers: SLOTS slots of 8 keys per wave (8 lanes per key
 // row of 64 halves), the 16 waves split the keys, partial (max, sum, P.V) triples meet in LDS -- the partition, the
-// arithmetic and the merge of attn_dec_x16_kernel (whisper_kernels.hip), so a row decodes to the same bits whichever
+// arithmetic and the merge of attn_dec_x16_kernel (whisper_attn.hip), so a row decodes to the same bits whichever
 // launch form ran its attention.  valid key <=> k_lo + 8 i + r < k_hi.  Returns with att_h[0..63] written (f16 of the
 // attention output) and a workgroup barrier behind it.
 // mid(): called once the keys and values have been consumed (their registers are free) and before the merge: the place

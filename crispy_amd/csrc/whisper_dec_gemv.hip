@@ -2,7 +2,7 @@
 // small, medium, large-v3 / turbo -- src-tauri/src/managers/model.rs:74-148), dense f16 or resident ggml blocks, at the
 // reference's call shape: one chunk at a time (engine.transcribe, managers/transcription.rs:183-185), i.e. 1 .. 4 rows.
 //
-// Round 5 ran these steps through the 32 x 32-tile "skinny" kernels (whisper_kernels.hip): N / 32 workgroups -- 32 of the
+// Round 5 ran these steps through the 32 x 32-tile "skinny" kernels (whisper_gemm.hip): N / 32 workgroups -- 32 of the
 // chip's 256 CUs for a 1024-wide projection -- each walking K in chunks of 32 per wave, plus a LayerNorm launch in front of
 // three of the six projections: 11 launches per layer, 4.5 - 6 us each whatever they do (15 us for fc2, K = 4096 walked by
 // 16 waves), 1.75 - 1.94 ms per token on Whisper-medium (profiles/r06_decode_medium_*).  A step of one row is a

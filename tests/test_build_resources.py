@@ -184,8 +184,8 @@ def test_f16_encoder_kernels_run_at_four_waves_per_simd_without_scratch(tmp_path
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-@pytest.mark.parametrize("src_name", ["whisper_kernels.hip", "whisper_dec_f16.hip", "whisper_dec_fused.hip", "mel_kernels.hip",
-                                      "resample_kernels.hip"])
+@pytest.mark.parametrize("src_name", ["whisper_gemm.hip", "whisper_attn.hip", "whisper_pick.hip", "whisper_dec_f16.hip",
+                                      "whisper_dec_fused.hip", "mel_kernels.hip", "resample_kernels.hip"])
 def test_asr_kernels_have_no_scratch_at_all(tmp_path, src_name):
     """with this compiler a VGPR spill next to a divergent region is a correctness hazard (see the
     module docstring), and the decode-step kernels -- gemm_skinny_f32_kernel (every LayerNorm / GELU / residual / K-split /
@@ -209,10 +209,14 @@ def test_asr_kernels_have_no_scratch_at_all(tmp_path, src_name):
         if m and cur:
             res[cur][m.group(1).strip()] = int(m.group(2))
     assert res, out.stderr[-500:]
-    if src_name == "whisper_kernels.hip":
-        for must in ("gemm_skinny_f32_kernel", "ts_pick_kernel", "argmax_kernel", "attn_dec_kernel"):
-            assert any(must in k for k in res), (must, list(res))
+    must_have = {"whisper_gemm.hip": ("gemm_skinny_f32_kernel", "gemm_skinny_q_kernel"), "whisper_attn.hip": ("attn_dec_kernel",),
+                 "whisper_pick.hip": ("ts_pick_kernel", "argmax_kernel")}
+    for must in must_have.get(src_name, ()):
+        assert any(must in k for k in res), (must, list(res))
+    if src_name == "whisper_gemm.hip":
         assert sum("gemm_skinny_f32_kernel" in k for k in res) == 44      # 8 epilogue forms x 4 K splits + 3 x 4 f16-weight forms (residual; bias; bias + GELU)
+        assert sum("gemm_skinny_q_kernel" in k for k in res) == 100       # 5 block types x 4 K splits x (LayerNorm fold; + GELU; f16: residual; bias; bias + GELU)
+    if src_name == "whisper_attn.hip":
         assert sum("attn_dec_x16_kernel" in k for k in res) == 5           # 1 / 2 / 4 / 12 key slots per wave + the non-temporal 12 (K|V streams of many clips)
     if src_name == "whisper_dec_fused.hip":       # the fused decode step: every (width, key slots, rows per workgroup) form at <= 128 registers
         for must, n in (("fused_self_kernel", 20), ("fused_cross_kernel", 4), ("fused_mlp_kernel", 8), ("fused_finish_kernel", 2)):
