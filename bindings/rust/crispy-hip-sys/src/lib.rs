@@ -28,6 +28,8 @@ pub const CRISPY_ERR_OOM: c_int = -4;
 pub const CRISPY_ERR_BAD_MODEL: c_int = -5;
 pub const CRISPY_ERR_UNSUPPORTED: c_int = -6;
 pub const CRISPY_ERR_CANCELLED: c_int = -7;
+/// Longest clip of one transcribe call: 2 h at 16 kHz (`CRISPY_ASR_MAX_SAMPLES`).
+pub const CRISPY_ASR_MAX_SAMPLES: usize = 115_200_000;
 
 pub const CRISPY_RN_FRAME_SIZE: usize = 480;
 pub const CRISPY_RN_WEIGHT_BYTES: usize = 87503;
@@ -246,6 +248,7 @@ extern "C" {
     pub fn crispy_mel_destroy(h: *mut crispy_mel);
     pub fn crispy_mel_compute(h: *mut crispy_mel, pcm: *const c_float, pcm_stride: c_long, n_samples: *const c_int, batch: c_int, out: *mut c_float) -> c_int;
     pub fn crispy_mel_compute_device(h: *mut crispy_mel, d_pcm: *const c_float, pcm_stride: c_long, n_samples: *const c_int, batch: c_int, d_out: *mut c_float, d_out_t: *mut c_float, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_mel_compute_long_device(h: *mut crispy_mel, d_pcm: *const c_float, pcm_stride: c_long, n_samples: *const c_int, batch: c_int, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_mel_window_device(h: *mut crispy_mel, clip_idx: *const c_int, seek: *const c_int, n: c_int, d_out: *mut c_float, d_out_t: *mut c_float, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_mel_synchronize(h: *mut crispy_mel) -> c_int;
 
@@ -278,6 +281,7 @@ extern "C" {
     pub fn crispy_asr_align_device(h: *mut crispy_asr, d_enc: *const c_float, batch: c_int, tokens: *const c_int, n_tokens: *const c_int, ld_tokens: c_int, n_sot: c_int, n_frames: *const c_int, heads: *const c_int, n_heads: c_int, d_probs: *mut c_float, d_matrix: *mut c_float, jump_times: *mut c_float) -> c_int;
     pub fn crispy_asr_dtw_device(h: *mut crispy_asr, d_x: *const c_float, n_rows: c_int, n_cols: c_int, ld: c_long, text_idx: *mut c_int, time_idx: *mut c_int, n_path: *mut c_int) -> c_int;
     pub fn crispy_asr_transcribe_recording(h: *mut crispy_asr, pcm16k: *const c_float, n: usize, opts: *const crispy_asr_opts, max_batch: c_int, cancel_flag: *const c_int, progress: crispy_asr_progress_fn, progress_user: *mut c_void, out: *mut *mut crispy_asr_result) -> c_int;
+    pub fn crispy_asr_transcribe_hooks(h: *mut crispy_asr, pcm16k: *const c_float, n: usize, opts: *const crispy_asr_opts, cancel_flag: *const c_int, progress: crispy_asr_progress_fn, progress_user: *mut c_void, out: *mut *mut crispy_asr_result) -> c_int;
 
     pub fn crispy_resampler_create(device: c_int, out: *mut *mut crispy_resampler) -> c_int;
     pub fn crispy_resampler_destroy(h: *mut crispy_resampler);
@@ -684,7 +688,16 @@ impl GpuWhisperEngine {
     pub fn set_precision(&mut self, mode: i32) -> Result<(), CrispyError> {
         check(unsafe { crispy_asr_set_precision(self.h, mode as c_int) })
     }
-    /// One chunk of at most 480 000 samples (16 kHz, f32 in +-1); `opts = None` is `TranscribeOptions::default()`:
+    /// Audio of any length up to `CRISPY_ASR_MAX_SAMPLES` (16 kHz, f32 in +-1) through ONE `whisper_full`: the log-mel of
+    /// the whole recording, then 30 s windows that advance to the last closed timestamp pair and carry the text so far --
+    /// what `SpeechModel::transcribe(&mut self, &[f32], ..)` means for a whisper.cpp engine, and not the hard 30 s cuts of
+    /// `transcribe_recording`.  `opts = None` is `TranscribeOptions::default()`.  Segment, word and window times count from
+    /// the start of `audio`.
+    pub fn transcribe(&mut self, audio: &[f32], opts: Option<&crispy_asr_opts>) -> Result<Transcript, CrispyError> {
+        self.transcribe_chunk(audio, opts)
+    }
+    /// One chunk (16 kHz, f32 in +-1) as the reference's chunker hands it over: at most 480 000 samples there, though the
+    /// engine takes what `transcribe` takes; `opts = None` is `TranscribeOptions::default()`:
     /// language auto-detected, transcribe task, timestamps on.  Empty audio gives an empty transcript
     /// (managers/transcription.rs:175-177).
     pub fn transcribe_chunk(&mut self, audio: &[f32], opts: Option<&crispy_asr_opts>) -> Result<Transcript, CrispyError> {
@@ -831,7 +844,7 @@ mod speech_model {
                 o.language_token = tok;
             }
             o.translate = options.translate as c_int;
-            let t = self.transcribe_chunk(audio, Some(&o))?;
+            let t = GpuWhisperEngine::transcribe(self, audio, Some(&o))?;      // any length, as the trait's &[f32] promises
             Ok(TranscriptionResult {
                 text: t.text,
                 segments: t.segments.map(|v| v.into_iter().map(|s| TranscriptionSegment { start: s.start, end: s.end, text: s.text }).collect()),

@@ -44,7 +44,8 @@ PCM_F32, PCM_I16, PCM_U16 = 0, 1, 2      # CRISPY_PCM_*
 
 
 MEL_SYMBOLS = ("crispy_mel_create", "crispy_mel_destroy", "crispy_mel_compute",
-               "crispy_mel_compute_device", "crispy_mel_window_device", "crispy_mel_synchronize")
+               "crispy_mel_compute_device", "crispy_mel_compute_long_device", "crispy_mel_window_device",
+               "crispy_mel_synchronize")
 ASR_SYMBOLS = ("crispy_asr_create", "crispy_asr_set_tensor", "crispy_asr_finalize", "crispy_asr_free",
                "crispy_asr_hparams_get", "crispy_asr_encode", "crispy_asr_encode_device", "crispy_asr_synchronize",
                "crispy_asr_set_suppress", "crispy_asr_decode_greedy_device", "crispy_asr_transcribe_tokens",
@@ -52,7 +53,7 @@ ASR_SYMBOLS = ("crispy_asr_create", "crispy_asr_set_tensor", "crispy_asr_finaliz
                "crispy_asr_decode_greedy_lang_device", "crispy_asr_detect_language_device",
                "crispy_asr_transcribe_batch", "crispy_asr_decode_timestamps_device", "crispy_asr_set_precision",
                "crispy_asr_vocab_specials", "crispy_asr_stage_logits_device", "crispy_asr_language_token",
-               "crispy_asr_decode_window_device", "crispy_asr_transcribe_recording",
+               "crispy_asr_decode_window_device", "crispy_asr_transcribe_recording", "crispy_asr_transcribe_hooks",
                "crispy_asr_align_device", "crispy_asr_dtw_device")
 RS_SYMBOLS = ("crispy_resampler_create", "crispy_resampler_destroy", "crispy_resampler_out_len",
               "crispy_resampler_process_device", "crispy_resampler_synchronize")
@@ -238,6 +239,8 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_asr_free_result.argtypes = [C.c_void_p]
     L.crispy_asr_transcribe_recording.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
                                                   PROGRESS_FN, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.crispy_asr_transcribe_hooks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, PROGRESS_FN,
+                                              C.c_void_p, C.POINTER(C.c_void_p)]
     L.crispy_asr_free_result.restype = None
     L.crispy_asr_set_precision.argtypes = [C.c_void_p, C.c_int]
     L.crispy_asr_stage_logits_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -247,6 +250,7 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_asr_decode_window_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                   C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.crispy_mel_compute_long_device.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p]
     L.crispy_mel_window_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.crispy_asr_decode_greedy_lang_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

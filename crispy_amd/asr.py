@@ -14,6 +14,7 @@ from .mel_filters import whisper_mel_filters
 
 N_FRAMES = 3000
 CHUNK_SAMPLES = 480000  # 30 s at 16 kHz (commands/transcription.rs:175-176)
+MAX_SAMPLES = 115200000  # CRISPY_ASR_MAX_SAMPLES: 2 h at 16 kHz, the longest clip of one transcribe call
 
 
 class LogMel:
@@ -66,8 +67,16 @@ class LogMel:
         self._ck(self._L.crispy_mel_compute_device(self._h, d_pcm, pcm_stride, lens.ctypes.data, lens.size,
                                                   d_out or None, d_out_t or None, stream or None))
 
+    def compute_long_device(self, d_pcm: int, pcm_stride: int, n_samples: np.ndarray, stream: int = 0):
+        """`crispy_mel_compute_long_device`: clips of any length (1 .. MAX_SAMPLES each), as whisper.cpp computes the
+        log-mel of a whole recording once -- (n + 480000) / 160 frames, one maximum.  Keeps the frames and the maxima in
+        the handle and writes no window: `window_device` reads them, at any seek up to the clip's 1 + (n - 200) // 160."""
+        lens = np.ascontiguousarray(n_samples, dtype=np.int32)
+        self._ck(self._L.crispy_mel_compute_long_device(self._h, d_pcm, pcm_stride, lens.ctypes.data, lens.size, stream or None))
+
     def window_device(self, clip_idx, seek, d_out: int = 0, d_out_t: int = 0, stream: int = 0):
-        """Later 30 s windows (whisper_full's seek loop) of the clips of the last compute_device call."""
+        """30 s windows (whisper_full's seek loop) of the clips of the last compute_device (seek <= 3000) or
+        compute_long_device call."""
         ci = np.ascontiguousarray(clip_idx, dtype=np.int32)
         sk = np.ascontiguousarray(seek, dtype=np.int32)
         self._ck(self._L.crispy_mel_window_device(self._h, ci.ctypes.data, sk.ctypes.data, ci.size, d_out or None,
@@ -301,8 +310,13 @@ class WhisperEngine(WhisperModel):
         return C.string_at(p, n.value)
 
     def transcribe(self, audio: np.ndarray, max_new_tokens: int = 0, translate: bool = False, language_token: int = 0,
-                   timestamps: bool = False, prev_text: bool = True, **decision):
-        """One chunk (<= 480000 samples at 16 kHz) -> (text, token ids); empty audio -> ("", []).
+                   timestamps: bool = False, prev_text: bool = True, cancel=None, progress=None, **decision):
+        """16 kHz audio of any length up to MAX_SAMPLES -> (text, token ids); empty audio -> ("", []).  With timestamps = True
+        more than 480000 samples are ONE whisper_full over the whole audio (the log-mel of all of it, 30 s windows that
+        advance to the last closed timestamp pair and carry the text so far), not the 30 s cuts of `transcribe_recording`;
+        timestamps = False decodes one window and refuses more than 480000 samples.
+        cancel / progress: whisper_full's two hooks (`crispy_asr_transcribe_hooks`) -- a `ctypes.c_int` polled before
+        every window (non-zero raises `Cancelled`) and a callable (samples_done, samples_total) after every window.
         language_token = 0 auto-detects, as `TranscribeOptions::default()` does.  timestamps = True is whisper.cpp's
         default decoding mode (timestamp tokens, seek loop); its segments are kept in `self.last_segments` as
         (t0 seconds, t1 seconds, text), what whisper_full decided per window in `self.last_windows` (dicts of the
@@ -314,8 +328,16 @@ class WhisperEngine(WhisperModel):
         a = np.ascontiguousarray(audio, dtype=np.float32).ravel()
         opts = make_opts(language_token, translate, max_new_tokens, timestamps, prev_text, **decision)
         res = C.c_void_p()
-        self._ck(self._L.crispy_asr_transcribe(self._h, a.ctypes.data if a.size else None, a.size, C.byref(opts),
-                                              C.byref(res)))
+        if cancel is None and progress is None:
+            self._ck(self._L.crispy_asr_transcribe(self._h, a.ctypes.data if a.size else None, a.size, C.byref(opts),
+                                                  C.byref(res)))
+        else:
+            cb = N.PROGRESS_FN(lambda done, total, _user: progress(int(done), int(total))) if progress else N.PROGRESS_FN()
+            rc = self._L.crispy_asr_transcribe_hooks(self._h, a.ctypes.data if a.size else None, a.size, C.byref(opts),
+                                                     C.byref(cancel) if cancel is not None else None, cb, None, C.byref(res))
+            if rc == N.ERR_CANCELLED:
+                raise Cancelled()
+            self._ck(rc)
         try:
             text, tokens, self.last_language_token, self.last_segments, self.last_windows = _read_result(res)
             self.last_token_times, self.last_words = _read_alignment(res)
@@ -325,7 +347,8 @@ class WhisperEngine(WhisperModel):
 
     def transcribe_segments(self, audio: np.ndarray, max_new_tokens: int = 0, language_token: int = 0, prev_text: bool = True,
                             **decision):
-        """`engine.transcribe(..)` with whisper.cpp's default options -> (text, [(t0, t1, text)], token ids)."""
+        """`engine.transcribe(..)` with whisper.cpp's default options, audio of any length up to MAX_SAMPLES ->
+        (text, [(t0, t1, text)], token ids); times count from the start of the audio."""
         text, tokens = self.transcribe(audio, max_new_tokens, False, language_token, timestamps=True, prev_text=prev_text,
                                        **decision)
         return text, self.last_segments, tokens
@@ -385,7 +408,8 @@ def _read_alignment(res) -> tuple:
 def transcribe_batch(engine: "WhisperEngine", clips, max_new_tokens: int = 0, language_token: int = 0,
                      timestamps: bool = False, with_segments: bool = False, prev_text: bool = True, with_words: bool = False,
                      **decision):
-    """`crispy_asr_transcribe_batch`: a list of chunks (each <= 30 s, empty allowed) -> [(text, tokens, language)]
+    """`crispy_asr_transcribe_batch`: a list of clips (any lengths up to MAX_SAMPLES, mixed and empty allowed; more than
+    30 s needs timestamps=True) -> [(text, tokens, language)]
     (+ segments and window decisions with with_segments; + token times and words, `_read_alignment`, with with_words --
     pass dtw=True for them)."""
     arrs = [np.ascontiguousarray(c, dtype=np.float32).ravel() for c in clips]

@@ -25,6 +25,10 @@ struct crispy_mel {
   DevBuf<float> d_out;
   DevBuf<int> d_idx;        // [2][cap_batch]: clip index | seek of a window call
   int last_batch = 0;       // clips whose raw frames d_raw / d_max currently hold
+  // after crispy_mel_compute_long_device: where each clip's rows lie in d_raw (MelArgs::clip_rows) and the last frame a
+  // window of it may start at, n_len_org; seek_max empty = the last compute was the 30 s form (seek <= 3000)
+  DevBuf<long> d_rows;
+  std::vector<int> seek_max;
 };
 
 namespace {
@@ -36,6 +40,7 @@ int mel_reserve(crispy_mel* h, int batch, long stride, bool need_pcm, bool need_
     h->cap_stride = 0;
     h->cap_batch = 0;
     const size_t elems = (size_t)batch * h->n_mel * MEL_RAW_FRAMES;
+    h->seek_max.clear();
     HIP_TRY(h->d_n.alloc(sizeof(int) * batch));
     HIP_TRY(h->d_idx.alloc(sizeof(int) * 2 * batch));
     HIP_TRY(h->d_max.alloc(sizeof(int) * batch));
@@ -148,8 +153,75 @@ int crispy_mel_compute_device(crispy_mel* h, const float* d_pcm, long pcm_stride
   a.out_t = d_out_t;
   HIP_TRY(mel_launch(a, batch, s));
   h->last_batch = batch;
+  h->seek_max.clear();
   return CRISPY_OK;
 } CRISPY_CATCH_RET("crispy_mel_compute_device")
+
+// whisper.cpp computes the log-mel of a whole recording once [UPSTREAM-RECALL: log_mel_spectrogram -- reflect 200 in front,
+// 30 s of zeros + 200 behind, (n + 480000) / 160 frames, ONE maximum] and the seek loop reads windows of it.  Kept per clip:
+// the frames that touch audio, in whole tiles (MelArgs::clip_rows); the padding behind them is one known float.
+int crispy_mel_compute_long_device(crispy_mel* h, const float* d_pcm, long pcm_stride, const int* n_samples, int batch,
+                                   void* hip_stream) try {
+  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "crispy_mel_compute_long_device: NULL handle");
+  if (batch < 0) return fail(CRISPY_ERR_INVALID_ARG, "crispy_mel_compute_long_device: batch < 0");
+  if (batch == 0) return CRISPY_OK;
+  if (!d_pcm || !n_samples) return fail(CRISPY_ERR_INVALID_ARG, "crispy_mel_compute_long_device: NULL argument");
+  for (int b = 0; b < batch; ++b)
+    if (n_samples[b] <= 0 || n_samples[b] > CRISPY_ASR_MAX_SAMPLES || n_samples[b] > pcm_stride)
+      return fail(CRISPY_ERR_INVALID_ARG, "crispy_mel_compute_long_device: clip %d has %d samples (1..%d, <= stride %ld)", b,
+                  n_samples[b], CRISPY_ASR_MAX_SAMPLES, pcm_stride);
+  // per clip: rows of `pitch` frames = whole tiles up to the last frame whose 400 samples (from 160 t - 200) reach audio
+  std::vector<long> rows((size_t)2 * batch);
+  std::vector<int> key0((size_t)batch), len_org((size_t)batch);
+  size_t elems = 0;
+  int tiles = 0;
+  for (int b = 0; b < batch; ++b) {
+    const int live = (n_samples[b] + 200 + 159) / 160;
+    const int t = (live + MEL_TILE - 1) / MEL_TILE;
+    rows[2 * b] = (long)elems;
+    rows[2 * b + 1] = (long)t * MEL_TILE;
+    elems += (size_t)h->n_mel * t * MEL_TILE;
+    if (t > tiles) tiles = t;
+    key0[b] = (int)(0xc1200000u ^ 0x7fffffffu);           // the order key of -10.f: the zero padding is part of every clip
+    len_org[b] = 1 + (n_samples[b] + 200 - 400) / 160;
+    if (len_org[b] < 0) len_org[b] = 0;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  int rc = mel_reserve(h, batch, pcm_stride, false, false);
+  if (rc != CRISPY_OK) return rc;
+  // grown into fresh buffers first: on CRISPY_ERR_OOM the handle still holds what it held (and serves windows of it)
+  if (h->d_rows.bytes < sizeof(long) * 2 * batch) {
+    DevBuf<long> fresh;
+    HIP_TRY(fresh.alloc(sizeof(long) * 2 * h->cap_batch));
+    h->d_rows = std::move(fresh);
+  }
+  if (h->d_raw.bytes < sizeof(float) * elems) {
+    DevBuf<float> fresh;
+    HIP_TRY(fresh.alloc(sizeof(float) * elems));
+    h->d_raw = std::move(fresh);
+  }
+  h->last_batch = 0;                                        // from here on the old frames are being overwritten
+  h->seek_max.clear();
+  HIP_TRY(hipMemcpyAsync(h->d_n, n_samples, sizeof(int) * batch, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->d_rows, rows.data(), sizeof(long) * 2 * batch, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->d_max, key0.data(), sizeof(int) * batch, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));                         // the host arrays go out of scope
+  MelArgs a{};
+  a.pcm = d_pcm;
+  a.pcm_stride = pcm_stride;
+  a.n_samples = h->d_n;
+  a.n_mel = h->n_mel;
+  a.tab = h->d_tab;
+  a.raw = h->d_raw;
+  a.clip_max = h->d_max;
+  a.clip_rows = h->d_rows;
+  a.tiles = tiles;
+  HIP_TRY(mel_launch(a, batch, s));
+  h->seek_max.swap(len_org);
+  h->last_batch = batch;
+  return CRISPY_OK;
+} CRISPY_CATCH_RET("crispy_mel_compute_long_device")
 
 int crispy_mel_compute(crispy_mel* h, const float* pcm, long pcm_stride, const int* n_samples, int batch,
                        float* out) try {
@@ -180,8 +252,10 @@ int crispy_mel_window_device(crispy_mel* h, const int* clip_idx, const int* seek
   if (n > h->cap_batch || h->last_batch == 0)
     return fail(CRISPY_ERR_INVALID_ARG, "crispy_mel_window_device: %d windows, but the last crispy_mel_compute_device call held %d clips",
                 n, h->last_batch);
+  const bool long_form = !h->seek_max.empty();
   for (int k = 0; k < n; ++k)
-    if (clip_idx[k] < 0 || clip_idx[k] >= h->last_batch || seek[k] < 0 || seek[k] > MEL_FRAMES)
+    if (clip_idx[k] < 0 || clip_idx[k] >= h->last_batch || seek[k] < 0 ||
+        seek[k] > (long_form ? h->seek_max[clip_idx[k]] : MEL_FRAMES))
       return fail(CRISPY_ERR_INVALID_ARG, "crispy_mel_window_device: window %d = (clip %d, seek %d) out of range", k, clip_idx[k], seek[k]);
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
@@ -196,6 +270,7 @@ int crispy_mel_window_device(crispy_mel* h, const int* clip_idx, const int* seek
   a.out_t = d_out_t;
   a.clip_idx = h->d_idx;
   a.seek = h->d_idx + h->cap_batch;
+  a.clip_rows = long_form ? h->d_rows.p : nullptr;
   HIP_TRY(mel_window_launch(a, n, s));
   return CRISPY_OK;
 } CRISPY_CATCH_RET("crispy_mel_window_device")

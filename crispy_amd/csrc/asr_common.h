@@ -53,7 +53,7 @@ struct MelArgs {
   const int* n_samples;    // [batch] (device)
   int n_mel;
   const MelTables* tab;
-  float* raw;              // [batch][n_mel][3008] log10 values before normalisation
+  float* raw;              // [batch][n_mel][3008] log10 values before normalisation (clip_rows: the long form below)
   int* clip_max;           // [batch] order-preserving int key of the clip maximum
   float* out;              // [batch][n_mel][3000] or null
   float* out_t;            // [batch][3002][n_mel] zero padded frame-major copy or null
@@ -61,6 +61,12 @@ struct MelArgs {
   // computed range are pure zero padding (log10 floor), the normalisation uses the clip-wide maximum
   const int* clip_idx;
   const int* seek;
+  // long form (crispy_mel_compute_long_device; null = the 30 s form, 47 tiles per clip): per clip {element offset of its
+  // rows in raw, frames per row} (device).  A row holds whole tiles up to the clip's last frame that touches audio;
+  // every later frame lies in the zero padding and is the float an all-zero frame gives, log10(1e-10) = -10.f, which
+  // the window kernel substitutes and from which the host starts clip_max.  tiles = grid.x = tiles of the longest clip.
+  const long* clip_rows;
+  int tiles;
 };
 
 hipError_t mel_launch(const MelArgs& a, int batch, hipStream_t s);

@@ -5,7 +5,8 @@
 // Semantics: SURVEY.md Appendix B.1 / oracle/logmel_oracle.c.
 //
 // HBM-bound stage: per 30 s clip 1.92 MB of PCM in, 0.96 MB of mel out.
-//   mel_frames_kernel  grid (47 tiles, batch); 4 waves per workgroup, each wave transforms 16
+//   mel_frames_kernel  grid (47 tiles, batch) -- clips of any length (MelArgs::clip_rows): (tiles of the longest clip,
+//                      batch), a workgroup past its clip's last live tile leaves at once; 4 waves per workgroup, each wave transforms 16
 //                      consecutive frames: Hann window, 400-point real FFT as a 200-point complex
 //                      Stockham FFT in LDS (radices 4.2.5.5), power spectrum, sparse triangular mel
 //                      filters (double accumulation as upstream), log10.  The tables of the stage
@@ -61,6 +62,9 @@ __device__ __forceinline__ float log10_to_float(double s) {
   const double ln_m = 2.0 * z + 2.0 * z * (z2 * p);
   return (float)((double)e * 0.30102999566398120 + ln_m * 0.43429448190325176);
 }
+// LONG: the clips' rows lie where MelArgs::clip_rows says (clips of any length); otherwise [batch][n_mel][3008].  The 30 s
+// form keeps its constant row length: the two instantiations differ in addresses only, never in arithmetic.
+template <bool LONG>
 __global__ __launch_bounds__(256) void mel_frames_kernel(MelArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -75,6 +79,10 @@ __global__ __launch_bounds__(256) void mel_frames_kernel(MelArgs a) {
   int* l_meta = reinterpret_cast<int*>(l_fw + MEL_FW_MAX);
   const float* __restrict__ x = a.pcm + (long)b * a.pcm_stride;
   const int n = a.n_samples[b];
+  // where the clip's rows lie and how long they are (the same for the whole workgroup, as is the exit)
+  const long row0 = LONG ? a.clip_rows[2 * b] : (long)b * a.n_mel * MEL_RAW_FRAMES;
+  const int pitch = LONG ? (int)a.clip_rows[2 * b + 1] : MEL_RAW_FRAMES;
+  if (LONG && t0 >= pitch) return;      // wholly in the zero padding: before the table copy and the barrier
   {
     const MelTables* __restrict__ tab = a.tab;
     for (int i = threadIdx.x; i < 400; i += 256) { l_w400[i] = tab->w400[i]; l_hann[i] = tab->hann[i]; }
@@ -167,7 +175,7 @@ __global__ __launch_bounds__(256) void mel_frames_kernel(MelArgs a) {
         wmax = fmaxf(wmax, lv[f]);
       }
       static_assert(MEL_NF == 4, "one float4 per mel bin and batch");
-      *reinterpret_cast<float4*>(a.raw + ((long)b * a.n_mel + m) * MEL_RAW_FRAMES + t0 + f0) = make_float4(lv[0], lv[1], lv[2], lv[3]);
+      *reinterpret_cast<float4*>(a.raw + row0 + (long)m * pitch + t0 + f0) = make_float4(lv[0], lv[1], lv[2], lv[3]);
     }
     wave_lds_sync();
   }
@@ -176,6 +184,7 @@ __global__ __launch_bounds__(256) void mel_frames_kernel(MelArgs a) {
   if (lane == 0) atomicMax(a.clip_max + b, float_order_key(wmax));
 }
 
+template <bool LONG>
 __global__ __launch_bounds__(256) void mel_finish_kernel(MelArgs a) {
   const int k = blockIdx.y;                        // output index
   const int b = a.clip_idx ? a.clip_idx[k] : k;    // clip whose raw frames / maximum are used
@@ -186,8 +195,10 @@ __global__ __launch_bounds__(256) void mel_finish_kernel(MelArgs a) {
   const int m = (int)(idx / MEL_FRAMES), t = (int)(idx % MEL_FRAMES);
   const double mmax = (double)float_from_key(a.clip_max[b]) - 8.0;
   const int src = seek + t;
-  // frames >= 3002 are zeros only (clips are <= 30 s): log10(1e-10)
-  double v = src < MEL_RAW_FRAMES ? (double)a.raw[((long)b * a.n_mel + m) * MEL_RAW_FRAMES + src] : -10.0;
+  const long row0 = LONG ? a.clip_rows[2 * b] : (long)b * a.n_mel * MEL_RAW_FRAMES;
+  const int pitch = LONG ? (int)a.clip_rows[2 * b + 1] : MEL_RAW_FRAMES;
+  // frames past the row are zeros only (>= 3002 for a clip of <= 30 s): log10(1e-10), the frame kernel's float for them
+  double v = src < pitch ? (double)a.raw[row0 + (long)m * pitch + src] : -10.0;
   if (v < mmax) v = mmax;
   const float r = (float)((v + 4.0) / 4.0);
   if (a.out) a.out[(long)k * total + idx] = r;
@@ -197,21 +208,26 @@ __global__ __launch_bounds__(256) void mel_finish_kernel(MelArgs a) {
 }  // namespace
 
 hipError_t mel_launch(const MelArgs& a, int batch, hipStream_t s) {
-  hipError_t e = hipMemsetAsync(a.clip_max, 0x80, sizeof(int) * batch, s);  // 0x80808080: below any key
-  if (e != hipSuccess) return e;
   constexpr size_t smem = MEL_LDS;     // 36 KB whatever the number of mel bins
   static_assert(smem <= 64 * 1024, "above the default dynamic-LDS limit: the launch would need hipFuncSetAttribute per device");
-  hipLaunchKernelGGL(mel_frames_kernel, dim3(MEL_TILES, batch), dim3(256), smem, s, a);
+  if (a.clip_rows) {                   // long form: clip_max starts from the padding's floor (the caller), no window is written
+    hipLaunchKernelGGL(mel_frames_kernel<true>, dim3(a.tiles, batch), dim3(256), smem, s, a);
+    return hipGetLastError();
+  }
+  hipError_t e = hipMemsetAsync(a.clip_max, 0x80, sizeof(int) * batch, s);  // 0x80808080: below any key
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mel_frames_kernel<false>, dim3(MEL_TILES, batch), dim3(256), smem, s, a);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   const long total = (long)a.n_mel * MEL_FRAMES;
-  hipLaunchKernelGGL(mel_finish_kernel, dim3((unsigned)((total + 255) / 256), batch), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(mel_finish_kernel<false>, dim3((unsigned)((total + 255) / 256), batch), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t mel_window_launch(const MelArgs& a, int n, hipStream_t s) {
   const long total = (long)a.n_mel * MEL_FRAMES;
-  hipLaunchKernelGGL(mel_finish_kernel, dim3((unsigned)((total + 255) / 256), n), dim3(256), 0, s, a);
+  if (a.clip_rows) hipLaunchKernelGGL(mel_finish_kernel<true>, dim3((unsigned)((total + 255) / 256), n), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(mel_finish_kernel<false>, dim3((unsigned)((total + 255) / 256), n), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

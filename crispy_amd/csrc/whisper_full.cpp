@@ -13,7 +13,8 @@ namespace asr {
 namespace {
 
 int transcribe_batch_impl(crispy_asr* h, const float* const* pcm, const size_t* n, int batch, const crispy_asr_opts* opts,
-                          crispy_asr_result** results, const volatile int* cancel);
+                          crispy_asr_result** results, const volatile int* cancel, crispy_asr_progress_fn progress = nullptr,
+                          void* progress_user = nullptr);
 
 struct crispy_asr_result_impl {
   crispy_asr_result pub;
@@ -346,6 +347,17 @@ int crispy_asr_transcribe_batch(crispy_asr* h, const float* const* pcm, const si
   return transcribe_batch_impl(h, pcm, n, batch, opts, results, nullptr);
 } CRISPY_CATCH_RET("crispy_asr_transcribe_batch")
 
+// crispy_asr_transcribe with whisper_full's two hooks [UPSTREAM-RECALL: whisper_full_params abort_callback / progress_callback]
+int crispy_asr_transcribe_hooks(crispy_asr* h, const float* pcm16k, size_t n, const crispy_asr_opts* opts,
+                                const volatile int* cancel_flag, crispy_asr_progress_fn progress, void* progress_user,
+                                crispy_asr_result** out) try {
+  if (!out) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_transcribe_hooks: out is NULL");
+  *out = nullptr;
+  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_transcribe_hooks: NULL handle");
+  if (n > 0 && !pcm16k) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_transcribe_hooks: NULL audio");
+  return transcribe_batch_impl(h, &pcm16k, &n, 1, opts, out, cancel_flag, progress, progress_user);
+} CRISPY_CATCH_RET("crispy_asr_transcribe_hooks")
+
 }  // extern "C"
 
 namespace crispy {
@@ -377,8 +389,10 @@ struct GroupPicks {
 
 class BatchCall {
  public:
-  BatchCall(crispy_asr* h_, const float* const* pcm_, const size_t* n_, int batch_, const crispy_asr_opts* opts_, const volatile int* cancel_)
-      : h(h_), pcm(pcm_), n(n_), batch(batch_), opts(opts_), cancel(cancel_), sp(special_tokens(h_)) {}
+  BatchCall(crispy_asr* h_, const float* const* pcm_, const size_t* n_, int batch_, const crispy_asr_opts* opts_, const volatile int* cancel_,
+            crispy_asr_progress_fn progress_, void* progress_user_)
+      : h(h_), pcm(pcm_), n(n_), batch(batch_), opts(opts_), cancel(cancel_), progress(progress_), progress_user(progress_user_),
+        sp(special_tokens(h_)) {}
   ~BatchCall() {
     for (auto* r : impl) delete r;
   }
@@ -414,12 +428,15 @@ class BatchCall {
   int batch;
   const crispy_asr_opts* opts;
   const volatile int* cancel;
+  crispy_asr_progress_fn progress;     // (nullable) after every round of the seek loop
+  void* progress_user;
   const Special sp;
   std::vector<crispy_asr_result_impl*> impl;
   std::vector<int> live, lens, lang, prompt;
   size_t stride = 1;
   int nb = 0, max_new = 0, n_init = 0;
   bool timestamps = true, detect = false;
+  bool long_form = false;              // a clip of more than 30 s: the log-mel of whole clips, kept; every window read from it
   bool dtw = false;                    // opts.dtw_token_timestamps
   std::vector<int> dtw_heads;          // (layer, head) pairs; empty = the default set
   // whisper_full's parameters (0 in crispy_asr_opts = whisper.cpp's default)
@@ -472,14 +489,15 @@ int BatchCall::prepare() {
   // shorter than 1 s = 100 mel frames, which whisper.cpp's whisper_full refuses ("input is too short", returns no
   // segments) [UPSTREAM-RECALL] -- the 168 samples the 48 -> 16 kHz resampler leaves past a 30 s chunk are such a clip
   for (int i = 0; i < batch; ++i) {
-    if (n[i] > 480000)
-      return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_transcribe_batch: clip %d has %zu samples; the caller chunks at 480000 "
-                  "(commands/transcription.rs:249-302)", i, n[i]);
+    if (n[i] > (size_t)CRISPY_ASR_MAX_SAMPLES)
+      return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_transcribe_batch: clip %d has %zu samples; at most %d (CRISPY_ASR_MAX_SAMPLES, "
+                  "2 h at 16 kHz)", i, n[i], CRISPY_ASR_MAX_SAMPLES);
     if (n[i] > 0) {
       if (!pcm[i]) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_transcribe_batch: clip %d is NULL", i);
       if (1 + ((long)n[i] + 200 - 400) / 160 < TS_DELTA_MIN) continue;
       live.push_back(i);
       if (n[i] > stride) stride = n[i];
+      if (n[i] > 480000) long_form = true;
     }
   }
   impl.assign((size_t)batch, nullptr);
@@ -492,6 +510,9 @@ int BatchCall::prepare() {
   timestamps = !(opts && opts->no_timestamps) && sp.beg + 1501 <= h->hp.n_vocab;
   const int rc = check_options();
   if (rc != CRISPY_OK) return rc;
+  if (long_form && !timestamps)
+    return fail(CRISPY_ERR_UNSUPPORTED, "crispy_asr_transcribe_batch: no_timestamps decodes ONE 30 s window; a clip of more than 480000 "
+                "samples needs whisper_full's seek loop (timestamps on)");
   dtw = opts && opts->dtw_token_timestamps;
   if (dtw && opts->n_dtw_heads > 0) dtw_heads.assign(opts->dtw_heads, opts->dtw_heads + 2 * opts->n_dtw_heads);
   for (int i = 0; i < batch; ++i) impl[i]->dtw = dtw;
@@ -523,7 +544,15 @@ int BatchCall::upload_and_encode() {
   // never read -- the log-mel takes n_samples per clip
   for (int k = 0; k < nb; ++k)
     HIP_TRY(hipMemcpyAsync(h->ew.pcm + (size_t)k * stride, pcm[live[k]], (size_t)lens[k] * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  rc = crispy_mel_compute_device(h->mel, h->ew.pcm, (long)stride, lens.data(), nb, nullptr, h->ew.melt, h->stream);
+  if (long_form) {      // whisper.cpp: the log-mel of the whole recording once, window 0 is frames [0, 3000) of it
+    rc = crispy_mel_compute_long_device(h->mel, h->ew.pcm, (long)stride, lens.data(), nb, h->stream);
+    if (rc != CRISPY_OK) return rc;
+    std::vector<int> idx(nb), zero(nb, 0);
+    for (int k = 0; k < nb; ++k) idx[k] = k;
+    rc = crispy_mel_window_device(h->mel, idx.data(), zero.data(), nb, nullptr, h->ew.melt, h->stream);
+  } else {
+    rc = crispy_mel_compute_device(h->mel, h->ew.pcm, (long)stride, lens.data(), nb, nullptr, h->ew.melt, h->stream);
+  }
   if (rc != CRISPY_OK) return rc;
   rc = crispy_asr_encode_device(h, h->ew.melt, nb, h->ew.enc, h->stream);
   if (rc != CRISPY_OK) return rc;
@@ -656,15 +685,18 @@ std::vector<int> BatchCall::build_prompt(int k, int lang_tok, float t_cur) const
 int BatchCall::seek_loop() {
   // whisper.cpp loops until seek + delta_min >= seek_end.  Every round advances every active clip by seek_delta >= 2
   // (a closed pair ends on a timestamp strictly above <|0.00|>, otherwise the delta is the whole window), so
-  // 1500 rounds cover any 30 s clip; running out of them is reported, never a silently shorter transcript.
-  const int kMaxRounds = 1501;
+  // seek_end / 2 rounds cover the longest clip (1500 for 30 s); running out of them is reported, never a silently shorter
+  // transcript.
+  const int kMaxRounds = *std::max_element(seek_end.begin(), seek_end.end()) / 2 + 1;
   for (int round = 0;; ++round) {
-    if (round >= kMaxRounds)
-      return fail(CRISPY_ERR_HIP, "crispy_asr_transcribe_batch: seek loop did not terminate after %d windows", kMaxRounds);
-    if (cancel && *cancel) return fail(CRISPY_ERR_CANCELLED, "transcription cancelled by the caller");
     std::vector<int> act;
     for (int k = 0; k < nb; ++k)
       if (seek_end[k] >= TS_DELTA_MIN && seek[k] + TS_DELTA_MIN < seek_end[k]) act.push_back(k);   // < 100 ms left: whisper.cpp stops
+    if (round > 0 && progress)           // (one clip: crispy_asr_transcribe_hooks) the audio behind the window just finished, all of it at the end
+      progress(act.empty() ? (size_t)lens[0] : std::min((size_t)lens[0], (size_t)seek[0] * 160), (size_t)lens[0], progress_user);
+    if (round >= kMaxRounds)
+      return fail(CRISPY_ERR_HIP, "crispy_asr_transcribe_batch: seek loop did not terminate after %d windows", kMaxRounds);
+    if (cancel && *cancel) return fail(CRISPY_ERR_CANCELLED, "transcription cancelled by the caller");
     if (act.empty()) return CRISPY_OK;
     const int na = (int)act.size();
     if (!(round == 0 && na == nb)) {     // round 0 with every clip active: the encoder output is already there
@@ -931,7 +963,8 @@ void BatchCall::finish_window(int k, const Accepted& A) {
 // cancel (nullable): polled at the top of every round of the seek loop -- a set flag ends the call with
 // CRISPY_ERR_CANCELLED and no results (crispy_asr_transcribe_recording: commands/transcription.rs:251,359,402)
 int transcribe_batch_impl(crispy_asr* h, const float* const* pcm, const size_t* n, int batch, const crispy_asr_opts* opts,
-                          crispy_asr_result** results, const volatile int* cancel) {
+                          crispy_asr_result** results, const volatile int* cancel, crispy_asr_progress_fn progress,
+                          void* progress_user) {
   if (!h || !results) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_transcribe_batch: NULL argument");
   if (batch < 0) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_transcribe_batch: batch < 0");
   for (int i = 0; i < batch; ++i) results[i] = nullptr;
@@ -945,7 +978,7 @@ int transcribe_batch_impl(crispy_asr* h, const float* const* pcm, const size_t* 
   constexpr int kOneAnswerClips = SKINNY_MAX_M;
   for (int b0 = 0; b0 < batch; b0 += kOneAnswerClips) {
     const int nb = std::min(kOneAnswerClips, batch - b0);
-    BatchCall call(h, pcm + b0, n + b0, nb, opts, cancel);
+    BatchCall call(h, pcm + b0, n + b0, nb, opts, cancel, progress, progress_user);
     int rc = call.prepare();
     if (rc == CRISPY_OK) rc = call.run();
     if (rc != CRISPY_OK) {                   // (the call object owns every result it made; the earlier turns' are given back)

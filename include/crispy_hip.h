@@ -55,7 +55,7 @@ typedef enum crispy_status {
   CRISPY_ERR_OOM = -4,
   CRISPY_ERR_BAD_MODEL = -5,
   CRISPY_ERR_UNSUPPORTED = -6,
-  CRISPY_ERR_CANCELLED = -7 /* crispy_asr_transcribe_recording: the caller's cancel flag was set; no result */
+  CRISPY_ERR_CANCELLED = -7 /* crispy_asr_transcribe_recording / _hooks: the caller's cancel flag was set; no result */
 } crispy_status;
 
 #define CRISPY_RN_FRAME_SIZE 480      /* nnnoiseless::FRAME_SIZE (audio.rs:4) */
@@ -449,9 +449,21 @@ int crispy_mel_compute(crispy_mel *h, const float *pcm, long pcm_stride, const i
 int crispy_mel_compute_device(crispy_mel *h, const float *d_pcm, long pcm_stride,
                               const int *n_samples, int batch, float *d_out, float *d_out_t,
                               void *hip_stream);
-/* Later 30 s windows of the clips of the LAST crispy_mel_compute_device call (whisper_full's seek loop): output
- * k is clip clip_idx[k] starting at mel frame seek[k] (0..3000; both host arrays), normalised with that clip's
- * maximum; frames past the end of the computed range are zero padding.  Same output layouts. */
+/* Clips of any length, as whisper.cpp computes the log-mel of a whole recording ONCE before whisper_full's seek loop:
+ * reflect-pad 200 in front, 30 s of zeros + 200 behind, (n + 480000) / 160 frames, one maximum over all of them.
+ * DEVICE pcm rows, n_samples[batch] a host array with 1 .. CRISPY_ASR_MAX_SAMPLES each (2 h at 16 kHz: the sample
+ * indices stay below 2^31).  The call keeps the un-normalised frames and the maximum of every clip in the handle and
+ * writes no window itself: crispy_mel_window_device reads them.  One clip at the cap holds 230 MB (80 mel bins) or
+ * 369 MB (128) of frames; on CRISPY_ERR_OOM the handle still holds what it held.  A clip of <= 480000 samples gives
+ * the same window bits here as through crispy_mel_compute_device, whatever its neighbours. */
+#define CRISPY_ASR_MAX_SAMPLES 115200000
+int crispy_mel_compute_long_device(crispy_mel *h, const float *d_pcm, long pcm_stride, const int *n_samples,
+                                   int batch, void *hip_stream);
+/* 30 s windows of the clips of the LAST crispy_mel_compute_device or crispy_mel_compute_long_device call
+ * (whisper_full's seek loop): output k is clip clip_idx[k] starting at mel frame seek[k] (both host arrays), clamped to
+ * that clip's maximum - 8, then (x + 4) / 4; frames past the audio are the zero padding.  seek[k] is 0..3000 after
+ * crispy_mel_compute[_device] (clips of <= 30 s) and 0 .. n_len_org = 1 + (n - 200) / 160 of the clip after
+ * crispy_mel_compute_long_device.  Same output layouts. */
 int crispy_mel_window_device(crispy_mel *h, const int *clip_idx, const int *seek, int n, float *d_out,
                              float *d_out_t, void *hip_stream);
 int crispy_mel_synchronize(crispy_mel *h);
@@ -744,15 +756,20 @@ typedef struct crispy_asr_result {
                                 scalar / pointer field types every binding of this header mirrors) */
 } crispy_asr_result;
 
-/* engine.transcribe(&audio, &TranscribeOptions::default()) for ONE chunk of <= 480000 samples
- * (16 kHz f32, host).  n == 0 returns an empty result (transcription.rs:175-177), and so does a chunk of fewer than
+/* engine.transcribe(&audio, &TranscribeOptions::default()) for ONE recording of any length up to
+ * CRISPY_ASR_MAX_SAMPLES (16 kHz f32, host): ONE whisper_full over all of it -- the log-mel of the whole recording with
+ * one maximum, then 30 s windows that advance to the last closed timestamp pair and carry the text so far; what
+ * whisper.cpp does with audio of more than 30 s, and NOT the hard 30 s cuts of crispy_asr_transcribe_recording below.
+ * Language detection and the first window's no-speech probability see the first 30 s, as upstream.  With
+ * opts->no_timestamps (one window by definition) more than 480000 samples are CRISPY_ERR_UNSUPPORTED.  n == 0 returns an empty result (transcription.rs:175-177), and so does a chunk of fewer than
  * 10 mel frames (100 ms; the frame count is 1 + (n - 200) / 160, i.e. 2999 for a full chunk): whisper.cpp's whisper_full
  * refuses it and yields no segments [UPSTREAM-RECALL: delta_min, n_len_org].  Needs a model
  * loaded from a file (vocabulary) for text; tokens are always returned.  opts == NULL is
  * TranscribeOptions::default(): language auto-detected, transcribe, timestamps on. */
 int crispy_asr_transcribe(crispy_asr *h, const float *pcm16k, size_t n, const crispy_asr_opts *opts,
                           crispy_asr_result **out);
-/* The same for `batch` chunks at once (pcm[i]: host pointer to n[i] <= 480000 samples, n[i] == 0 allowed):
+/* The same for `batch` clips at once (pcm[i]: host pointer to n[i] <= CRISPY_ASR_MAX_SAMPLES samples, n[i] == 0 allowed;
+ * lengths may be mixed, a clip that has run out of audio leaves the lock step):
  * one log-mel + encoder + language-detection + decoder pass over all clips (more than 512: in turns of 512).  results[batch]
  * receives one library-owned result per clip (free each); on failure every results[i] is NULL.  A clip's result is the result
  * of crispy_asr_transcribe on it alone, bit for bit, whatever the batch (every precision mode, every model width). */
@@ -780,6 +797,14 @@ typedef void (*crispy_asr_progress_fn)(size_t samples_done, size_t samples_total
 int crispy_asr_transcribe_recording(crispy_asr *h, const float *pcm16k, size_t n, const crispy_asr_opts *opts,
                                     int max_batch, const volatile int *cancel_flag, crispy_asr_progress_fn progress,
                                     void *progress_user, crispy_asr_result **out);
+/* crispy_asr_transcribe (ONE whisper_full over the whole audio, any length) with the same two hooks, as whisper.cpp's
+ * whisper_full has them [UPSTREAM-RECALL: whisper_full_params abort_callback / progress_callback]: cancel_flag is polled
+ * before every window of the seek loop (non-zero: CRISPY_ERR_CANCELLED, no result), progress is called on the calling
+ * thread after every window with (samples behind the seek position, n, progress_user) and once more with (n, n) when the
+ * audio is used up.  Both nullable; with both NULL this is crispy_asr_transcribe. */
+int crispy_asr_transcribe_hooks(crispy_asr *h, const float *pcm16k, size_t n, const crispy_asr_opts *opts,
+                                const volatile int *cancel_flag, crispy_asr_progress_fn progress, void *progress_user,
+                                crispy_asr_result **out);
 
 /* Stage entry points of the word-level alignment (crispy_asr_opts::dtw_token_timestamps), for tests and profiling.
  *   crispy_asr_align_device: one teacher-forced decoder pass and the alignment matrix of `batch` clips.
