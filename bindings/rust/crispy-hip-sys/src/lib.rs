@@ -280,6 +280,12 @@ extern "C" {
     pub fn crispy_asr_free_result(r: *mut crispy_asr_result);
     pub fn crispy_asr_align_device(h: *mut crispy_asr, d_enc: *const c_float, batch: c_int, tokens: *const c_int, n_tokens: *const c_int, ld_tokens: c_int, n_sot: c_int, n_frames: *const c_int, heads: *const c_int, n_heads: c_int, d_probs: *mut c_float, d_matrix: *mut c_float, jump_times: *mut c_float) -> c_int;
     pub fn crispy_asr_dtw_device(h: *mut crispy_asr, d_x: *const c_float, n_rows: c_int, n_cols: c_int, ld: c_long, text_idx: *mut c_int, time_idx: *mut c_int, n_path: *mut c_int) -> c_int;
+    pub fn crispy_asr_set_confidence(h: *mut crispy_asr, on: c_int) -> c_int;
+    pub fn crispy_asr_result_token_probs(r: *const crispy_asr_result, plog: *mut *const c_float, p_forced: *mut *const c_float, n: *mut c_int) -> c_int;
+    pub fn crispy_asr_result_word_probs(r: *const crispy_asr_result, prob: *mut *const c_float, n: *mut c_int) -> c_int;
+    pub fn crispy_asr_result_language_probs(r: *const crispy_asr_result, probs: *mut *const c_float, n_lang: *mut c_int) -> c_int;
+    pub fn crispy_asr_detect_language_probs_device(h: *mut crispy_asr, d_enc: *const c_float, batch: c_int, lang_tokens_out: *mut c_int, probs_out: *mut c_float) -> c_int;
+    pub fn crispy_asr_token_probs_device(h: *mut crispy_asr, d_enc: *const c_float, batch: c_int, tokens: *const c_int, n_tokens: *const c_int, ld_tokens: c_int, n_sot: c_int, logp_out: *mut c_float) -> c_int;
     pub fn crispy_asr_transcribe_recording(h: *mut crispy_asr, pcm16k: *const c_float, n: usize, opts: *const crispy_asr_opts, max_batch: c_int, cancel_flag: *const c_int, progress: crispy_asr_progress_fn, progress_user: *mut c_void, out: *mut *mut crispy_asr_result) -> c_int;
     pub fn crispy_asr_transcribe_hooks(h: *mut crispy_asr, pcm16k: *const c_float, n: usize, opts: *const crispy_asr_opts, cancel_flag: *const c_int, progress: crispy_asr_progress_fn, progress_user: *mut c_void, out: *mut *mut crispy_asr_result) -> c_int;
 
@@ -640,6 +646,16 @@ pub struct Transcript {
     pub token_times: Option<Vec<f32>>,
     /// With `dtw_token_timestamps`: the words, seconds relative to the chunk.
     pub words: Vec<Word>,
+    /// Timestamp mode: the log-probability of every token under the distribution it was picked from (whisper.cpp's `plog`),
+    /// parallel to `tokens` -- the addends of its window's `avg_logprob`.  `None` with `no_timestamps`.
+    pub token_logprobs: Option<Vec<f32>>,
+    /// `set_confidence(true)` + `dtw_token_timestamps`: openai-whisper's `text_token_probs`, the probability of every token in
+    /// the teacher-forced alignment pass (-1 for timestamp tokens), parallel to `tokens`.
+    pub token_probs_forced: Option<Vec<f32>>,
+    /// `set_confidence(true)` + `dtw_token_timestamps`: openai-whisper's word `probability`, parallel to `words`.
+    pub word_probs: Option<Vec<f32>>,
+    /// `set_confidence(true)` + auto-detection: whisper.cpp's `lang_probs`; entry i belongs to language token `lang0 + i`.
+    pub language_probs: Option<Vec<f32>>,
 }
 /// One word of a transcript (`dtw_token_timestamps`).
 #[derive(Debug, Clone, PartialEq)]
@@ -687,6 +703,38 @@ impl GpuWhisperEngine {
     /// attention), opt-in and slower.
     pub fn set_precision(&mut self, mode: i32) -> Result<(), CrispyError> {
         check(unsafe { crispy_asr_set_precision(self.h, mode as c_int) })
+    }
+    /// From the next transcribe call on, transcripts carry `language_probs` and -- with `dtw_token_timestamps` --
+    /// `token_probs_forced` and `word_probs` (`token_logprobs` needs no switch).  Off (the default): nothing extra runs.
+    pub fn set_confidence(&mut self, on: bool) -> Result<(), CrispyError> {
+        check(unsafe { crispy_asr_set_confidence(self.h, on as c_int) })
+    }
+    /// `crispy_asr_detect_language_probs_device` on `batch` encoder outputs in device memory: the language token per clip
+    /// and the distribution over the vocabulary's `n_lang` languages, `[batch][n_lang]` (empty for an English-only model).
+    /// SAFETY: `d_enc` is a device pointer to `batch` encoder outputs of this model (`crispy_asr_encode_device`).
+    pub unsafe fn detect_language_probs_device(&mut self, d_enc: *const f32, batch: usize) -> Result<(Vec<i32>, Vec<f32>), CrispyError> {
+        let mut sp = crispy_asr_specials::default();
+        check(crispy_asr_vocab_specials(self.n_vocab(), &mut sp))?;
+        let mut tok = vec![0 as c_int; batch];
+        let mut probs = vec![0f32; batch * sp.n_lang as usize];
+        let pp = if probs.is_empty() { std::ptr::null_mut() } else { probs.as_mut_ptr() };
+        check(crispy_asr_detect_language_probs_device(self.h, d_enc, batch as c_int, tok.as_mut_ptr(), pp))?;
+        Ok((tok, probs))
+    }
+    /// `crispy_asr_token_probs_device`: `rows[b]` = clip b's token rows (sot sequence of `n_sot` ids, `<|notimestamps|>`, text,
+    /// `<|endoftext|>`); returns per clip the LOG-probability of every text token given the rows before it.
+    /// SAFETY: `d_enc` is a device pointer to `rows.len()` encoder outputs of this model.
+    pub unsafe fn token_probs_device(&mut self, d_enc: *const f32, rows: &[Vec<i32>], n_sot: usize) -> Result<Vec<Vec<f32>>, CrispyError> {
+        let ld = rows.iter().map(|r| r.len()).max().unwrap_or(0);
+        let mut tok = vec![0 as c_int; rows.len() * ld];
+        for (b, r) in rows.iter().enumerate() {
+            tok[b * ld..b * ld + r.len()].copy_from_slice(r);
+        }
+        let n_tok: Vec<c_int> = rows.iter().map(|r| r.len() as c_int).collect();
+        let mut lp = vec![0f32; rows.len() * ld];
+        check(crispy_asr_token_probs_device(self.h, d_enc, rows.len() as c_int, tok.as_ptr(), n_tok.as_ptr(), ld as c_int, n_sot as c_int,
+                                            lp.as_mut_ptr()))?;
+        Ok(rows.iter().enumerate().map(|(b, r)| lp[b * ld..b * ld + r.len().saturating_sub(n_sot + 2)].to_vec()).collect())
     }
     /// Audio of any length up to `CRISPY_ASR_MAX_SAMPLES` (16 kHz, f32 in +-1) through ONE `whisper_full`: the log-mel of
     /// the whole recording, then 30 s windows that advance to the last closed timestamp pair and carry the text so far --
@@ -807,7 +855,17 @@ unsafe fn take_result(r: *mut crispy_asr_result) -> Transcript {
     } else {
         Vec::new()
     };
-    let out = Transcript { text, segments, tokens, language_token: res.language_token, windows, token_times, words };
+    // the confidence arrays live behind the public prefix: NULL = not computed in this call (a present, empty array is non-NULL)
+    let copy = |p: *const c_float, n: c_int| if p.is_null() { None } else if n > 0 { Some(std::slice::from_raw_parts(p, n as usize).to_vec()) } else { Some(Vec::new()) };
+    let (mut plog, mut forced, mut wprob, mut lprob) = (std::ptr::null(), std::ptr::null(), std::ptr::null(), std::ptr::null());
+    let (mut n_tok, mut n_word, mut n_lang) = (0 as c_int, 0 as c_int, 0 as c_int);
+    let ok = crispy_asr_result_token_probs(r, &mut plog, &mut forced, &mut n_tok) == CRISPY_OK
+        && crispy_asr_result_word_probs(r, &mut wprob, &mut n_word) == CRISPY_OK
+        && crispy_asr_result_language_probs(r, &mut lprob, &mut n_lang) == CRISPY_OK;
+    let (token_logprobs, token_probs_forced, word_probs, language_probs) =
+        if ok { (copy(plog, n_tok), copy(forced, n_tok), copy(wprob, n_word), copy(lprob, n_lang)) } else { (None, None, None, None) };
+    let out = Transcript { text, segments, tokens, language_token: res.language_token, windows, token_times, words, token_logprobs,
+                           token_probs_forced, word_probs, language_probs };
     crispy_asr_free_result(r);
     out
 }

@@ -190,6 +190,35 @@ class WhisperModel:
         self._ck(self._L.crispy_asr_detect_language_device(self._h, d_enc, batch, out.ctypes.data))
         return out
 
+    def detect_language_probs_device(self, d_enc: int, batch: int):
+        """`crispy_asr_detect_language_probs_device`: (language token per clip, probabilities [batch, n_lang]) -- whisper.cpp's
+        lang_probs, the soft-max of the detection logits over the language tokens; n_lang = 0 for an English-only vocabulary."""
+        n_lang = int(N.vocab_specials(self.hp.n_vocab).n_lang)
+        out = np.empty(batch, dtype=np.int32)
+        probs = np.full((batch, n_lang), np.nan, dtype=np.float32)
+        self._ck(self._L.crispy_asr_detect_language_probs_device(self._h, C.c_void_p(d_enc), batch, out.ctypes.data,
+                                                                 probs.ctypes.data if n_lang else None))
+        return out, probs
+
+    def set_confidence(self, on: bool = True):
+        """`crispy_asr_set_confidence`: from the next transcribe call on, results carry the language distribution and -- with
+        dtw=True -- the teacher-forced token and word probabilities (`_read_confidence`)."""
+        self._ck(self._L.crispy_asr_set_confidence(self._h, 1 if on else 0))
+
+    def token_probs_device(self, d_enc: int, rows, n_sot: int, ld_tokens: int = 0) -> np.ndarray:
+        """`crispy_asr_token_probs_device`: rows as for `align_device` -> log-probabilities [batch][ld_tokens] (f32; entry i of
+        clip b is text token i of its row given everything before it, entries 0 .. len(row) - n_sot - 3 are set, the rest NaN)."""
+        b = len(rows)
+        ld = int(ld_tokens) or max(len(r) for r in rows)
+        tok = np.zeros((b, ld), np.int32)
+        for i, r in enumerate(rows):
+            tok[i, :len(r)] = r
+        n_tok = np.array([len(r) for r in rows], np.int32)
+        lp = np.full((b, ld), np.nan, np.float32)
+        self._ck(self._L.crispy_asr_token_probs_device(self._h, C.c_void_p(d_enc), b, tok.ctypes.data, n_tok.ctypes.data, ld,
+                                                       int(n_sot), lp.ctypes.data))
+        return lp
+
     def decode_greedy_lang_device(self, d_enc: int, batch: int, prompt, lang_tokens, max_new: int):
         p = np.ascontiguousarray(prompt, dtype=np.int32)
         lt = np.ascontiguousarray(lang_tokens, dtype=np.int32)
@@ -341,6 +370,7 @@ class WhisperEngine(WhisperModel):
         try:
             text, tokens, self.last_language_token, self.last_segments, self.last_windows = _read_result(res)
             self.last_token_times, self.last_words = _read_alignment(res)
+            self.last_confidence = _read_confidence(res)
         finally:
             self._L.crispy_asr_free_result(res)
         return text, tokens
@@ -405,9 +435,45 @@ def _read_alignment(res) -> tuple:
     return times, words
 
 
+def _read_confidence(res) -> dict:
+    """The confidence arrays of a result (`crispy_asr_result_{token,word,language}_probs`), each a float32 array or None:
+    plog [n_tokens] (timestamp mode), p_forced [n_tokens] and word_probs [n_words] (set_confidence + dtw), lang_probs [n_lang]
+    (set_confidence + auto-detection)."""
+    L = N.lib()
+    FP = C.POINTER(C.c_float)
+    arr = lambda p, n: (np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.float32)) if p else None
+    plog, forced, wp, lp, n, nw, nl = FP(), FP(), FP(), FP(), C.c_int(), C.c_int(), C.c_int()
+    for rc in (L.crispy_asr_result_token_probs(res, C.byref(plog), C.byref(forced), C.byref(n)),
+               L.crispy_asr_result_word_probs(res, C.byref(wp), C.byref(nw)),
+               L.crispy_asr_result_language_probs(res, C.byref(lp), C.byref(nl))):
+        if rc != 0:
+            raise RuntimeError(f"confidence accessor failed: {L.crispy_last_error().decode()}")
+    return {"plog": arr(plog, n.value), "p_forced": arr(forced, n.value), "word_probs": arr(wp, nw.value), "lang_probs": arr(lp, nl.value),
+            "n": n.value, "n_words": nw.value, "n_lang": nl.value}
+
+
+def transcribe_words_with_confidence(engine: "WhisperEngine", audio: np.ndarray, chunk_offset_seconds: float = 0.0,
+                                     max_new_tokens: int = 0, dtw_heads=None):
+    """`transcribe_with_timestamps(words=True)` with openai-whisper's word `probability`: one (offset + t0, offset + t1, word,
+    prob) per word.  Switches the engine's confidence on for the call and back off afterwards."""
+    a = np.ascontiguousarray(audio, dtype=np.float32).ravel()
+    if a.size == 0:
+        return []
+    engine.set_confidence(True)
+    try:
+        text, _ = engine.transcribe(a, max_new_tokens, timestamps=True, dtw=True, dtw_heads=dtw_heads)
+    finally:
+        engine.set_confidence(False)
+    if not text.strip():
+        return []
+    off = float(chunk_offset_seconds)
+    wp = engine.last_confidence["word_probs"]
+    return [(off + t0, off + t1, w, float(wp[i])) for i, (t0, t1, w, _f, _n) in enumerate(engine.last_words)]
+
+
 def transcribe_batch(engine: "WhisperEngine", clips, max_new_tokens: int = 0, language_token: int = 0,
                      timestamps: bool = False, with_segments: bool = False, prev_text: bool = True, with_words: bool = False,
-                     **decision):
+                     with_confidence: bool = False, **decision):
     """`crispy_asr_transcribe_batch`: a list of clips (any lengths up to MAX_SAMPLES, mixed and empty allowed; more than
     30 s needs timestamps=True) -> [(text, tokens, language)]
     (+ segments and window decisions with with_segments; + token times and words, `_read_alignment`, with with_words --
@@ -425,7 +491,8 @@ def transcribe_batch(engine: "WhisperEngine", clips, max_new_tokens: int = 0, la
         try:
             full = _read_result(r)
             full = full if with_segments else full[:3]
-            out.append(full + _read_alignment(r) if with_words else full)
+            full = full + _read_alignment(r) if with_words else full
+            out.append(full + (_read_confidence(r),) if with_confidence else full)   # (a trailing dict: the shapes above stay)
         finally:
             engine._L.crispy_asr_free_result(r)
     return out
@@ -452,7 +519,7 @@ class Cancelled(Exception):
 
 def transcribe_recording(engine: "WhisperEngine", pcm16k: np.ndarray, max_new_tokens: int = 0, timestamps: bool = False,
                          max_batch: int = 0, cancel=None, progress=None, with_result: bool = False, with_words: bool = False,
-                         **decision):
+                         with_confidence: bool = False, **decision):
     """`crispy_asr_transcribe_recording`: the same chunk loop with the chunks decoded side by side, `max_batch` (0 = 128) per
     engine call -- an hour of audio is one call instead of 120 -- and the reference's two hooks:
     cancel: a `ctypes.c_int` another thread (or the progress callback) sets non-zero -> raises `Cancelled`;
@@ -472,6 +539,8 @@ def transcribe_recording(engine: "WhisperEngine", pcm16k: np.ndarray, max_new_to
         full = _read_result(res)
         if with_words:
             full = full + _read_alignment(res)
+        if with_confidence:
+            full = full + (_read_confidence(res),)
     finally:
         engine._L.crispy_asr_free_result(res)
     return full if with_result else full[0]

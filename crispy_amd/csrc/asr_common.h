@@ -383,6 +383,13 @@ struct BeamArgs {
 hipError_t beam_advance(const BeamArgs& a, int n_clips, hipStream_t s);
 // p_out[b] = softmax(logits[b])[token] over the whole, unfiltered row (whisper_full's no_speech_prob)
 hipError_t softmax_prob_f32(const float* logits, int V, long ld, int token, float* p_out, int B, hipStream_t s);
+// ---- confidence (whisper_conf.hip) ----
+// Row r of `rows` logits rows is position pos + r % P of clip r / P (a multi-position prompt step).  logp[clip][ld_t] at that
+// position = log soft-max over ids < n_cols of the row, at target[clip][ld_t] of that position; target < 0: skipped.  ld % 4 == 0.
+hipError_t tok_logprob_f32(const float* logits, long ld, int n_cols, const int* target, float* logp, int ld_t, int P, int pos,
+                           int rows, hipStream_t s);
+// probs[r][n_lang] = soft-max over ids [lang0, lang0 + n_lang) of row r; n_lang <= 128
+hipError_t lang_probs_f32(const float* logits, long ld, int lang0, int n_lang, float* probs, int rows, hipStream_t s);
 
 hipError_t argmax_f32(const float* logits, const unsigned char* mask, const unsigned char* mask_first,
                       const int* step_dev, int V, long ld, int* tokens_out, int* tokens_all, float* best, int B, hipStream_t s,

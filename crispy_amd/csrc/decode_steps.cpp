@@ -76,15 +76,17 @@ int reserve_dec(crispy_asr* h, int batch, int xclips) {
 // k|v of the self-attention block from one launch and, in mode 0, folds the preceding LayerNorm in
 bool folded(const crispy_asr* h, int rows) { return rows <= SKINNY_MAX_M && h->hp.n_text_state % 128 == 0; }
 
-// the last block of a decoder step: final LayerNorm and vocabulary projection of h->dw.dx into h->dw.logits
-int decoder_logits(crispy_asr* h, int batch, hipStream_t s, const float* x = nullptr) {
+// the last block of a decoder step: final LayerNorm and vocabulary projection of h->dw.dx into h->dw.logits (`out`: into
+// other rows of the same stride -- the teacher-forced rows of a confidence pass, which are more than h->dw.logits holds)
+int decoder_logits(crispy_asr* h, int batch, hipStream_t s, const float* x = nullptr, float* out = nullptr) {
   const int dt = h->hp.n_text_state, V = h->hp.n_vocab;
   if (!x) x = h->dw.dx;
+  if (!out) out = h->dw.logits;
   const bool fold = folded(h, batch);
   if (h->enc_precision == 1 && h->tok_emb_hp) {
     // the reference's arithmetic: final LayerNorm in f32, rounded to f16, against the f16 embedding, f32 accumulation
     HIP_TRY(layernorm_f16out(x, h->dec_ln_w, h->dec_ln_b, h->dw.dxn, batch, dt, s));
-    HIP_TRY(vocab_f16(h->dw.dxn, dt, h->tok_emb_hp, h->dw.logits, logits_ld(h), batch, V, dt, s));
+    HIP_TRY(vocab_f16(h->dw.dxn, dt, h->tok_emb_hp, out, logits_ld(h), batch, V, dt, s));
   } else {
     // Vocabulary projection in f32: LayerNorm launch + the 128 x 128 tiled kernel for every batch size.  (Up to 64 clips a
     // persistent LayerNorm-folded kernel, gemm_vocab_f32_kernel, used to run instead -- ~7 us faster per step, but other
@@ -92,7 +94,7 @@ int decoder_logits(crispy_asr* h, int batch, hipStream_t s, const float* x = nul
     // the batch it was decoded in.  Mode 0 is the mode the parity claims are made in; one path keeps "alone = in any
     // batch" exact there too.)
     HIP_TRY(layernorm_f32(x, h->dec_ln_w, h->dec_ln_b, h->dw.dxn, batch, dt, s));
-    GemmArgs g = gemm(h->dw.dxn, dt, h->tok_emb, dt, h->dw.logits, logits_ld(h), nullptr, batch, V, dt);
+    GemmArgs g = gemm(h->dw.dxn, dt, h->tok_emb, dt, out, logits_ld(h), nullptr, batch, V, dt);
     g.tiled = fold ? 1 : 0;
     HIP_TRY(gemm_f32_nt(g, 1, s));
   }
@@ -540,6 +542,12 @@ int prompt_step(crispy_asr* h, const DecodePass& p, int pos, int P, bool want_lo
     int rc = layer_self_block(c, l);
     if (rc == CRISPY_OK) rc = layer_cross_and_mlp(c, l);
     if (rc != CRISPY_OK) return rc;
+  }
+  if (h->conf.on) {      // a confidence pass: every row of the step predicts the id after it (openai's text_token_probs)
+    if (c.rows > SKINNY_MAX_M) return fail(CRISPY_ERR_INVALID_ARG, "prompt_step: %d rows exceed the confidence rows", c.rows);
+    const int rc = decoder_logits(h, c.rows, s, h->dw.dx, h->conf.logits);
+    if (rc != CRISPY_OK) return rc;
+    HIP_TRY(g_conf_kernels->tok_logprob(h->conf.logits, logits_ld(h), h->eot, h->conf.target, h->conf.logp, h->conf.rows, P, pos, c.rows, s));      // (conf_begin checked the table)
   }
   if (!want_logits) return CRISPY_OK;
   if (P == 1) return decoder_logits(h, clips, s);
@@ -1024,6 +1032,86 @@ int generation_body(crispy_asr* h, const DecodePass& pass, hipStream_t s) {
   return token_step(h, pass, s);
 }
 
+// whisper.cpp `whisper_lang_auto_detect`: feed <|startoftranscript|> alone and take the most probable language token; its
+// `lang_probs` are the soft-max of the same logits over the language tokens only [UPSTREAM-RECALL].  (The caller has checked
+// the arguments; `who` names the entry point in a message.)
+int detect_language(crispy_asr* h, const char* who, const float* d_enc, int batch, int* lang_tokens_out, float* probs_out) {
+  if (h->hp.n_vocab < 51865) return fail(CRISPY_ERR_UNSUPPORTED, "%s: English-only vocabulary", who);
+  if (probs_out && !g_conf_kernels) return fail(CRISPY_ERR_UNSUPPORTED, "%s: this build has no confidence kernels", who);
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  int rc = reserve_dec(h, batch);
+  if (rc != CRISPY_OK) return rc;
+  const int V = h->hp.n_vocab;
+  rc = compute_cross_kv(h, d_enc, batch, s);
+  if (rc != CRISPY_OK) return rc;
+  const int sot = h->eot + 1, n_lang = 99 + (V - 51865);
+  std::vector<int> tok(batch, sot);
+  HIP_TRY(hipMemcpyAsync(h->dw.tok, tok.data(), sizeof(int) * batch, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  rc = prompt_step(h, DecodePass{batch, 1, 1, nullptr}, 0, 1, true, s);      // a pass of one position
+  if (rc != CRISPY_OK) return rc;
+  if (!h->d_lang_mask) {
+    std::vector<unsigned char> m(V, 1);
+    for (int t = sot + 1; t < sot + 1 + n_lang && t < V; ++t) m[t] = 0;
+    rc = upload_mask(h->d_lang_mask, m);
+    if (rc != CRISPY_OK) return rc;
+  }
+  HIP_TRY(argmax_f32(h->dw.logits, h->d_lang_mask, nullptr, nullptr, V, logits_ld(h), h->dw.tok, nullptr, nullptr, batch, s));
+  HIP_TRY(hipMemcpyAsync(lang_tokens_out, h->dw.tok, sizeof(int) * batch, hipMemcpyDeviceToHost, s));
+  if (probs_out) {
+    HIP_TRY(h->conf.lang.grow((size_t)batch * n_lang * sizeof(float)));
+    HIP_TRY(g_conf_kernels->lang_probs(h->dw.logits, logits_ld(h), sot + 1, n_lang, h->conf.lang, batch, s));
+    HIP_TRY(hipMemcpyAsync(probs_out, h->conf.lang, sizeof(float) * batch * n_lang, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  return CRISPY_OK;
+}
+
+const ConfKernels* g_conf_kernels = nullptr;
+
+int conf_begin(crispy_asr* h, const int* tok_mat, int batch, int n_rows, const int* row_len, int n_sot, hipStream_t s) {
+  if (!g_conf_kernels) return fail(CRISPY_ERR_UNSUPPORTED, "token probabilities: this build has no confidence kernels");
+  if (batch < 1 || batch > SKINNY_MAX_M)
+    return fail(CRISPY_ERR_INVALID_ARG, "token probabilities: %d clips in one pass; 1 .. %d", batch, SKINNY_MAX_M);
+  std::vector<int> target((size_t)batch * n_rows, -1);
+  for (int b = 0; b < batch; ++b) {
+    const int off = n_rows - row_len[b];
+    for (int q = n_sot; q <= row_len[b] - 3; ++q) {
+      const int t = tok_mat[(size_t)b * n_rows + off + q + 1];
+      if (t >= h->eot) return fail(CRISPY_ERR_INVALID_ARG, "token probabilities: row %d of clip %d is the special token %d, not text", q + 1, b, t);
+      target[(size_t)b * n_rows + off + q] = t;
+    }
+  }
+  ConfWs& w = h->conf;
+  if (!w.logits) HIP_TRY(w.logits.alloc((size_t)SKINNY_MAX_M * logits_ld(h) * sizeof(float)));
+  HIP_TRY(w.target.grow(target.size() * sizeof(int)));
+  HIP_TRY(w.logp.grow(target.size() * sizeof(float)));
+  HIP_TRY(hipMemcpyAsync(w.target, target.data(), target.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(w.logp, 0, target.size() * sizeof(float), s));
+  HIP_TRY(hipStreamSynchronize(s));      // `target` is this frame's
+  w.rows = n_rows;
+  w.on = true;
+  return CRISPY_OK;
+}
+
+void conf_end(crispy_asr* h) {
+  h->conf.on = false;
+  h->conf.rows = 0;
+}
+
+int conf_read(crispy_asr* h, int batch, int n_rows, const int* row_len, int n_sot, hipStream_t s, std::vector<std::vector<float>>* logp) {
+  std::vector<float> all((size_t)batch * n_rows);
+  HIP_TRY(hipMemcpyAsync(all.data(), h->conf.logp, all.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  logp->assign((size_t)batch, {});
+  for (int b = 0; b < batch; ++b) {
+    const int n = std::max(0, row_len[b] - n_sot - 2);
+    const float* src = all.data() + (size_t)b * n_rows + (n_rows - row_len[b]) + n_sot;
+    (*logp)[b].assign(src, src + n);
+  }
+  return CRISPY_OK;
+}
 
 }  // namespace asr
 }  // namespace crispy
@@ -1199,31 +1287,69 @@ int crispy_asr_detect_language_device(crispy_asr* h, const float* d_enc, int bat
   if (batch < 0) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_detect_language_device: batch < 0");
   if (batch == 0) return CRISPY_OK;
   if (!d_enc || !lang_tokens_out) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_detect_language_device: NULL argument");
-  if (h->hp.n_vocab < 51865) return fail(CRISPY_ERR_UNSUPPORTED, "crispy_asr_detect_language_device: English-only vocabulary");
+  return detect_language(h, "crispy_asr_detect_language_device", d_enc, batch, lang_tokens_out, nullptr);
+} CRISPY_CATCH_RET("crispy_asr_detect_language_device")
+
+// crispy_asr_detect_language_device plus whisper.cpp's lang_probs: probs_out host [batch][n_lang].  An English-only
+// vocabulary has no languages to weigh (n_lang 0): nothing runs, the tokens are 0, the status is OK.
+int crispy_asr_detect_language_probs_device(crispy_asr* h, const float* d_enc, int batch, int* lang_tokens_out, float* probs_out) try {
+  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_detect_language_probs_device: NULL handle");
+  if (!h->finalized) return fail(CRISPY_ERR_BAD_MODEL, "crispy_asr_detect_language_probs_device: model not finalized");
+  if (batch < 0) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_detect_language_probs_device: batch < 0");
+  if (batch == 0) return CRISPY_OK;
+  if (!d_enc || !lang_tokens_out) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_detect_language_probs_device: NULL argument");
+  if (h->hp.n_vocab < 51865) {
+    std::fill(lang_tokens_out, lang_tokens_out + batch, 0);
+    return CRISPY_OK;
+  }
+  if (!probs_out) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_detect_language_probs_device: probs_out is NULL");
+  return detect_language(h, "crispy_asr_detect_language_probs_device", d_enc, batch, lang_tokens_out, probs_out);
+} CRISPY_CATCH_RET("crispy_asr_detect_language_probs_device")
+
+int crispy_asr_set_confidence(crispy_asr* h, int on) try {
+  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_set_confidence: NULL handle");
+  h->confidence = on != 0;
+  return CRISPY_OK;
+} CRISPY_CATCH_RET("crispy_asr_set_confidence")
+
+// The teacher-forced pass of crispy_asr_align_device without the alignment: the log-probability of every text token of
+// `tokens` rows (sot sequence, <|notimestamps|>, text, <|endoftext|>) given the rows before it, soft-max over ids < eot.
+int crispy_asr_token_probs_device(crispy_asr* h, const float* d_enc, int batch, const int* tokens, const int* n_tokens, int ld_tokens,
+                                  int n_sot, float* logp_out) try {
+  if (!h || !d_enc || batch <= 0 || !tokens || !n_tokens || !logp_out || ld_tokens <= 0)
+    return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_token_probs_device: NULL argument or empty batch");
+  if (!h->finalized) return fail(CRISPY_ERR_BAD_MODEL, "crispy_asr_token_probs_device: model not finalized");
+  if (n_sot < 1) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_token_probs_device: n_sot %d", n_sot);
+  if (batch > SKINNY_MAX_M) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_token_probs_device: batch %d > %d", batch, SKINNY_MAX_M);
+  const int C = h->hp.n_text_ctx;
+  std::vector<std::vector<int>> rows((size_t)batch);
+  std::vector<int> len((size_t)batch);
+  for (int b = 0; b < batch; ++b) {
+    const int R = n_tokens[b];
+    if (R < n_sot + 2 || R > ld_tokens || R > C)
+      return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_token_probs_device: clip %d has %d token rows (%d ... %d)", b, R, n_sot + 2, std::min(C, ld_tokens));
+    rows[b].assign(tokens + (size_t)b * ld_tokens, tokens + (size_t)b * ld_tokens + R);
+    len[b] = R;
+  }
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  int rc = reserve_dec(h, batch);
+  PassStart ps;                          // the alignment's pass: left padding, one cross K|V per clip, a fixed key bound
+  int rc = begin_pass(h, "token probabilities:", rows, 1, 0, C, true, &ps);
   if (rc != CRISPY_OK) return rc;
-  const int V = h->hp.n_vocab;
-  rc = compute_cross_kv(h, d_enc, batch, s);
+  rc = conf_begin(h, ps.tok_mat.data(), batch, ps.n_rows, len.data(), n_sot, s);
   if (rc != CRISPY_OK) return rc;
-  const int sot = h->eot + 1, n_lang = 99 + (V - 51865);
-  std::vector<int> tok(batch, sot);
-  HIP_TRY(hipMemcpyAsync(h->dw.tok, tok.data(), sizeof(int) * batch, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  rc = prompt_step(h, DecodePass{batch, 1, 1, nullptr}, 0, 1, true, s);      // a pass of one position
-  if (rc != CRISPY_OK) return rc;
-  if (!h->d_lang_mask) {
-    std::vector<unsigned char> m(V, 1);
-    for (int t = sot + 1; t < sot + 1 + n_lang && t < V; ++t) m[t] = 0;
-    rc = upload_mask(h->d_lang_mask, m);
+  {
+    struct Guard { crispy_asr* h; ~Guard() { conf_end(h); } } guard{h};
+    int pos = 0;
+    rc = prefill(h, ps.pass, d_enc, ps.tok_mat.data(), ps.n_rows, s, &pos);
     if (rc != CRISPY_OK) return rc;
   }
-  HIP_TRY(argmax_f32(h->dw.logits, h->d_lang_mask, nullptr, nullptr, V, logits_ld(h), h->dw.tok, nullptr, nullptr, batch, s));
-  HIP_TRY(hipMemcpyAsync(lang_tokens_out, h->dw.tok, sizeof(int) * batch, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  std::vector<std::vector<float>> lp;
+  rc = conf_read(h, batch, ps.n_rows, len.data(), n_sot, s, &lp);
+  if (rc != CRISPY_OK) return rc;
+  for (int b = 0; b < batch; ++b) std::copy(lp[b].begin(), lp[b].end(), logp_out + (size_t)b * ld_tokens);
   return CRISPY_OK;
-} CRISPY_CATCH_RET("crispy_asr_detect_language_device")
+} CRISPY_CATCH_RET("crispy_asr_token_probs_device")
 
 int crispy_asr_transcribe_tokens(crispy_asr* h, const float* pcm, long pcm_stride, const int* n_samples, int batch,
                                  const int* prompt, int n_prompt, int max_new, int* tokens_out, int* n_out) try {

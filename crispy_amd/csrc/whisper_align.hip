@@ -359,9 +359,11 @@ int resolve_heads(const crispy_asr* h, const int* heads, int n_heads, std::vecto
 
 // The whole alignment of `batch` clips: prefill, row statistics, matrix, DTW.  rows[b] = clip b's token rows; heads =
 // resolved (layer, head) pairs.  d_probs / d_matrix_out: the stage entry point's optional outputs ([batch][n_heads][ld_rows]
-// [ld_f] / [batch][ld_rows][ld_f]); time_idx receives the first N entry columns per clip.
+// [ld_f] / [batch][ld_rows][ld_f]); time_idx receives the first N entry columns per clip.  logp (nullable; crispy_asr_set_confidence):
+// the same prefill also projects its rows onto the vocabulary and leaves every text token's log-probability (conf_begin).
 int run_alignment(crispy_asr* h, const float* d_enc, const std::vector<std::vector<int>>& rows, int n_sot, const std::vector<int>& n_frames,
-                  const std::vector<int>& heads, float* d_probs, float* d_matrix_out, int ld_rows, std::vector<std::vector<int>>* time_idx) {
+                  const std::vector<int>& heads, float* d_probs, float* d_matrix_out, int ld_rows, std::vector<std::vector<int>>* time_idx,
+                  std::vector<std::vector<float>>* logp = nullptr) {
   const int batch = (int)rows.size();
   if (batch == 0) return CRISPY_OK;
   const int dt = h->hp.n_text_state, Tn = h->hp.n_audio_ctx, L = h->hp.n_text_layer, C = h->hp.n_text_ctx;
@@ -424,8 +426,11 @@ int run_alignment(crispy_asr* h, const float* d_enc, const std::vector<std::vect
     (void)hipStreamSynchronize(s);      // the uploads above read host vectors of this frame
     return rc;
   }
+  std::vector<int> row_len((size_t)batch);
+  for (int b = 0; b < batch; ++b) row_len[b] = (int)rows[b].size();
+  if (logp && (rc = conf_begin(h, ps.tok_mat.data(), batch, n_rows, row_len.data(), n_sot, s)) != CRISPY_OK) return rc;
   {
-    struct Guard { crispy_asr* h; ~Guard() { h->align.on = false; h->align.rows = 0; } } guard{h};
+    struct Guard { crispy_asr* h; ~Guard() { h->align.on = false; h->align.rows = 0; conf_end(h); } } guard{h};
     A.rows = n_rows;
     A.on = true;
     int pos = 0;
@@ -465,17 +470,18 @@ int run_alignment(crispy_asr* h, const float* d_enc, const std::vector<std::vect
     for (int b = 0; b < batch; ++b)
       (*time_idx)[b].assign(jumps.begin() + (size_t)b * n_rows, jumps.begin() + (size_t)b * n_rows + hc[b].dtw_rows);
   }
+  if (logp) return conf_read(h, batch, n_rows, row_len.data(), n_sot, s, logp);
   return CRISPY_OK;
 }
 
 int align_round(crispy_asr* h, const float* d_enc, const std::vector<std::vector<int>>& rows, int n_sot, const std::vector<int>& n_frames,
-                const std::vector<int>& heads, std::vector<std::vector<int>>& time_idx) {
+                const std::vector<int>& heads, std::vector<std::vector<int>>& time_idx, std::vector<std::vector<float>>* logp) {
   std::vector<int> hv;
   const int rc = resolve_heads(h, heads.empty() ? nullptr : heads.data(), (int)heads.size() / 2, hv);
   if (rc != CRISPY_OK) return rc;
   int ld = 0;
   for (const auto& r : rows) ld = std::max(ld, (int)r.size());
-  return run_alignment(h, d_enc, rows, n_sot, n_frames, hv, nullptr, nullptr, ld, &time_idx);
+  return run_alignment(h, d_enc, rows, n_sot, n_frames, hv, nullptr, nullptr, ld, &time_idx, logp);
 }
 
 [[maybe_unused]] const bool kInstalled = (g_align_round = &align_round, true);

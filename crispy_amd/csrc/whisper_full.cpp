@@ -30,6 +30,12 @@ struct crispy_asr_result_impl {
   std::vector<float> tok_t;
   std::vector<std::string> word_text;
   std::vector<crispy_asr_word> words;      // text pointers filled in by publish
+  // confidence, behind the public prefix (crispy_asr_result_{token,word,language}_probs)
+  bool have_plog = false;                  // timestamp mode: the log-probability of every pick, parallel to tokens
+  std::vector<float> plog;
+  bool have_forced = false;                // crispy_asr_set_confidence + dtw: parallel to tokens (-1: no text token, or not aligned) / to words
+  std::vector<float> p_forced, word_prob;
+  std::vector<float> lang_probs;           // crispy_asr_set_confidence + auto-detection
 };
 
 }  // namespace
@@ -190,6 +196,7 @@ struct WordSpan {
   std::string text;
   int first = 0, n = 0;          // the window's text tokens [first, first + n)
   float t0 = 0.f, t1 = 0.f;
+  float prob = -1.f;             // (confidence) like the times, that of the word it was computed for
 };
 
 // Python's str.isspace for the code points a token can hold (str.strip() in the reference)
@@ -367,6 +374,9 @@ namespace {
 // ---- engine.transcribe for a batch of chunks: one object per call, one short method per step of whisper_full ----
 // (Round 6: this was one 400-line function.  The statements are the same; what each group of them is FOR is now its name.)
 
+// a published probability: the exponential in double, rounded once (a log-probability of -100 gives 0 or a denormal, never NaN)
+float prob_of(float logp) { return (float)std::exp((double)logp); }
+
 // the pass whisper_full ends up accepting for one active clip of a round
 struct Accepted {
   std::vector<int> toks, tids, prompt;
@@ -377,6 +387,7 @@ struct Accepted {
   bool have = false;
   std::vector<int> align;             // dtw_token_timestamps: entry column of <|notimestamps|> and of every text token's row
   bool aligned = false;
+  std::vector<float> logp;            // ... with confidence: teacher-forced log-probability of every text token
 };
 
 // what one decode of a group of clips (n_dec rows each) returned
@@ -438,6 +449,7 @@ class BatchCall {
   bool timestamps = true, detect = false;
   bool long_form = false;              // a clip of more than 30 s: the log-mel of whole clips, kept; every window read from it
   bool dtw = false;                    // opts.dtw_token_timestamps
+  bool conf = false;                   // crispy_asr_set_confidence as the call found it
   std::vector<int> dtw_heads;          // (layer, head) pairs; empty = the default set
   // whisper_full's parameters (0 in crispy_asr_opts = whisper.cpp's default)
   float entropy_thold = 2.4f, logprob_thold = -1.0f, no_speech_thold = 0.6f;
@@ -515,7 +527,12 @@ int BatchCall::prepare() {
                 "samples needs whisper_full's seek loop (timestamps on)");
   dtw = opts && opts->dtw_token_timestamps;
   if (dtw && opts->n_dtw_heads > 0) dtw_heads.assign(opts->dtw_heads, opts->dtw_heads + 2 * opts->n_dtw_heads);
-  for (int i = 0; i < batch; ++i) impl[i]->dtw = dtw;
+  conf = h->confidence;
+  for (int i = 0; i < batch; ++i) {
+    impl[i]->dtw = dtw;
+    impl[i]->have_plog = timestamps;
+    impl[i]->have_forced = dtw && conf;
+  }
   prompt = {sp.sot};
   if (sp.multilingual) {
     prompt.push_back(opts && opts->language_token > 0 ? opts->language_token : sp.lang0);   // <|en|>
@@ -556,7 +573,12 @@ int BatchCall::upload_and_encode() {
   if (rc != CRISPY_OK) return rc;
   rc = crispy_asr_encode_device(h, h->ew.melt, nb, h->ew.enc, h->stream);
   if (rc != CRISPY_OK) return rc;
-  if (detect) {
+  if (detect && conf) {
+    std::vector<float> lp((size_t)nb * sp.n_lang);
+    rc = crispy_asr_detect_language_probs_device(h, h->ew.enc, nb, lang.data(), lp.data());
+    if (rc != CRISPY_OK) return rc;
+    for (int k = 0; k < nb; ++k) impl[live[k]]->lang_probs.assign(lp.begin() + (size_t)k * sp.n_lang, lp.begin() + (size_t)(k + 1) * sp.n_lang);
+  } else if (detect) {
     rc = crispy_asr_detect_language_device(h, h->ew.enc, nb, lang.data());
     if (rc != CRISPY_OK) return rc;
   } else if (sp.multilingual) {
@@ -858,11 +880,19 @@ void BatchCall::add_words(int k, const Accepted& A, const std::vector<int>& text
   for (auto& x : w) {
     x.t0 = (float)(seek[k] * 0.01 + A.align[x.first] * 0.02);
     x.t1 = (float)(seek[k] * 0.01 + A.align[x.first + x.n] * 0.02);
+    // openai's find_alignment: the mean of text_token_probs over the word's tokens as split (f32 probabilities, summed in
+    // double in token order, divided, rounded once)
+    if (conf && (size_t)(x.first + x.n) <= A.logp.size()) {
+      double sum = 0;
+      for (int i = 0; i < x.n; ++i) sum += (double)prob_of(A.logp[x.first + i]);
+      x.prob = (float)(sum / x.n);
+    }
   }
   merge_punctuations(w);
   for (const auto& x : w) {
     r->word_text.push_back(x.text);
     r->words.push_back(crispy_asr_word{x.t0, x.t1, nullptr, text_at[x.first], x.n});
+    if (conf) r->word_prob.push_back(x.prob);
   }
 }
 
@@ -913,11 +943,13 @@ int BatchCall::align_round(const std::vector<int>& act, std::vector<Accepted>& a
     d_enc = d_enc_rep;
   }
   std::vector<std::vector<int>> idx;
-  const int rc = g_align_round(h, d_enc, rows, n_init, n_frames, dtw_heads, idx);
+  std::vector<std::vector<float>> logp;
+  const int rc = g_align_round(h, d_enc, rows, n_init, n_frames, dtw_heads, idx, conf ? &logp : nullptr);
   if (rc != CRISPY_OK) return rc;
   for (size_t c = 0; c < who.size(); ++c) {
     acc[who[c]].align = std::move(idx[c]);
     acc[who[c]].aligned = true;
+    if (conf) acc[who[c]].logp = std::move(logp[c]);
   }
   return CRISPY_OK;
 }
@@ -943,9 +975,11 @@ void BatchCall::finish_window(int k, const Accepted& A) {
         if (dtw) {
           const bool text = A.toks[i] < h->eot && A.aligned && text_at.size() < A.align.size();
           r->tok_t.push_back(text ? (float)(seek[k] * 0.01 + A.align[text_at.size()] * 0.02) : -1.f);
+          if (conf) r->p_forced.push_back(text && text_at.size() < A.logp.size() ? prob_of(A.logp[text_at.size()]) : -1.f);
           if (A.toks[i] < h->eot) text_at.push_back((int)r->tokens.size());
         }
         r->tokens.push_back(A.toks[i]);
+        r->plog.push_back(A.plog[i]);
       }
     if (dtw && A.aligned && !text_at.empty() && A.align.size() == text_at.size() + 1) add_words(k, A, text_at, r);
   }
@@ -1082,6 +1116,13 @@ int crispy_asr_transcribe_recording(crispy_asr* h, const float* pcm16k, size_t n
       const int tok0 = (int)R->tokens.size();
       R->tokens.insert(R->tokens.end(), r.tokens, r.tokens + r.n_tokens);
       if (ci == 0) R->language_token = r.language_token;
+      const crispy_asr_result_impl& ri = *reinterpret_cast<const crispy_asr_result_impl*>(res[i]);      // pub is the first member
+      if (ci == 0) R->lang_probs = ri.lang_probs;
+      R->have_plog = R->have_plog || ri.have_plog;
+      R->have_forced = R->have_forced || ri.have_forced;
+      R->plog.insert(R->plog.end(), ri.plog.begin(), ri.plog.end());
+      R->p_forced.insert(R->p_forced.end(), ri.p_forced.begin(), ri.p_forced.end());
+      R->word_prob.insert(R->word_prob.end(), ri.word_prob.begin(), ri.word_prob.end());
       if (r.token_t_dtw) {
         R->dtw = true;
         for (int k = 0; k < r.n_tokens; ++k) R->tok_t.push_back(r.token_t_dtw[k] < 0.f ? r.token_t_dtw[k] : t_off + r.token_t_dtw[k]);
@@ -1110,6 +1151,38 @@ int crispy_asr_transcribe_recording(crispy_asr* h, const float* pcm16k, size_t n
   *out = &R->pub;
   return CRISPY_OK;
 } CRISPY_CATCH_RET("crispy_asr_transcribe_recording")
+
+// ---- confidence accessors: what the result holds behind its public prefix (no device, no handle) ----
+// An array that is present but empty (a call that kept no token) is a non-NULL pointer with a count of 0: NULL always means
+// "not computed in this call".
+static const float kNoFloats[1] = {0.f};
+static const float* present(const std::vector<float>& v) { return v.empty() ? kNoFloats : v.data(); }
+int crispy_asr_result_token_probs(const crispy_asr_result* r, const float** plog, const float** p_forced, int* n) try {
+  if (!r || !plog || !p_forced || !n) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_result_token_probs: NULL argument");
+  const crispy_asr_result_impl* ri = reinterpret_cast<const crispy_asr_result_impl*>(r);
+  const bool have = ri->have_plog && ri->plog.size() == ri->tokens.size();
+  *plog = have ? present(ri->plog) : nullptr;
+  *n = have ? (int)ri->plog.size() : 0;
+  *p_forced = have && ri->have_forced && ri->p_forced.size() == ri->tokens.size() ? present(ri->p_forced) : nullptr;
+  return CRISPY_OK;
+} CRISPY_CATCH_RET("crispy_asr_result_token_probs")
+
+int crispy_asr_result_word_probs(const crispy_asr_result* r, const float** prob, int* n) try {
+  if (!r || !prob || !n) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_result_word_probs: NULL argument");
+  const crispy_asr_result_impl* ri = reinterpret_cast<const crispy_asr_result_impl*>(r);
+  const bool have = ri->have_forced && ri->word_prob.size() == ri->words.size();
+  *prob = have ? present(ri->word_prob) : nullptr;
+  *n = have ? (int)ri->word_prob.size() : 0;
+  return CRISPY_OK;
+} CRISPY_CATCH_RET("crispy_asr_result_word_probs")
+
+int crispy_asr_result_language_probs(const crispy_asr_result* r, const float** probs, int* n_lang) try {
+  if (!r || !probs || !n_lang) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_result_language_probs: NULL argument");
+  const crispy_asr_result_impl* ri = reinterpret_cast<const crispy_asr_result_impl*>(r);
+  *probs = ri->lang_probs.empty() ? nullptr : ri->lang_probs.data();
+  *n_lang = (int)ri->lang_probs.size();
+  return CRISPY_OK;
+} CRISPY_CATCH_RET("crispy_asr_result_language_probs")
 
 void crispy_asr_free_result(crispy_asr_result* r) try {
   if (!r) return;

@@ -6,6 +6,8 @@
 //   whisper_full.cpp   whisper_full on top of them: seek loop, temperature ladder, segments, results, the recording chunker
 //   whisper_align.hip  word-level timestamps: the alignment pass, its kernels, crispy_asr_{align,dtw}_device (reached from
 //                      whisper_full.cpp through a hook that file installs: not linked, a dtw request is unsupported)
+//   whisper_conf.hip   confidence: the log-probability of a target per logits row, the language soft-max (launchers in
+//                      asr_common.h; the host side is conf_* / detect_language in decode_steps.cpp)
 // Device memory: every buffer of the handle is a DevBuf member (api_util.h) -- the tensors, the resident blocks (a QTensor reads
 // through `d`, which is its own blocks or a dense Tensor's floats), the copies derived from them (crispy_asr::derived, made by
 // derived_copy in whisper_api.cpp and summed by crispy_asr_memory_info), the token masks (upload_mask), the de-quantisation slot,
@@ -81,6 +83,18 @@ struct AlignWs {
   DevBuf<float> q;
   DevBuf<void> ws;                             // row statistics, matrix, DTW outputs, per-clip arguments
   std::vector<int> slot;                       // [n_text_layer]: the layer's slot in q, -1 = none
+  int rows = 0;                                // token rows per clip of the running pass
+  bool on = false;
+};
+
+// Confidence (whisper_conf.hip): while a teacher-forced prefill runs with `on`, prompt_step projects ALL rows of every step
+// onto the vocabulary (into `logits`, rows of their own: h->dw.logits holds one row per clip) and tok_logprob_f32 reads the
+// log-probability of the next token off every row.  `logits` is made the first time confidence is asked for, never otherwise.
+struct ConfWs {
+  DevBuf<float> logits;                        // [SKINNY_MAX_M][logits_ld]
+  DevBuf<int> target;                          // [clips][rows] id the row predicts (-1: none)
+  DevBuf<float> logp;                          // [clips][rows]
+  DevBuf<float> lang;                          // [clips][n_lang] language distribution of a detection step
   int rows = 0;                                // token rows per clip of the running pass
   bool on = false;
 };
@@ -204,6 +218,8 @@ struct crispy_asr {
   std::vector<unsigned char> sup_all, sup_first;   // host copies of the two suppression lists
   std::vector<std::string> vocab;                  // token byte strings of a loaded model file
   crispy::asr::AlignWs align;                      // word alignment (opts.dtw_token_timestamps)
+  crispy::asr::ConfWs conf;                        // token / language probabilities
+  bool confidence = false;                         // crispy_asr_set_confidence: transcribe calls collect them
 };
 
 namespace crispy {
@@ -266,15 +282,36 @@ struct PassStart {
 int begin_pass(crispy_asr* h, const char* who, const std::vector<std::vector<int>>& prompts, int xgroup, int max_new, int fixed_keys,
                bool row_offsets, PassStart* out);
 int prefill(crispy_asr* h, const DecodePass& pass, const float* d_enc, const int* tok_mat, int n_rows, hipStream_t s, int* pos_out);
+// whisper_lang_auto_detect for `batch` clips: the most probable language token per clip and -- probs_out non-null -- the
+// soft-max over the language tokens, host [batch][n_lang]
+int detect_language(crispy_asr* h, const char* who, const float* d_enc, int batch, int* lang_tokens_out, float* probs_out);
+// Teacher-forced token log-probabilities: conf_begin readies the workspace for a prefill over tok_mat [batch][n_rows] (begin_pass's
+// right-aligned rows; row_len[b] = clip b's own rows) and switches the collection on -- every row then predicts the id after
+// it, but the rows before n_sot, the last one and the padding; conf_end switches it off (always call it) and conf_read copies
+// the numbers out: logp[b][i] = log p(row n_sot + 1 + i of clip b), i < row_len[b] - n_sot - 2.  Needs batch <= SKINNY_MAX_M.
+int conf_begin(crispy_asr* h, const int* tok_mat, int batch, int n_rows, const int* row_len, int n_sot, hipStream_t s);
+void conf_end(crispy_asr* h);
+int conf_read(crispy_asr* h, int batch, int n_rows, const int* row_len, int n_sot, hipStream_t s, std::vector<std::vector<float>>* logp);
+// The two launchers of whisper_conf.hip (asr_common.h: tok_logprob_f32, lang_probs_f32), reached through a table that file
+// installs at static initialisation, as whisper_align.hip installs g_align_round: the host translation units call no launcher
+// of it by name, and where the file is not part of the build asking for these numbers is CRISPY_ERR_UNSUPPORTED.
+struct ConfKernels {
+  hipError_t (*tok_logprob)(const float* logits, long ld, int n_cols, const int* target, float* logp, int ld_t, int P, int pos,
+                            int rows, hipStream_t s);
+  hipError_t (*lang_probs)(const float* logits, long ld, int lang0, int n_lang, float* probs, int rows, hipStream_t s);
+};
+extern const ConfKernels* g_conf_kernels;
 
 // ---- whisper_full.cpp ----
 int build_ts_masks(crispy_asr* h);
 // Word alignment of one round of the seek loop: rows[c] = clip c's token rows (sot sequence of n_sot ids, <|notimestamps|>,
 // text tokens, <|endoftext|>), d_enc = the clips' encoder outputs in order, n_frames[c] = mel frames of its window;
-// time_idx[c] receives the warping path's entry column of every row after the sot sequence but the last (10 ms x 2 each).
+// time_idx[c] receives the warping path's entry column of every row after the sot sequence but the last (10 ms x 2 each);
+// logp[c] (nullable) the teacher-forced log-probability of every text token of the clip, from the same pass.
 // Installed by whisper_align.hip at static initialisation; null where that file is not part of the build.
 using AlignRoundFn = int (*)(crispy_asr* h, const float* d_enc, const std::vector<std::vector<int>>& rows, int n_sot,
-                             const std::vector<int>& n_frames, const std::vector<int>& heads, std::vector<std::vector<int>>& time_idx);
+                             const std::vector<int>& n_frames, const std::vector<int>& heads, std::vector<std::vector<int>>& time_idx,
+                             std::vector<std::vector<float>>* logp);
 extern AlignRoundFn g_align_round;
 // what the DTW kernel takes: its trace at 2 bits per cell, the last two anti-diagonals and the row entries share the LDS
 constexpr int kAlignDtwMaxRows = 512, kAlignDtwMaxCols = 4096, kAlignDtwMaxTraceWords = 35000;

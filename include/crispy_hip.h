@@ -835,6 +835,52 @@ int crispy_asr_align_device(crispy_asr *h, const float *d_enc, int batch, const 
 int crispy_asr_dtw_device(crispy_asr *h, const float *d_x, int n_rows, int n_cols, long ld, int *text_idx, int *time_idx,
                           int *n_path);
 
+/* Confidence: how sure the model was of a token, a word, the detected language.  New entry points only -- no public struct
+ * grew, CRISPY_ABI_VERSION is unchanged: a switch on the handle and accessors on the library-owned result.
+ *   crispy_asr_set_confidence(h, on): default 0; holds from the next transcribe call on.  It gates the two things that
+ *     cost device work: the language distribution of the auto-detection, and the teacher-forced token / word
+ *     probabilities of a call with opts.dtw_token_timestamps (the alignment pass then also projects its rows onto the
+ *     vocabulary; a scratch of 512 logits rows, 106 MB, is made the first time and kept).  Off: a call runs the launches it
+ *     ran before this switch existed and gives the same results.
+ *   crispy_asr_result_token_probs: *n = n_tokens entries each, parallel to result->tokens, owned by the result.
+ *     plog      the log-probability of the token under the distribution it was picked from (whisper.cpp's
+ *               whisper_token_data::plog), for the decoder whisper_full accepted for the window -- greedy, temperature ladder
+ *               or beam.  Present in timestamp mode whatever the switch (it is computed anyway): the addends of the window's
+ *               avg_logprob (which also counts a kept <|endoftext|>, never part of tokens).  With opts.no_timestamps the
+ *               plain arg-max takes no log-soft-max: *plog = NULL, *n = 0.
+ *     p_forced  openai-whisper's text_token_probs [UPSTREAM-RECALL: timing.py find_alignment]: the probability of the token
+ *               in the teacher-forced alignment pass (sot sequence, <|notimestamps|>, the window's text), soft-max over the
+ *               ids below <|endoftext|> of the unfiltered logits; -1 for timestamp tokens and for a window that got no
+ *               alignment, as token_t_dtw.  NULL unless the switch was on and the call had dtw_token_timestamps.
+ *   crispy_asr_result_word_probs: *n = n_words entries parallel to result->words: the mean of p_forced over the word's
+ *     tokens as split, BEFORE merge_punctuations -- a word that absorbed a punctuation mark keeps its own probability, as
+ *     it keeps its times (openai's order).  NULL / 0 under the conditions of p_forced.
+ *   crispy_asr_result_language_probs: whisper.cpp's lang_probs [UPSTREAM-RECALL: whisper_lang_auto_detect] -- the soft-max
+ *     of the detection logits over the language tokens only; entry i belongs to token lang0 + i (crispy_asr_vocab_specials).
+ *     *n_lang = 99, 100 for large-v3's vocabulary; NULL / 0 when the switch was off, the language was given in the options,
+ *     or the vocabulary is English-only.  crispy_asr_transcribe_recording: the first chunk's, as language_token.
+ *   The accessors need no device; a NULL result or out-pointer is CRISPY_ERR_INVALID_ARG.  The arrays live as long as the
+ *   result; NULL always means "not computed in this call" (an array that is present but empty -- a call that kept no token --
+ *   is a non-NULL pointer with a count of 0).  crispy_asr_transcribe_batch's
+ *   "a clip's result is that of the call on it alone, bit for bit" covers all of these numbers. */
+int crispy_asr_set_confidence(crispy_asr *h, int on);
+int crispy_asr_result_token_probs(const crispy_asr_result *r, const float **plog, const float **p_forced, int *n);
+int crispy_asr_result_word_probs(const crispy_asr_result *r, const float **prob, int *n);
+int crispy_asr_result_language_probs(const crispy_asr_result *r, const float **probs, int *n_lang);
+/* Stage entry points of the above (no switch needed), for tests and profiling.
+ *   crispy_asr_detect_language_probs_device: crispy_asr_detect_language_device plus the distribution, probs_out host
+ *     [batch][n_lang].  An English-only vocabulary has n_lang = 0: nothing runs, the tokens are 0, the status is OK.
+ *   crispy_asr_token_probs_device: the teacher-forced pass of crispy_asr_align_device -- the same `tokens` rows (sot
+ *     sequence, <|notimestamps|>, text, <|endoftext|>), limits and left padding; at most 512 clips -- with every row projected
+ *     onto the vocabulary as a decode step projects it, in the current precision mode.  logp_out host [batch][ld_tokens]:
+ *     entry i = the LOG-probability of tokens[n_sot + 1 + i] given the rows before it, i = 0 ... n_tokens[b] - n_sot - 3,
+ *     soft-max over the ids below <|endoftext|> (the text tokens must be such ids).  The exponential is taken only where a
+ *     probability is published, so a probability that underflows still has a finite logarithm here.  A clip's numbers do
+ *     not depend on the other clips of the batch. */
+int crispy_asr_detect_language_probs_device(crispy_asr *h, const float *d_enc, int batch, int *lang_tokens_out, float *probs_out);
+int crispy_asr_token_probs_device(crispy_asr *h, const float *d_enc, int batch, const int *tokens, const int *n_tokens,
+                                  int ld_tokens, int n_sot, float *logp_out);
+
 /* ------------------------------------------------------------------------------------------
  * 48 kHz -> 16 kHz resampler between the denoiser and the ASR front end:
  * rubato FftFixedIn::<f32>::new(48000, 16000, 1024, 1, 1) as driven by
