@@ -47,6 +47,10 @@ pub const CRISPY_RN_LAYOUT_BTF: crispy_rn_layout = 1;
 pub const CRISPY_PCM_F32: c_int = 0;
 pub const CRISPY_PCM_I16: c_int = 1;
 pub const CRISPY_PCM_U16: c_int = 2;
+/// NsState::RnnNoise / NsState::Legacy(ModelKind::Dummy) / NsState::Legacy(ModelKind::Noisy): crispy_rn_model_configure
+pub const CRISPY_NS_RNNOISE: c_int = 0;
+pub const CRISPY_NS_DUMMY: c_int = 1;
+pub const CRISPY_NS_NOISY: c_int = 2;
 
 #[repr(C)]
 pub struct crispy_rn {
@@ -237,6 +241,9 @@ extern "C" {
     pub fn crispy_rn_capture(h: *mut crispy_rn, input: *const c_void, in_stride: c_long, n_frames: c_long, channels: c_int, format: c_int, out: *mut c_float, out_stride: c_long, rms: *mut c_float, n_out: *mut c_long) -> c_int;
     pub fn crispy_rn_record_app_push_at_device(h: *mut crispy_rn, d_in: *const c_float, in_stride: c_long, n_frames: c_long, channels: c_int, from_rate: c_int, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_rn_record_app_push_at(h: *mut crispy_rn, input: *const c_float, in_stride: c_long, n_frames: c_long, channels: c_int, from_rate: c_int) -> c_int;
+    pub fn crispy_rn_model_configure(h: *mut crispy_rn, model: c_int) -> c_int;
+    pub fn crispy_rn_model(h: *const crispy_rn, model: *mut c_int) -> c_int;
+    pub fn crispy_ns_noise_state(state: c_long, n: c_long, noise: *mut c_float) -> c_long;
     pub fn crispy_rn_synchronize(h: *mut crispy_rn) -> c_int;
     pub fn crispy_rn_set_timing(h: *mut crispy_rn, enable: c_int) -> c_int;
     pub fn crispy_rn_last_kernel_ms(h: *mut crispy_rn, frame_kernel_ms: *mut c_float, total_ms: *mut c_float) -> c_int;
@@ -547,6 +554,23 @@ impl BatchDenoiser {
     /// `capture_f32` resample the raw mono to 48 kHz instead of denoising it.  0 returns to the RNNoise arm.
     pub fn configure_bypass(&mut self, raw_input_rate: f32) -> Result<(), CrispyError> {
         check(unsafe { crispy_rn_bypass_configure(self.h, raw_input_rate) })
+    }
+    /// `set_monitoring_model` (audio.rs:942-967): a fresh processor of the named model at the configured rates and the current
+    /// volume, also when the model is unchanged -- "rnnnoise", "noisy", anything else the dummy (`ModelKind::from_name`).
+    /// From here on push, pull and capture are that processor's: for the Legacy models `SharedAudio` (audio.rs:136-200).
+    pub fn set_model(&mut self, name: &str) -> Result<(), CrispyError> {
+        let model = match name {
+            "rnnnoise" => CRISPY_NS_RNNOISE,
+            "noisy" => CRISPY_NS_NOISY,
+            _ => CRISPY_NS_DUMMY,
+        };
+        check(unsafe { crispy_rn_model_configure(self.h, model) })
+    }
+    /// The handle's model, a CRISPY_NS_* code.
+    pub fn model(&self) -> Result<c_int, CrispyError> {
+        let mut model: c_int = 0;
+        check(unsafe { crispy_rn_model(self.h, &mut model) })?;
+        Ok(model)
     }
     /// Samples per stream the next capture of `n_frames` frames returns.
     pub fn capture_out_len(&self, n_frames: usize) -> Result<usize, CrispyError> {

@@ -38,9 +38,11 @@ RN_SYMBOLS = (
     "crispy_rn_record_drain_device", "crispy_rn_record_drain", "crispy_record_worker_plan",
     "crispy_rn_bypass_configure", "crispy_rn_capture_out_len", "crispy_rn_capture_device", "crispy_rn_capture",
     "crispy_rn_record_app_push_at_device", "crispy_rn_record_app_push_at",
+    "crispy_rn_model_configure", "crispy_rn_model", "crispy_ns_noise_state",
 )
 REC_FRAME = 1152                          # the recording worker's frame_size (commands/recording.rs:196)
 PCM_F32, PCM_I16, PCM_U16 = 0, 1, 2      # CRISPY_PCM_*
+NS_RNNOISE, NS_DUMMY, NS_NOISY = 0, 1, 2   # CRISPY_NS_*
 
 
 MEL_SYMBOLS = ("crispy_mel_create", "crispy_mel_destroy", "crispy_mel_compute",
@@ -211,6 +213,10 @@ def load_library(path: str) -> C.CDLL:
                                     C.c_void_p, lp]
     L.crispy_rn_record_app_push_at_device.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_void_p]
     L.crispy_rn_record_app_push_at.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int]
+    L.crispy_rn_model_configure.argtypes = [C.c_void_p, C.c_int]
+    L.crispy_rn_model.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.crispy_ns_noise_state.argtypes = [C.c_long, C.c_long, C.c_void_p]
+    L.crispy_ns_noise_state.restype = C.c_long
     L.crispy_rn_debug_capture.argtypes = [C.c_void_p, C.c_int]
     L.crispy_rn_debug_read.argtypes = [C.c_void_p, C.c_int, f32p, C.c_size_t]
     L.crispy_mel_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]

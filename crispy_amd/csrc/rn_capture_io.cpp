@@ -51,7 +51,7 @@ int plan_capture(const crispy_rn* h, long n_frames, std::vector<int>* idx, std::
     PushPlan pp;
     const int rc = plan_push(adapter_of(h), n_frames, nullptr, nullptr, &pp, who);
     if (rc != CRISPY_OK) return rc;
-    p->n_out = pp.n_out;
+    p->n_out = legacy_active(h) ? n_frames : pp.n_out;      // NsState::Legacy: one sample out per sample in
     return CRISPY_OK;
   }
   const RnCaptureState* c = h->cap.get();
@@ -127,8 +127,12 @@ int capture_device_impl(crispy_rn* h, const void* d_in, long in_stride, long n_f
     rc = level_device_impl(h, d_mono, mono_stride, n_frames, d_rms, s);
     if (rc != CRISPY_OK) return rc;
   }
-  if (!p.bypass)      // Some(shared): push_sample on every mono sample, its output to the playback and recording rings
+  if (!p.bypass) {    // Some(shared): push_sample on every mono sample, its output to the playback and recording rings
+    // (every argument the Legacy push checks -- the sample count, both strides against it, d_out against the mono rows -- was
+    // checked above with p.n_out = n_frames, before anything was launched)
+    if (legacy_active(h)) return h->lg->push(h, d_mono, mono_stride, n_frames, d_out, out_stride, n_out, s, who);
     return push_device_impl(h, d_mono, mono_stride, n_frames, d_out, out_stride, nullptr, 0, nullptr, n_out, s, who);
+  }
 
   // shared == None: the callback's resampler on the raw mono (audio.rs:697-714)
   RnCaptureResample cr{};
@@ -205,6 +209,21 @@ int app_push_at_device_impl(crispy_rn* h, const float* d_in, long in_stride, lon
 
 }  // namespace
 
+int crispy::ensure_capture_last(crispy_rn* h, const char* who) {
+  RnCaptureState* c = capture_of(h);
+  if (c->last.p) return CRISPY_OK;
+  const size_t bytes = 2 * (size_t)h->B * sizeof(float);
+  DevBuf<float> last;
+  if (last.alloc(bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(CRISPY_ERR_OOM, "%s: resampler state allocation of %zu bytes failed", who, bytes);
+  }
+  HIP_TRY(hipMemset(last.p, 0, bytes));
+  HIP_TRY(hipDeviceSynchronize());
+  c->last = std::move(last);
+  return CRISPY_OK;
+}
+
 extern "C" {
 
 int crispy_rn_bypass_configure(crispy_rn* h, float raw_input_rate) try {
@@ -214,17 +233,9 @@ int crispy_rn_bypass_configure(crispy_rn* h, float raw_input_rate) try {
     return fail(CRISPY_ERR_INVALID_ARG, "%s: raw_input_rate must be a positive number of Hz, or 0 to leave the arm", who);
   HIP_TRY(hipSetDevice(h->device));
   RnCaptureState* c = capture_of(h);
-  if (raw_input_rate > 0.f && !c->last.p) {
-    // the last-sample halves are state: they exist before the arm is entered
-    const size_t bytes = 2 * (size_t)h->B * sizeof(float);
-    DevBuf<float> last;
-    if (last.alloc(bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(CRISPY_ERR_OOM, "%s: resampler state allocation of %zu bytes failed", who, bytes);
-    }
-    HIP_TRY(hipMemset(last.p, 0, bytes));
-    HIP_TRY(hipDeviceSynchronize());
-    c->last = std::move(last);
+  if (raw_input_rate > 0.f) {
+    const int rc = ensure_capture_last(h, who);
+    if (rc != CRISPY_OK) return rc;
   }
   c->bypass_rate = raw_input_rate;
   c->resample = raw_input_rate > 0.f && std::fabs(raw_input_rate - 48000.f) >= 1.f;

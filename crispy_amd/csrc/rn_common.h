@@ -282,6 +282,73 @@ hipError_t rn_launch_capture(const RnCapture& a, int format, hipStream_t s);    
 hipError_t rn_launch_capture_resample(const RnCaptureResample& a, hipStream_t s);
 hipError_t rn_launch_rec_app_at(const RnRecAppAt& a, hipStream_t s);
 
+// ---- the Legacy arm of NsState: SharedAudio (src-tauri/src/audio.rs:136-200) on crispy_rn_push* / crispy_rn_pull* (rn_legacy.hip) ----
+// SharedAudio's noise source is the LCG  rng = rng * 1664525 + 1013904223  (wrapping u32), one step per noisy sample.  2^j
+// steps are the affine map x -> a[j] * x + c[j]: n steps are one multiply-add per set bit of n, on the host (the handle's copy
+// of the state, crispy_ns_noise_state) and in the kernels (a lane's own starting state) alike.  Nothing is carried serially.
+constexpr uint32_t NS_LCG_A = 1664525u, NS_LCG_C = 1013904223u, NS_LCG_SEED = 0x1234abcdu;
+struct NsLcgPowers {
+  uint32_t a[32], c[32];
+};
+constexpr NsLcgPowers ns_lcg_powers() {
+  NsLcgPowers p{};
+  uint32_t a = NS_LCG_A, c = NS_LCG_C;
+  for (int j = 0; j < 32; ++j) {
+    p.a[j] = a;
+    p.c[j] = c;
+    c = (a + 1u) * c;       // f(f(x)) = a (a x + c) + c
+    a = a * a;
+  }
+  return p;
+}
+__host__ __device__ inline uint32_t ns_lcg_step(uint32_t s) { return s * NS_LCG_A + NS_LCG_C; }
+// Bits LO ... HI - 1 of n: the state n & (2^HI - 2^LO) steps on.  Unrolled, the powers are immediates.
+template <int LO, int HI>
+__host__ __device__ inline uint32_t ns_lcg_jump_bits(uint32_t s, uint32_t n) {
+  constexpr NsLcgPowers P = ns_lcg_powers();
+#pragma unroll
+  for (int j = LO; j < HI; ++j)
+    if ((n >> j) & 1u) s = s * P.a[j] + P.c[j];
+  return s;
+}
+__host__ __device__ inline uint32_t ns_lcg_jump(uint32_t s, uint32_t n) { return ns_lcg_jump_bits<0, 32>(s, n); }
+// `(rng as f32 / u32::MAX as f32) * 2.0 - 1.0`: the conversion rounds to nearest even, u32::MAX as f32 is 2^32, so the division
+// is an exact scaling (written as the multiply by 2^-32), as is the doubling; the subtraction rounds.  +1.0 from 0xffffff80 on.
+__host__ __device__ inline float ns_noise(uint32_t s) {
+#pragma clang fp contract(off)
+  const float u = (float)s;
+  const float q = u * 0x1p-32f;
+  const float d = q * 2.0f;
+  return d - 1.0f;
+}
+
+// One Legacy push of n samples per stream: out[b][k] = in[b][k] * volume, Noisy: + noise(step k + 1 from rng) * 0.05 -- every
+// operation rounded on its own --, and the raw in[b][k] of the samples skip ... n - 1 into the playback ring from `tail` on.
+struct RnLegacyPush {
+  const float* in;     // [B][in_stride]
+  long in_stride;
+  int n;               // samples per stream, 1...2^24
+  float* out;          // [B][out_stride]
+  long out_stride;
+  float volume;
+  uint32_t rng;        // rng_state in front of the push (Noisy)
+  float* ring;         // [B][cap] or null: no playback configured
+  int cap;
+  int tail;            // where sample `skip` goes, < cap
+  int skip;            // samples at the front that the ring's eviction drops; n - skip <= cap
+  bool ring_vec;       // set by the launcher: every ring row is 16-byte aligned
+  int B;
+};
+// One Legacy pull: RnPull's gather and interpolation, Noisy: + noise(step j + 1 from rng) * 0.05 for live frame j -- the live
+// frames of a pull are a prefix of it, so j is the frame's index --, then x volume, the conversion and the fan-out.
+struct RnLegacyPull {
+  RnPull p;
+  float volume;
+  uint32_t rng;        // rng_state in front of the pull (Noisy)
+};
+hipError_t rn_launch_legacy_push(const RnLegacyPush& a, bool noisy, hipStream_t s);
+hipError_t rn_launch_legacy_pull(const RnLegacyPull& a, int format, bool noisy, hipStream_t s);
+
 // A launch covers at most 2^23 workgroups (the runtime refuses 2^32 work-items per grid dimension and more): a handle of
 // several hundred thousand streams is covered in turns of streams, each turn with its own row pointers.
 // launch(b0, nb): the kernel for streams b0 ... b0 + nb - 1, `tiles` (<= RN_MAX_BLOCKS) workgroups each.

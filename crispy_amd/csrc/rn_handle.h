@@ -1,7 +1,7 @@
 // rn_handle.h -- the RNNoise handle behind `crispy_rn` (include/crispy_hip.h) and the state of its three halves, shared by
 // the translation units that implement its entry points: crispy_api.cpp (create / process / reset ...), rn_io.cpp
-// (crispy_rn_push*, crispy_rn_pull*, crispy_rn_record_*, crispy_rn_level*) and rn_capture_io.cpp (crispy_rn_capture*,
-// crispy_rn_bypass_configure, crispy_rn_record_app_push_at*).  Everything here owns what it holds: device
+// (crispy_rn_push*, crispy_rn_pull*, crispy_rn_record_*, crispy_rn_level*), rn_capture_io.cpp (crispy_rn_capture*,
+// crispy_rn_bypass_configure, crispy_rn_record_app_push_at*) and rn_legacy_io.cpp (crispy_rn_model*, the Legacy arm).  Everything here owns what it holds: device
 // buffers are DevBuf, events EventList (api_util.h), streams Stream, the halves unique_ptr members -- deleting the handle
 // releases all of it, streams last.  The types are plain state; the logic that drives them is in the .cpp files.
 #pragma once
@@ -125,6 +125,28 @@ struct RnCaptureState {
   DevBuf<float> mono;       // scratch [B][mono_stride]: the mono of a capture whose caller does not ask for it
 };
 
+// NsState's other variant, Legacy(SharedAudio) (audio.rs:47-71, 136-200, 317-358), and which variant the handle is: created by
+// the first crispy_rn_model_configure; a handle without one is the RNNoise arm.  SharedAudio's rates and volume are the
+// adapter's (RnAdapter::rate, ::volume), its buffer, max_len and resample_pos the playback ring's (RnPlayback, sized from the
+// raw rate); its own are the model kind and the LCG state, the same for every stream as ring heads are.
+// crispy_api.cpp and rn_io.cpp read and write the plain fields and reach the arm's code only through the pointers here,
+// which crispy_rn_model_configure sets: they link without rn_legacy_io.cpp and rn_legacy.hip (tests/asan/harness.cpp).
+struct RnLegacy {
+  int model = CRISPY_NS_RNNOISE;
+  uint32_t rng = NS_LCG_SEED;     // rng_state: one step per sample a Noisy push returned or a Noisy pull found live
+  // input_rate of the capture callback's LinearResampler(_, 48000) (audio.rs:701-709), whose positions and last samples are
+  // RnCaptureState's: what the last push that returned samples produced.  A Legacy push that produces 1 Hz or more off
+  // it is the callback's set_rates: the resampler starts afresh.
+  float rec_rate = 48000.f;
+  DevBuf<float> rec;              // scratch [B][stride]: what that resampler emitted of one push, on its way to the mic ring
+  // SharedAudio::push_sample over a block + the rest of push_mono_to_buffers; arguments checked as push_device_impl's
+  int (*push)(crispy_rn* h, const float* d_in, long in_stride, long n_in, float* d_out, long out_stride, long* n_out, hipStream_t s,
+              const char* who) = nullptr;
+  // SharedAudio::next_sample over a block; the contract of rn_io.cpp's pull_device_impl
+  int (*pull)(crispy_rn* h, long n_frames, int channels, int format, void* d_out, long out_stride, long* n_live, hipStream_t s,
+              const char* who) = nullptr;
+};
+
 }  // namespace crispy
 
 struct crispy_rn {
@@ -189,6 +211,7 @@ struct crispy_rn {
   std::unique_ptr<crispy::RnPlayback> pb;    // the playback ring (crispy_rn_pull*): created by crispy_rn_playback_configure
   std::unique_ptr<crispy::RnRecord> rec;     // the recording rings (crispy_rn_record_*): created on first use
   std::unique_ptr<crispy::RnCaptureState> cap;   // the capture callback's state (crispy_rn_capture*): created on first use
+  std::unique_ptr<crispy::RnLegacy> lg;      // the Legacy arm and the model switch (crispy_rn_model*): created on first use
 
   // Every stream the handle created is drained before anything it holds goes.
   ~crispy_rn() {
@@ -225,6 +248,8 @@ constexpr long kPushMaxNew = 1L << 28;      // 48 kHz samples per stream and pus
 RnAdapter* adapter_of(crispy_rn* h);
 const RnAdapter* adapter_of(const crispy_rn* h);
 inline bool recording(const crispy_rn* h) { return h->rec && h->rec->cap > 0; }
+// NsState::Legacy: pushes and pulls go through RnLegacy's pointers
+inline bool legacy_active(const crispy_rn* h) { return h->lg && h->lg->model != CRISPY_NS_RNNOISE; }
 // What a push of n_in samples will do, worked out on the host without touching the handle.
 struct PushPlan {
   LinResState rs;      // resampler state behind the push
@@ -243,4 +268,15 @@ int check_app_push(const crispy_rn* h, const float* in, long in_stride, long n_f
 int app_push_device_impl(crispy_rn* h, const float* d_in, long in_stride, long n_frames, int channels, hipStream_t s);
 // crispy_rn_level_device behind its checks
 int level_device_impl(crispy_rn* h, const float* d_in, long in_stride, long n_in, float* d_rms, hipStream_t s);
+// next_sample's recurrence (audio.rs:297-314, the same in SharedAudio: 167-199) over n_frames on copies of the playback
+// state: per frame the samples popped since the start and resample_pos as f32 into p->off / p->frac (off < 0: a dry frame).
+struct PullPlan {
+  long len = 0, pops = 0, live = 0;
+  double pos = 0.;
+};
+PullPlan plan_pull(RnPlayback* p, long n_frames);
+
+// rn_capture_io.cpp, what rn_legacy_io.cpp uses of it: the capture state with the callback resampler's last-sample halves
+// allocated (state: they exist before an arm that needs them is entered); CRISPY_ERR_OOM leaves the handle as it was.
+int ensure_capture_last(crispy_rn* h, const char* who);
 }  // namespace crispy

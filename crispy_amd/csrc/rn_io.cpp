@@ -279,6 +279,7 @@ int push_device_impl(crispy_rn* h, const float* d_in, long in_stride, long n_in,
     HIP_TRY(rn_launch_adapt_out(ao, s));
     if (timed) HIP_TRY(hipEventRecord(a->ev[3], s));
     a->timed = timed;
+    if (h->lg) h->lg->rec_rate = a->resample ? 48000.f : a->rate;      // the callback resampler's set_rates: it passes through (audio.rs:706-709)
     if (RnPlayback* pb = h->pb.get()) {      // playback configured: what push_sample appends to output_buf (audio.rs:280-285)
       rc = ring_append(pb->ring.p, pb->buf, pb->cap, d_out, out_stride, p.n_out, h->B, s);
       if (rc != CRISPY_OK) return rc;
@@ -294,9 +295,35 @@ int push_device_impl(crispy_rn* h, const float* d_in, long in_stride, long n_in,
 
 }  // namespace crispy
 
-namespace {
-
 // ---- pull -------------------------------------------------------------------------------------------------------------
+
+// next_sample (audio.rs:297-314), n_frames times, on copies of the state: the reference's own recurrence, never a closed form
+PullPlan crispy::plan_pull(RnPlayback* p, long n_frames) {
+  const double step = (double)p->in_rate / (double)p->out_rate;
+  PullPlan pl;
+  pl.len = p->buf.len;
+  pl.pos = p->pos;
+  p->off.resize((size_t)n_frames);
+  p->frac.resize((size_t)n_frames);
+  for (long f = 0; f < n_frames; ++f) {
+    p->off[f] = -1;
+    p->frac[f] = 0.f;
+    if (pl.len < 2) continue;
+    while (pl.pos >= 1.0 && pl.len >= 2) {
+      ++pl.pops;
+      --pl.len;
+      pl.pos -= 1.0;
+    }
+    if (pl.len < 2) continue;         // ran dry while popping: 0.0, the pops and the decrements stay
+    p->off[f] = (int)pl.pops;
+    p->frac[f] = (float)pl.pos;
+    pl.pos += step;
+    ++pl.live;
+  }
+  return pl;
+}
+
+namespace {
 
 // A fresh output_buf of one second at in_rate and resample_pos = 0.  The ring is state: it is replaced only when its size
 // changes, the new one allocated before the old one goes, so a failure leaves the handle as it was.
@@ -338,27 +365,9 @@ int check_pull(const crispy_rn* h, long n_frames, int channels, int format, cons
 int pull_device_impl(crispy_rn* h, long n_frames, int channels, int format, void* d_out, long out_stride, long* n_live, hipStream_t s,
                      const char* who) {
   RnPlayback* p = h->pb.get();
-  // next_sample (audio.rs:297-314), n_frames times, on copies of the state: the reference's own recurrence, never a closed form
-  const double step = (double)p->in_rate / (double)p->out_rate;
-  long len = p->buf.len, pops = 0, live = 0;
-  double pos = p->pos;
-  p->off.resize((size_t)n_frames);
-  p->frac.resize((size_t)n_frames);
-  for (long f = 0; f < n_frames; ++f) {
-    p->off[f] = -1;
-    p->frac[f] = 0.f;
-    if (len < 2) continue;
-    while (pos >= 1.0 && len >= 2) {
-      ++pops;
-      --len;
-      pos -= 1.0;
-    }
-    if (len < 2) continue;         // ran dry while popping: 0.0, the pops and the decrements stay
-    p->off[f] = (int)pops;
-    p->frac[f] = (float)pos;
-    pos += step;
-    ++live;
-  }
+  const PullPlan pl = plan_pull(p, n_frames);
+  const long len = pl.len, pops = pl.pops, live = pl.live;
+  const double pos = pl.pos;
   // every allocation first: a failure from here on returns with the handle's state as it was
   const size_t words = (size_t)2 * n_frames;
   int rc = p->frames.reserve(words, who);
@@ -540,12 +549,19 @@ int crispy_rn_adapter_configure(crispy_rn* h, float input_rate, float volume) tr
   if (volume != volume) return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_adapter_configure: volume is NaN");
   HIP_TRY(hipSetDevice(h->device));
   const bool resample = std::fabs(input_rate - 48000.f) >= 1.f;
+  // NsState::Legacy: a fresh SharedAudio of the same kind (audio.rs:136-149) -- the ring holds raw samples at the raw rate
+  const bool legacy = legacy_active(h);
   // the new processor's output_buf and resample_pos, on a handle with playback configured; first, as it may allocate
-  int rc = h->pb ? playback_fresh_ring(h, h->pb.get(), resample ? 48000.f : input_rate, "crispy_rn_adapter_configure") : CRISPY_OK;
+  int rc = h->pb ? playback_fresh_ring(h, h->pb.get(), resample && !legacy ? 48000.f : input_rate, "crispy_rn_adapter_configure") : CRISPY_OK;
   if (rc != CRISPY_OK) return rc;
-  rc = rn_zero_state(h, -1);
-  if (rc != CRISPY_OK) return rc;
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (legacy) {
+    (void)adapter_of(h);       // (may throw: before anything changes)
+    h->lg->rng = NS_LCG_SEED;
+  } else {
+    rc = rn_zero_state(h, -1);
+    if (rc != CRISPY_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
   RnAdapter* a = adapter_of(h);
   a->rate = input_rate;
   a->resample = resample;
@@ -567,7 +583,7 @@ int crispy_rn_adapter_set_volume(crispy_rn* h, float volume) try {
 int crispy_rn_adapter_produced_rate_hz(const crispy_rn* h, float* rate_hz) try {
   if (!h || !rate_hz) return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_adapter_produced_rate_hz: NULL argument");
   const RnAdapter* a = adapter_of(h);
-  *rate_hz = a->resample ? 48000.f : a->rate;
+  *rate_hz = a->resample && !legacy_active(h) ? 48000.f : a->rate;      // NsState::Legacy: s.input_rate, the raw rate
   return CRISPY_OK;
 } CRISPY_CATCH_RET("crispy_rn_adapter_produced_rate_hz")
 
@@ -575,6 +591,7 @@ long crispy_rn_push_out_len(const crispy_rn* h, long n_in) try {
   if (!h) return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_push_out_len: NULL handle");
   PushPlan p;
   const int rc = plan_push(adapter_of(h), n_in, nullptr, nullptr, &p, "crispy_rn_push_out_len");
+  if (rc == CRISPY_OK && legacy_active(h)) return n_in;      // SharedAudio::push_sample: Some(vec![processed])
   return rc != CRISPY_OK ? rc : p.n_out;
 } CRISPY_CATCH_RET("crispy_rn_push_out_len")
 
@@ -587,8 +604,12 @@ int crispy_rn_push_device(crispy_rn* h, const float* d_in, long in_stride, long 
   if (n_in == 0) return CRISPY_OK;
   if (!d_in || !d_out) return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_push_device: NULL audio pointer");
   HIP_TRY(hipSetDevice(h->device));
-  return push_device_impl(h, d_in, in_stride, n_in, d_out, out_stride, d_frames48, frames_stride, d_vad, n_out,
-                          hip_stream ? (hipStream_t)hip_stream : h->stream, "crispy_rn_push_device");
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  if (legacy_active(h)) {
+    if (d_frames48 || d_vad) return fail(CRISPY_ERR_INVALID_ARG, "crispy_rn_push_device: a Legacy model has no frames and no VAD (d_frames48 / d_vad must be NULL)");
+    return h->lg->push(h, d_in, in_stride, n_in, d_out, out_stride, n_out, s, "crispy_rn_push_device");
+  }
+  return push_device_impl(h, d_in, in_stride, n_in, d_out, out_stride, d_frames48, frames_stride, d_vad, n_out, s, "crispy_rn_push_device");
 } CRISPY_CATCH_RET("crispy_rn_push_device")
 
 int crispy_rn_push(crispy_rn* h, const float* in, long in_stride, long n_in, float* out, long out_stride, float* vad,
@@ -604,6 +625,12 @@ int crispy_rn_push(crispy_rn* h, const float* in, long in_stride, long n_in, flo
   PushPlan p;
   int rc = plan_push(adapter_of(h), n_in, nullptr, nullptr, &p, who);
   if (rc != CRISPY_OK) return rc;
+  const bool legacy = legacy_active(h);
+  if (legacy) {
+    if (vad) return fail(CRISPY_ERR_INVALID_ARG, "%s: a Legacy model has no VAD (vad must be NULL)", who);
+    p.n_out = n_in;
+    p.frames = 0;
+  }
   if (out_stride < p.n_out) return fail(CRISPY_ERR_INVALID_ARG, "%s: out_stride %ld shorter than the %ld samples of this push", who, out_stride, p.n_out);
   HIP_TRY(hipSetDevice(h->device));
   const size_t B = (size_t)h->B;
@@ -617,7 +644,8 @@ int crispy_rn_push(crispy_rn* h, const float* in, long in_stride, long n_in, flo
   HIP_TRY(hipMemcpy2DAsync(d_hin, (size_t)n_in * sizeof(float), in, (size_t)in_stride * sizeof(float), (size_t)n_in * sizeof(float),
                            B, hipMemcpyHostToDevice, s));
   long got = 0;
-  rc = push_device_impl(h, d_hin, n_in, n_in, d_hout, p.n_out, nullptr, 0, d_hvad, &got, s, who);
+  rc = legacy ? h->lg->push(h, d_hin, n_in, n_in, d_hout, p.n_out, &got, s, who)
+              : push_device_impl(h, d_hin, n_in, n_in, d_hout, p.n_out, nullptr, 0, d_hvad, &got, s, who);
   if (rc != CRISPY_OK) return rc;
   if (got > 0)
     HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride * sizeof(float), d_hout, (size_t)got * sizeof(float), (size_t)got * sizeof(float),
@@ -693,7 +721,8 @@ int crispy_rn_pull_device(crispy_rn* h, long n_frames, int channels, int format,
   if (n_live) *n_live = 0;
   if (n_frames == 0) return CRISPY_OK;
   HIP_TRY(hipSetDevice(h->device));
-  return pull_device_impl(h, n_frames, channels, format, d_out, out_stride, n_live, hip_stream ? (hipStream_t)hip_stream : h->stream, who);
+  const auto pull = legacy_active(h) ? h->lg->pull : pull_device_impl;
+  return pull(h, n_frames, channels, format, d_out, out_stride, n_live, hip_stream ? (hipStream_t)hip_stream : h->stream, who);
 } CRISPY_CATCH_RET("crispy_rn_pull_device")
 
 int crispy_rn_pull(crispy_rn* h, long n_frames, int channels, int format, void* out, long out_stride, long* n_live) try {
@@ -709,7 +738,8 @@ int crispy_rn_pull(crispy_rn* h, long n_frames, int channels, int format, void* 
   rc = h->stage_reserve(0, (size_t)h->B * pitch, 0, who);
   if (rc != CRISPY_OK) return rc;
   hipStream_t s = h->stream;
-  rc = pull_device_impl(h, n_frames, channels, format, h->stage_out.p, (long)(pitch / pcm_bytes(format)), n_live, s, who);
+  const auto pull = legacy_active(h) ? h->lg->pull : pull_device_impl;
+  rc = pull(h, n_frames, channels, format, h->stage_out.p, (long)(pitch / pcm_bytes(format)), n_live, s, who);
   if (rc != CRISPY_OK) return rc;
   HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride * pcm_bytes(format), h->stage_out.p, pitch, row, (size_t)h->B, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));

@@ -298,6 +298,22 @@ class DenoiseState:
                                                  C.byref(got), stream or None), self._L)
         return int(got.value)
 
+    # -- the model switch and NsState's Legacy arm (crispy_rn_model_configure / crispy_rn_model) -----
+    MODELS = {"rnnnoise": N.NS_RNNOISE, "dummy": N.NS_DUMMY, "noisy": N.NS_NOISY}
+
+    def model_configure(self, model):
+        """`set_monitoring_model` (audio.rs:942-967): a fresh processor of that model -- "rnnnoise", "dummy", "noisy" or a
+        CRISPY_NS_* code -- at the configured capture rate, the current volume and the configured output rate.  From here on
+        push, pull and capture are that processor's: for a Legacy model `SharedAudio` (audio.rs:136-200)."""
+        code = self.MODELS[model] if isinstance(model, str) else int(model)
+        N.check(self._L.crispy_rn_model_configure(self._h, code), self._L)
+
+    def model(self) -> int:
+        """The handle's model, a CRISPY_NS_* code (`_native.NS_*`)."""
+        m = C.c_int()
+        N.check(self._L.crispy_rn_model(self._h, C.byref(m)), self._L)
+        return int(m.value)
+
     def level(self, x: np.ndarray) -> np.ndarray:
         """`crispy_rn_level`: the callback's level meter over x [B, n], `(sum(mono * mono) / n).sqrt()` per stream with the
         reference's f32 rounding; n == 0 gives zeros (the callback emits nothing then)."""
@@ -509,6 +525,109 @@ class RnnNoiseProcessor:
         return (s0 + (s1 - s0) * frac).astype(np.float32)
 
 
+class SharedAudio:
+    """`SharedAudio` (audio.rs:63-72, 136-200), the processor of NsState's Legacy arm, sample by sample for B lock-stepped
+    streams: every f32 operation of the reference is a numpy f32 operation of its own, in the reference's order.  `model` is
+    "dummy" or "noisy" (`ModelKind::from_name`: anything but "noisy" is Dummy).  One LCG serves `push_sample` and
+    `next_sample` and is the same for every stream.  The device form is `NsState` below."""
+
+    def __init__(self, input_rate: float, output_rate: float, model: str, volume: float, n_streams: int = 1):
+        self.input_rate = np.float32(input_rate)
+        self.output_rate = np.float32(output_rate)
+        self.max_len = int(self.input_rate)          # `input_rate as usize`: the raw capture rate
+        self.buffer: deque = deque()
+        self.resample_pos = 0.0
+        self.noisy = model == "noisy"
+        self.volume = np.float32(volume)
+        self.rng_state = 0x1234ABCD
+        self.n_streams = n_streams
+
+    def _noise(self) -> np.float32:
+        self.rng_state = (self.rng_state * 1664525 + 1013904223) & 0xFFFFFFFF
+        r = np.float32(np.uint32(self.rng_state))            # `as f32`: to nearest even
+        return np.float32(np.float32(r / np.float32(4294967296.0)) * np.float32(2.0) - np.float32(1.0))
+
+    def push_sample(self, samples) -> np.ndarray:
+        """One sample per stream -> `Some(vec![processed])` as an array [1, B]."""
+        samples = np.atleast_1d(np.asarray(samples, dtype=np.float32))
+        if samples.size != self.n_streams:
+            raise ValueError("push_sample: one sample per stream")
+        if len(self.buffer) >= self.max_len:
+            self.buffer.popleft()
+        self.buffer.append(samples.copy())
+        with np.errstate(invalid="ignore", over="ignore"):
+            processed = samples * self.volume
+            if self.noisy:
+                processed = processed + np.float32(self._noise() * np.float32(0.05))
+        return processed.astype(np.float32)[None, :]
+
+    def next_sample(self) -> np.ndarray:
+        zero = np.zeros(self.n_streams, dtype=np.float32)
+        if len(self.buffer) < 2:
+            return zero
+        step = float(self.input_rate) / float(self.output_rate)
+        while self.resample_pos >= 1.0:
+            self.buffer.popleft()
+            self.resample_pos -= 1.0
+            if len(self.buffer) < 2:
+                return zero
+        s0, s1 = self.buffer[0], self.buffer[1]
+        frac = np.float32(self.resample_pos)
+        with np.errstate(invalid="ignore", over="ignore"):
+            sample = s0 + (s1 - s0) * frac
+            if self.noisy:
+                sample = sample + np.float32(self._noise() * np.float32(0.05))
+            self.resample_pos += step
+            return (sample * self.volume).astype(np.float32)
+
+
+class NsState:
+    """`NsState` (audio.rs:317-358) over one handle for B lock-stepped streams: the processor behind the capture and the
+    output callbacks, whichever model it is, with `set_monitoring_model` (audio.rs:942-967) as `set_model`.  Everything runs on
+    the device; `push_sample` / `next_sample` are blocks of one, so `CaptureBuffers.push_mono` takes it as it takes a
+    per-sample processor."""
+
+    def __init__(self, weights: np.ndarray, input_rate: float, output_rate: float, volume: float, n_streams: int = 1,
+                 device: int = 0, model: str = "rnnnoise"):
+        self.n_streams = n_streams
+        self.denoise = DenoiseState(weights, n_streams, device)
+        self.denoise.adapter_configure(input_rate, float(min(max(volume, 0.0), 1.0)))
+        self.denoise.playback_configure(output_rate)
+        if model != "rnnnoise":
+            self.set_model(model)
+
+    def set_model(self, name: str) -> None:
+        """A fresh processor of the named model at the remembered rates and the current volume, also when it is unchanged:
+        "rnnnoise", "noisy", anything else is the dummy (`ModelKind::from_name`)."""
+        self.denoise.model_configure(name if name in ("rnnnoise", "noisy") else "dummy")
+
+    def model(self) -> int:
+        return self.denoise.model()
+
+    def set_volume(self, volume: float) -> None:
+        self.denoise.adapter_set_volume(float(min(max(volume, 0.0), 1.0)))
+
+    def produced_rate_hz(self) -> float:
+        """RNNoise: the effective rate (48000 when it resamples); Legacy: the raw capture rate."""
+        return self.denoise.adapter_produced_rate_hz()
+
+    def push_block(self, x: np.ndarray) -> np.ndarray:
+        """A loop of `push_sample` over the columns of x [B, n] as one `crispy_rn_push` -> [B, n_out]."""
+        return self.denoise.push(x)
+
+    def pull_block(self, n: int, channels: int = 1, fmt: str = "f32") -> np.ndarray:
+        """n calls of `next_sample` and the output callback's conversion as one `crispy_rn_pull`."""
+        return self.denoise.pull(n, channels, fmt)
+
+    def push_sample(self, samples) -> Optional[np.ndarray]:
+        samples = np.atleast_1d(np.asarray(samples, dtype=np.float32))
+        out = self.denoise.push(samples.reshape(self.n_streams, 1))
+        return out.T if out.shape[1] else None
+
+    def next_sample(self) -> np.ndarray:
+        return self.denoise.pull(1)[:, 0]
+
+
 REC_SAMPLE_RATE = 48000          # recording::SAMPLE_RATE (recording.rs:8)
 
 
@@ -526,10 +645,13 @@ class CaptureBuffers:
         self.sum = np.float32(0.0)
         self.frames = np.float32(0.0)
 
-    def push_mono(self, mono: float, ns: "Optional[RnnNoiseProcessor]", raw_input_rate_hz: float) -> None:
+    def push_mono(self, mono: float, ns: "RnnNoiseProcessor | NsState | SharedAudio | None", raw_input_rate_hz: float) -> None:
+        """ns: any processor with `produced_rate_hz` and `push_sample` -- with an `NsState` the rate follows the model, so a
+        switch from RNNoise at 44.1 kHz (produces 48000) to a Legacy model (produces 44100) resets the recording resampler at
+        the first Legacy sample, and dummy <-> noisy at one rate does not."""
         mono = np.float32(mono)
         if ns is not None:
-            produced_rate = ns.produced_rate_hz()
+            produced_rate = float(ns.produced_rate_hz())
             out = ns.push_sample([mono])
             samples = None if out is None else out[:, 0]
         else:

@@ -396,6 +396,51 @@ int crispy_rn_record_app_push_at_device(crispy_rn *h, const float *d_in, long in
 /* the same with a HOST pointer; returns when the ring holds the samples */
 int crispy_rn_record_app_push_at(crispy_rn *h, const float *in, long in_stride, long n_frames, int channels, int from_rate);
 
+/*
+ * The other variant of NsState, Legacy(SharedAudio) (audio.rs:47-71, 136-200, 317-358), and the model switch of
+ * set_monitoring_model (audio.rs:942-967).  A handle is one of three models; the existing calls dispatch on it as NsState's
+ * methods do, so a host keeps its one push (or capture) per capture callback and its one pull per playback callback.  A handle
+ * whose model was never configured, or is CRISPY_NS_RNNOISE, takes exactly the paths described above.
+ *
+ * In a Legacy model (SharedAudio; every result bit for bit that of the per-sample loops):
+ *   crispy_rn_push*     *n_out = n_in, no first-frame drop: d_out[k] = x * volume, CRISPY_NS_NOISY: + noise * 0.05, where
+ *                       rng = rng * 1664525 + 1013904223 (wrapping u32) per sample and noise = (rng as f32 / 2^32) * 2.0 - 1.0
+ *                       -- every multiply and add rounded on its own.  The RAW x goes to the playback ring, which holds
+ *                       `rate as usize` samples at the raw capture rate.  What was returned goes through the capture callback's
+ *                       LinearResampler(rate, 48000) -- the one resampler state that the bypass arm uses, reset by
+ *                       crispy_rn_bypass_configure; do not push to a handle while it is bypassed -- and from there to the mic
+ *                       ring if the handle records; its positions and last sample advance on every Legacy push whether or
+ *                       not it records.  It is reset, as push_mono_to_buffers does (audio.rs:701-709), when the rate produced
+ *                       is 1 Hz or more off the rate of the last push that returned samples: RNNoise at 44.1 kHz (produces
+ *                       48000) followed by a Legacy model (produces 44100) resets it at the first Legacy sample; dummy <->
+ *                       noisy at one rate does not.  d_frames48, d_vad and vad must be NULL.  crispy_rn_push_out_len is n_in,
+ *                       crispy_rn_adapter_produced_rate_hz the configured rate.
+ *   crispy_rn_pull*     SharedAudio::next_sample: step = raw rate / output rate, s0 + (s1 - s0) * frac, NOISY: + noise * 0.05
+ *                       from the same LCG, then * the CURRENT volume (applied at the push and again here, as the reference
+ *                       does), conversion and fan-out as above.  A dry frame is 0.0 and advances neither the LCG nor the position.
+ *   crispy_rn_capture*  mono, level, then the Legacy push; a configured bypass still wins.
+ *   crispy_rn_adapter_configure   a fresh processor of the same Legacy kind at the new rate and volume;
+ *   crispy_rn_playback_configure  sizes the ring from the raw rate.
+ * The LCG state lives on the host, one for all streams: noise comes in the order of the calls, a Noisy push advances it by
+ * n_in, a Noisy pull by *n_live.
+ */
+#define CRISPY_NS_RNNOISE 0   /* NsState::RnnNoise */
+#define CRISPY_NS_DUMMY 1     /* NsState::Legacy, ModelKind::Dummy: "Select suppressor", suppression off */
+#define CRISPY_NS_NOISY 2     /* NsState::Legacy, ModelKind::Noisy */
+/* set_monitoring_model: a fresh processor of that model at the handle's configured capture rate, its current volume and (if
+ * configured) output rate -- also when the model is unchanged.  CRISPY_NS_RNNOISE: exactly crispy_rn_adapter_configure(rate,
+ * volume) with the current values.  Legacy: SharedAudio::new -- on a handle with playback the ring is emptied and sized
+ * `rate as usize`, resample_pos = 0 --, rng_state = 0x1234abcd.  The recording rings and the callback's resampler stay as
+ * they are.  Allocates before it changes anything: CRISPY_ERR_INVALID_ARG (NULL h, an unknown model) and CRISPY_ERR_OOM leave
+ * the handle as it was. */
+int crispy_rn_model_configure(crispy_rn *h, int model);
+/* the handle's model, a CRISPY_NS_*; CRISPY_NS_RNNOISE on a handle never configured */
+int crispy_rn_model(const crispy_rn *h, int *model);
+/* Pure, no device: SharedAudio's LCG.  Returns the state after n steps from `state` (0 ... 2^32 - 1; a long so that bindings
+ * need no unsigned type), < 0 = error: a negative argument, a state out of range.  noise (nullable) receives the n noise
+ * values of those steps; without it the call is O(log n): 2^j steps are one affine map, as in the kernels. */
+long crispy_ns_noise_state(long state, long n, float *noise);
+
 /* Block until everything enqueued on the handle's own stream has finished. */
 int crispy_rn_synchronize(crispy_rn *h);
 
