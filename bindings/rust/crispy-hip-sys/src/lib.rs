@@ -288,6 +288,8 @@ extern "C" {
     pub fn crispy_asr_align_device(h: *mut crispy_asr, d_enc: *const c_float, batch: c_int, tokens: *const c_int, n_tokens: *const c_int, ld_tokens: c_int, n_sot: c_int, n_frames: *const c_int, heads: *const c_int, n_heads: c_int, d_probs: *mut c_float, d_matrix: *mut c_float, jump_times: *mut c_float) -> c_int;
     pub fn crispy_asr_dtw_device(h: *mut crispy_asr, d_x: *const c_float, n_rows: c_int, n_cols: c_int, ld: c_long, text_idx: *mut c_int, time_idx: *mut c_int, n_path: *mut c_int) -> c_int;
     pub fn crispy_asr_set_confidence(h: *mut crispy_asr, on: c_int) -> c_int;
+    pub fn crispy_asr_set_audio_ctx(h: *mut crispy_asr, n: c_int) -> c_int;
+    pub fn crispy_asr_audio_ctx(h: *const crispy_asr, n: *mut c_int) -> c_int;
     pub fn crispy_asr_result_token_probs(r: *const crispy_asr_result, plog: *mut *const c_float, p_forced: *mut *const c_float, n: *mut c_int) -> c_int;
     pub fn crispy_asr_result_word_probs(r: *const crispy_asr_result, prob: *mut *const c_float, n: *mut c_int) -> c_int;
     pub fn crispy_asr_result_language_probs(r: *const crispy_asr_result, probs: *mut *const c_float, n_lang: *mut c_int) -> c_int;

@@ -58,7 +58,8 @@ ASR_SYMBOLS = ("crispy_asr_create", "crispy_asr_set_tensor", "crispy_asr_finaliz
                "crispy_asr_decode_window_device", "crispy_asr_transcribe_recording", "crispy_asr_transcribe_hooks",
                "crispy_asr_align_device", "crispy_asr_dtw_device",
                "crispy_asr_set_confidence", "crispy_asr_result_token_probs", "crispy_asr_result_word_probs",
-               "crispy_asr_result_language_probs", "crispy_asr_detect_language_probs_device", "crispy_asr_token_probs_device")
+               "crispy_asr_result_language_probs", "crispy_asr_detect_language_probs_device", "crispy_asr_token_probs_device",
+               "crispy_asr_set_audio_ctx", "crispy_asr_audio_ctx")
 RS_SYMBOLS = ("crispy_resampler_create", "crispy_resampler_destroy", "crispy_resampler_out_len",
               "crispy_resampler_process_device", "crispy_resampler_synchronize")
 ALL_SYMBOLS = RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS
@@ -275,6 +276,8 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_asr_result_language_probs.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int)]
     L.crispy_asr_detect_language_probs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.crispy_asr_token_probs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.crispy_asr_set_audio_ctx.argtypes = [C.c_void_p, C.c_int]
+    L.crispy_asr_audio_ctx.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.crispy_resampler_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.crispy_resampler_destroy.argtypes = [C.c_void_p]
     L.crispy_resampler_destroy.restype = None

@@ -134,9 +134,9 @@ class WhisperModel:
         return pcm, lens
 
     def encode(self, clips) -> np.ndarray:
-        """PCM clips (16 kHz, <= 30 s each) -> encoder output [B, 1500, d]."""
+        """PCM clips (16 kHz, <= 30 s each) -> encoder output [B, audio_ctx, d] (1500 rows unless `set_audio_ctx` says less)."""
         pcm, lens = self._pack(clips)
-        out = np.empty((pcm.shape[0], self.hp.n_audio_ctx, self.hp.n_audio_state), dtype=np.float32)
+        out = np.empty((pcm.shape[0], self.audio_ctx, self.hp.n_audio_state), dtype=np.float32)
         self._ck(self._L.crispy_asr_encode(self._h, pcm.ctypes.data, pcm.shape[1], lens.ctypes.data, pcm.shape[0],
                                           out.ctypes.data))
         return out
@@ -158,6 +158,19 @@ class WhisperModel:
         (whisper.cpp's ggml numerics); 2: mode 1 + the decoder's LayerNorm outputs rounded to f16 in front of q | k | v,
         cross q and fc1 (ggml's rounding points for those products too; opt-in)."""
         self._ck(self._L.crispy_asr_set_precision(self._h, int(mode)))
+
+    def set_audio_ctx(self, n: int = 0):
+        """`crispy_asr_set_audio_ctx` (whisper.cpp's `audio_ctx`, `-ac N`): from the next call on the encoder runs over the
+        first n of its positions and every cross-attention reads n keys; 0 = the model's own.  Encoder outputs -- `encode`'s
+        result, every d_enc argument -- are then [B, n, d]."""
+        self._ck(self._L.crispy_asr_set_audio_ctx(self._h, int(n)))
+
+    @property
+    def audio_ctx(self) -> int:
+        """`crispy_asr_audio_ctx`: encoder rows / cross-attention keys per clip in effect (never 0)."""
+        n = C.c_int()
+        self._ck(self._L.crispy_asr_audio_ctx(self._h, C.byref(n)))
+        return int(n.value)
 
     def stage_logits_device(self, d_x: int, batch: int, d_logits: int):
         """Final LayerNorm + vocabulary projection of d_x [batch][n_text_state] into d_logits [batch][n_vocab] (device

@@ -128,14 +128,14 @@ void choose_decode_path(crispy_asr* h) {
 
 bool fused_step_ok(const crispy_asr* h, const DecodePass& p) {
   return h->fused_path && h->enc_precision == 1 && !h->resident && h->ln16_ready && h->dec[0].qkv_p && h->tok_emb_hp && h->dw.fx[0] &&
-         p.rows <= FUSED_MAX_ROWS && fused_decode_supported(h->hp.n_text_state, p.max_keys, h->hp.n_audio_ctx);
+         p.rows <= FUSED_MAX_ROWS && fused_decode_supported(h->hp.n_text_state, p.max_keys, h->audio_ctx);
 }
 
 // A generated token's decoder step through the fused kernels (whisper_dec_fused.hip): 3 launches per layer + the final
 // LayerNorm + the vocabulary projection.  The token's embedding is in h->dw.dx (written by the pick that chose it), its
 // position in h->dw.counters[0]; one row per decoder, `rows / xgroup` clips (rows of a clip share its cross K | V).
 int decoder_step_fused(crispy_asr* h, const DecodePass& p, hipStream_t s) {
-  const int dt = h->hp.n_text_state, Tn = h->hp.n_audio_ctx, C = h->hp.n_text_ctx, rows = p.rows;
+  const int dt = h->hp.n_text_state, Tn = h->audio_ctx, C = h->hp.n_text_ctx, rows = p.rows;
   const size_t clips = (size_t)rows, xclips = (size_t)(rows / p.xgroup);
   const int attn16 = h->dec_attn16 ? 1 : 0;
   const int stream_kv = xclips * h->dec.size() * Tn * 2 * dt * 2 > ((size_t)256 << 20) ? 1 : 0;      // see step_ctx
@@ -496,7 +496,7 @@ int layer_cross_and_mlp(StepCtx& c, size_t l) {
 // what is the same for every layer of an un-fused step of pass `p`: P positions from `pos` on (a prompt step), or one at the
 // device position (a generated token)
 StepCtx step_ctx(crispy_asr* h, const DecodePass& p, int pos, int P, bool dev_pos, hipStream_t s) {
-  const int dt = h->hp.n_text_state, Tn = h->hp.n_audio_ctx;
+  const int dt = h->hp.n_text_state, Tn = h->audio_ctx;
   StepCtx c{};
   c.h = h; c.s = s; c.clips = p.rows; c.P = P; c.rows = p.rows * P; c.pos = pos; c.dev_pos = dev_pos;
   if (dev_pos) c.pos_dev = h->dw.counters;
@@ -604,7 +604,7 @@ Special special_tokens(const crispy_asr* h) { return vocab_specials(h->hp.n_voca
 
 // cross K | V of every layer, once per window (f16 mode: the decode steps stream an f16 copy of it)
 int compute_cross_kv(crispy_asr* h, const float* d_enc, int batch, hipStream_t s) {
-  const int dt = h->hp.n_text_state, Tn = h->hp.n_audio_ctx;
+  const int dt = h->hp.n_text_state, Tn = h->audio_ctx;
   if (h->enc_precision == 1 && (h->dec[0].xkv_wh || h->resident)) {
     // The reference's precision: the projection itself on the f16 matrix cores (encoder output and weights rounded
     // to f16, f32 accumulation), written as f16 head-major straight from the epilogue.  (It used to run as an f32 GEMM
@@ -629,6 +629,7 @@ int compute_cross_kv(crispy_asr* h, const float* d_enc, int batch, hipStream_t s
     // head-major store: per clip [K | V][head][Tn][64], so the decode-step attention streams contiguous runs
     GemmArgs g = gemm(d_enc, dt, h->dec[l].xkv_w, dt, xkv, 2L * dt, h->dec[l].xkv_b, batch * Tn, 2 * dt, dt);
     g.hm_rows = Tn; g.hm_width = dt;
+    g.tiled = 1;      // the head-major store is the tiled kernel's (a small audio context has a decode step's row count)
     HIP_TRY(gemm_f32_nt(g, 1, s));
   }
   if (h->enc_precision == 1)

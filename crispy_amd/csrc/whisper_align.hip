@@ -366,7 +366,10 @@ int run_alignment(crispy_asr* h, const float* d_enc, const std::vector<std::vect
                   std::vector<std::vector<float>>* logp = nullptr) {
   const int batch = (int)rows.size();
   if (batch == 0) return CRISPY_OK;
-  const int dt = h->hp.n_text_state, Tn = h->hp.n_audio_ctx, L = h->hp.n_text_layer, C = h->hp.n_text_ctx;
+  // Tn: keys per clip of the cross K | V the prefill builds (the handle's audio context); Tm: the model's own -- the bound of
+  // n_frames / 2 and the leading dimension of d_probs / d_matrix, which does not move with the setting
+  const int dt = h->hp.n_text_state, Tn = h->audio_ctx, Tm = h->hp.n_audio_ctx, L = h->hp.n_text_layer, C = h->hp.n_text_ctx;
+  auto keys_of = [&](int b) { return std::min(n_frames[b] / 2, Tn); };      // F: the frames a clip is aligned over
   if (dt % kHd != 0) return fail(CRISPY_ERR_UNSUPPORTED, "alignment: n_text_state %d is not whole 64-wide heads", dt);
   int n_rows = 0;
   for (int b = 0; b < batch; ++b) {
@@ -374,8 +377,9 @@ int run_alignment(crispy_asr* h, const float* d_enc, const std::vector<std::vect
     if (R < n_sot + 2 || R > C) return fail(CRISPY_ERR_INVALID_ARG, "alignment: clip %d has %d token rows (%d ... %d)", b, R, n_sot + 2, C);
     for (int t : rows[b])
       if (t < 0 || t >= h->hp.n_vocab) return fail(CRISPY_ERR_INVALID_ARG, "alignment: token %d out of range", t);
-    const int F = n_frames[b] / 2;
-    if (F < 4 || F > Tn) return fail(CRISPY_ERR_INVALID_ARG, "alignment: clip %d has %d frames (8 ... %d)", b, n_frames[b], 2 * Tn);
+    const int F = keys_of(b);
+    if (F < 4 || n_frames[b] / 2 > Tm)
+      return fail(CRISPY_ERR_INVALID_ARG, "alignment: clip %d has %d frames over %d keys (8 ... %d frames, >= 4 keys)", b, n_frames[b], Tn, 2 * Tm);
     const int N = R - n_sot - 1;
     if (!align_dtw_fits(N, F))
       return fail(CRISPY_ERR_UNSUPPORTED, "alignment: %d x %d DTW cells exceed the LDS trace", N, F);
@@ -393,9 +397,9 @@ int run_alignment(crispy_asr* h, const float* d_enc, const std::vector<std::vect
   for (int k = 0; k < n_heads; ++k)
     if (A.slot[heads[2 * k]] < 0) A.slot[heads[2 * k]] = n_slots++;
   HIP_TRY(A.q.grow((size_t)n_slots * batch * n_rows * dt * sizeof(float)));
-  const int ld_f = Tn;
+  const int ld_f = Tm;
   int max_n = 0;
-  for (int b = 0; b < batch; ++b) max_n = std::max(max_n, (int)rows[b].size() - n_sot - 1 + n_frames[b] / 2);
+  for (int b = 0; b < batch; ++b) max_n = std::max(max_n, (int)rows[b].size() - n_sot - 1 + keys_of(b));
   const size_t need = 256 * 8 + (size_t)batch * n_heads * n_rows * sizeof(float2) + (d_matrix_out ? 0 : (size_t)batch * ld_rows * ld_f * sizeof(float)) +
                       (size_t)batch * n_rows * sizeof(int) + (size_t)batch * sizeof(AlignClip) + (size_t)n_heads * (sizeof(int2) + sizeof(int));
   HIP_TRY(A.ws.grow(need));
@@ -409,7 +413,7 @@ int run_alignment(crispy_asr* h, const float* d_enc, const std::vector<std::vect
   std::vector<AlignClip> hc((size_t)batch);
   for (int b = 0; b < batch; ++b) {
     const int R = (int)rows[b].size();
-    hc[b] = AlignClip{n_rows - R, R, n_frames[b] / 2, n_sot, R - n_sot - 1};      // (the left padding begin_pass gives the row)
+    hc[b] = AlignClip{n_rows - R, R, keys_of(b), n_sot, R - n_sot - 1};      // (the left padding begin_pass gives the row)
   }
   std::vector<int2> hh((size_t)n_heads);
   std::vector<int> hl((size_t)n_heads);
@@ -446,7 +450,7 @@ int run_alignment(crispy_asr* h, const float* d_enc, const std::vector<std::vect
   a.heads = d_heads; a.head_layer = d_head_layer; a.n_heads = n_heads; a.clips = d_clips;
   a.stats = d_stats; a.n_rows = n_rows; a.matrix = d_matrix; a.probs = d_probs; a.ld_rows = ld_rows; a.ld_f = ld_f;
   int max_f = 0;
-  for (int b = 0; b < batch; ++b) max_f = std::max(max_f, n_frames[b] / 2);
+  for (int b = 0; b < batch; ++b) max_f = std::max(max_f, keys_of(b));
   hipLaunchKernelGGL(align_rowstats_kernel, dim3(n_heads, batch), dim3(256), 0, s, a);
   HIP_TRY(hipGetLastError());
   HIP_TRY(lds_limit(reinterpret_cast<const void*>(align_matrix_kernel), matrix_lds(n_rows)));

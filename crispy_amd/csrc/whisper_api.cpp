@@ -288,6 +288,7 @@ int crispy_asr_create(const crispy_asr_hparams* hp, const float* mel_filters, in
   if (!h) return fail(CRISPY_ERR_OOM, "crispy_asr_create: host allocation failed");
   h->device = device;
   h->hp = *hp;
+  h->audio_ctx = hp->n_audio_ctx;
   h->eot = hp->n_vocab >= 51865 ? 50257 : 50256;   // multilingual vocabularies shift the specials by one
   if (const char* e = dev_env("CRISPY_ASR_XCD")) h->xcd_swizzle = std::atoi(e) != 0;
   auto body = [&]() -> int {
@@ -648,15 +649,44 @@ int crispy_asr_set_precision(crispy_asr* h, int mode) try {
   return CRISPY_OK;
 } CRISPY_CATCH_RET("crispy_asr_set_precision")
 
+// whisper.cpp's whisper_full_params.audio_ctx [UPSTREAM-RECALL].  Every call builds its encoder output and cross K | V from
+// h->audio_ctx, so nothing of an earlier layout is read after a switch; what bakes the value in are the captured decode
+// steps (key count, strides, stream_kv of their launches): they go, after everything in flight on the handle has finished.
+int crispy_asr_set_audio_ctx(crispy_asr* h, int n) try {
+  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_set_audio_ctx: NULL handle");
+  if (!h->finalized) return fail(CRISPY_ERR_BAD_MODEL, "crispy_asr_set_audio_ctx: model not finalized");
+  if (n < 0 || n > h->hp.n_audio_ctx)
+    return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_set_audio_ctx: n = %d (0 = the model's own, or 1 ... %d)", n, h->hp.n_audio_ctx);
+  const int want = n == 0 ? h->hp.n_audio_ctx : n;
+  if (want == h->audio_ctx) return CRISPY_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->drop_graphs();
+  h->audio_ctx = want;
+  return CRISPY_OK;
+} CRISPY_CATCH_RET("crispy_asr_set_audio_ctx")
+
+int crispy_asr_audio_ctx(const crispy_asr* h, int* n) try {
+  if (!h || !n) return fail(CRISPY_ERR_INVALID_ARG, "crispy_asr_audio_ctx: NULL argument");
+  if (!h->finalized) return fail(CRISPY_ERR_BAD_MODEL, "crispy_asr_audio_ctx: model not finalized");
+  *n = h->audio_ctx;
+  return CRISPY_OK;
+} CRISPY_CATCH_RET("crispy_asr_audio_ctx")
+
 }  // extern "C"
 
 namespace crispy {
 namespace asr {
 namespace {
 
-// the convolution stem: padded frame-major mel -> residual stream h->ew.x [batch * 1500][d] (GELU, positional embedding added)
+// the convolution stem: padded frame-major mel -> residual stream h->ew.x [batch * Tn][d] (GELU, positional embedding added).
+// Tn = the handle's audio context.  Below the model's own, conv1 runs over the first 2 Tn frames and must see its own zero
+// padding at frame 2 Tn [UPSTREAM-RECALL: whisper.cpp builds the graph over a 2 * audio_ctx view of the mel], where the
+// caller's buffer holds the real frame: `cut` clears padded row 2 Tn + 1 in a copy (mode 1 has one anyway: the f16 mel).
 int encode_stem(crispy_asr* h, const float* d_mel_t, int batch, hipStream_t s) {
-  const int d = h->hp.n_audio_state, Tn = h->hp.n_audio_ctx, nm = h->hp.n_mels;
+  const int d = h->hp.n_audio_state, Tn = h->audio_ctx, nm = h->hp.n_mels;
+  const bool cut = Tn < h->hp.n_audio_ctx;
+  const int M1 = 2 * Tn;                                      // conv1's frames
   if (h->enc_precision == 1) {
     // The convolution stem on the f16 matrix cores too (ggml runs a convolution as im2col in f16 x f16 kernel): the
     // frame-major mel is rounded to f16 once, conv1 writes GELU(h1) as f16 (it only feeds conv2), conv2 reads it as
@@ -666,13 +696,14 @@ int encode_stem(crispy_asr* h, const float* d_mel_t, int batch, hipStream_t s) {
     const long mel_n = (long)batch * (MEL_FRAMES + 2) * nm;
     HIP_TRY(convert_f32_to_f16(d_mel_t, mel_h, mel_n, s));
     HIP_TRY(hipMemsetAsync(mel_h + mel_n, 0, 64 * sizeof(_Float16), s));  // what the last row's padded columns read
+    if (cut) HIP_TRY(hipMemset2DAsync(mel_h + (size_t)(M1 + 1) * nm, (size_t)(MEL_FRAMES + 2) * nm * 2, 0, (size_t)nm * 2, batch, s));
     HIP_TRY(hipMemset2DAsync(h1_h, (size_t)(MEL_FRAMES + 1) * d * 2, 0, (size_t)d * 2, batch, s));
     {
       HGemmArgs g{};
       g.A = mel_h; g.lda = nm; g.strideA = (long)(MEL_FRAMES + 2) * nm;
       g.W = reinterpret_cast<const _Float16*>(h->conv1_wh); g.ldw = h->conv1_kp;
       g.C = h1_h + d; g.ldc = d; g.strideC = (long)(MEL_FRAMES + 1) * d;
-      g.bias = h->conv1_b; g.M = MEL_FRAMES; g.N = d; g.K = h->conv1_kp; g.gelu = 1;
+      g.bias = h->conv1_b; g.M = M1; g.N = d; g.K = h->conv1_kp; g.gelu = 1;
       HIP_TRY(gemm_hh(g, HGEMM_F16, batch, s));
     }
     {
@@ -688,8 +719,14 @@ int encode_stem(crispy_asr* h, const float* d_mel_t, int batch, hipStream_t s) {
     // conv1 (k3, p1) + GELU: rows t of the padded frame-major mel are 3*n_mels contiguous floats
     // (the zero row in front of every clip's h1 is rewritten each call: precision mode 1 uses the same workspace as f16)
     HIP_TRY(hipMemset2DAsync(h->ew.h1, (size_t)(MEL_FRAMES + 1) * d * sizeof(float), 0, (size_t)d * sizeof(float), batch, s));
+    if (cut) {      // rows 0 .. 2 Tn of every clip into the hidden-layer workspace (free until fc1), row 2 Tn + 1 cleared
+      const size_t pitch = (size_t)(MEL_FRAMES + 2) * nm * sizeof(float);
+      HIP_TRY(hipMemcpy2DAsync(h->ew.h, pitch, d_mel_t, pitch, (size_t)(M1 + 1) * nm * sizeof(float), batch, hipMemcpyDeviceToDevice, s));
+      HIP_TRY(hipMemset2DAsync(h->ew.h + (size_t)(M1 + 1) * nm, pitch, 0, (size_t)nm * sizeof(float), batch, s));
+      d_mel_t = h->ew.h;
+    }
     {
-      GemmArgs g = gemm(d_mel_t, nm, h->conv1_w, 3L * nm, h->ew.h1 + d, d, h->conv1_b, MEL_FRAMES, d, 3 * nm);
+      GemmArgs g = gemm(d_mel_t, nm, h->conv1_w, 3L * nm, h->ew.h1 + d, d, h->conv1_b, M1, d, 3 * nm);
       g.strideA = (long)(MEL_FRAMES + 2) * nm;
       g.strideC = (long)(MEL_FRAMES + 1) * d;
       g.gelu = 1;
@@ -711,7 +748,7 @@ int encode_stem(crispy_asr* h, const float* d_mel_t, int batch, hipStream_t s) {
 
 // the encoder layers over h->ew.x in precision mode 1
 int encode_layers_f16(crispy_asr* h, int batch, hipStream_t s) {
-  const int d = h->hp.n_audio_state, Tn = h->hp.n_audio_ctx, H = h->hp.n_audio_head;
+  const int d = h->hp.n_audio_state, Tn = h->audio_ctx, H = h->hp.n_audio_head;
   const long rows = (long)batch * Tn;
   int rc = CRISPY_OK;
   // whisper.cpp's numerics with the bytes halved: every activation that only feeds a matrix product is stored as the
@@ -768,25 +805,34 @@ int encode_layers_f16(crispy_asr* h, int batch, hipStream_t s) {
 
 // ... and in precision mode 0 (f32 operands)
 int encode_layers_f32(crispy_asr* h, int batch, hipStream_t s) {
-  const int d = h->hp.n_audio_state, Tn = h->hp.n_audio_ctx, H = h->hp.n_audio_head;
+  const int d = h->hp.n_audio_state, Tn = h->audio_ctx, H = h->hp.n_audio_head;
   const long rows = (long)batch * Tn;
+  // g.tiled: the 128 x 128 kernel at every row count.  At a small audio context batch x Tn falls into the skinny kernel's
+  // range (a decode step's shape), whose sums run in another order: a clip's bits would depend on the batch it is encoded in.
   for (const EncLayer& L : h->enc) {
     HIP_TRY(layernorm_f32(h->ew.x, L.ln1_w, L.ln1_b, h->ew.xn, rows, d, s));
-    HIP_TRY(gemm_f32_nt(gemm(h->ew.xn, d, L.qkv_w, d, h->ew.qkv, 3L * d, L.qkv_b, (int)rows, 3 * d, d), 1, s));
+    {
+      GemmArgs g = gemm(h->ew.xn, d, L.qkv_w, d, h->ew.qkv, 3L * d, L.qkv_b, (int)rows, 3 * d, d);
+      g.tiled = 1;
+      HIP_TRY(gemm_f32_nt(g, 1, s));
+    }
     HIP_TRY(attn_encoder_f32(h->ew.qkv, h->ew.att, batch, Tn, d, H, s));
     {
       GemmArgs g = gemm(h->ew.att, d, L.out_w, d, h->ew.x, d, L.out_b, (int)rows, d, d);
+      g.tiled = 1;
       g.residual = h->ew.x; g.ldr = d;
       HIP_TRY(gemm_f32_nt(g, 1, s));
     }
     HIP_TRY(layernorm_f32(h->ew.x, L.ln2_w, L.ln2_b, h->ew.xn, rows, d, s));
     {
       GemmArgs g = gemm(h->ew.xn, d, L.fc1_w, d, h->ew.h, 4L * d, L.fc1_b, (int)rows, 4 * d, d);
+      g.tiled = 1;
       g.gelu = 1;
       HIP_TRY(gemm_f32_nt(g, 1, s));
     }
     {
       GemmArgs g = gemm(h->ew.h, 4L * d, L.fc2_w, 4L * d, h->ew.x, d, L.fc2_b, (int)rows, d, 4 * d);
+      g.tiled = 1;
       g.residual = h->ew.x; g.ldr = d;
       HIP_TRY(gemm_f32_nt(g, 1, s));
     }
@@ -830,7 +876,7 @@ int crispy_asr_encode_device(crispy_asr* h, const float* d_mel_t, int batch, flo
   rc = encode_stem(h, d_mel_t, batch, s);
   if (rc == CRISPY_OK) rc = h->enc_precision == 1 ? encode_layers_f16(h, batch, s) : encode_layers_f32(h, batch, s);
   if (rc != CRISPY_OK) return rc;
-  const long rows = (long)batch * h->hp.n_audio_ctx;
+  const long rows = (long)batch * h->audio_ctx;
   const int d = h->hp.n_audio_state;
   HIP_TRY(layernorm_f32(h->ew.x, h->ln_post_w, h->ln_post_b, d_out, rows, d, s));
   return CRISPY_OK;
@@ -853,7 +899,7 @@ int crispy_asr_encode(crispy_asr* h, const float* pcm, long pcm_stride, const in
   if (rc != CRISPY_OK) return rc;
   rc = crispy_asr_encode_device(h, h->ew.melt, batch, h->ew.enc, h->stream);
   if (rc != CRISPY_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(out, h->ew.enc, (size_t)batch * h->hp.n_audio_ctx * h->hp.n_audio_state * sizeof(float),
+  HIP_TRY(hipMemcpyAsync(out, h->ew.enc, (size_t)batch * h->audio_ctx * h->hp.n_audio_state * sizeof(float),
                          hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return CRISPY_OK;

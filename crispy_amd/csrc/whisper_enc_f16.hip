@@ -44,6 +44,16 @@ __device__ __forceinline__ half4 to_half4(float a, float b, float c, float d) {
   return half4{lo[0], lo[1], hi[0], hi[1]};
 }
 
+// EPI_VT with rows per clip T % 4 != 0 (a reduced audio context): the four consecutive rows m .. m + 3 of a register group
+// may lie in two clips and start at any t, so they are stored one by one -- V^T[clip][n][t], each row by its own (clip, t)
+__device__ __forceinline__ void vt_store_rows(_Float16* __restrict__ C, half4 v, int m, int M, int T, int N, int n) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int me = m + e, clip = me / T, t = me - clip * T;
+    if (me < M) C[((long)clip * N + n) * ENC_TP + t] = v[e];
+  }
+}
+
 template <int PER>
 __global__ __launch_bounds__(256) void layernorm_h_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, _Float16* __restrict__ y,
@@ -195,11 +205,15 @@ __device__ __forceinline__ void hh_epilogue(const HGemmArgs& g, f32x16 (&acc)[2]
         const float bias = g.bias ? g.bias[nc] : 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const int m = m0 + wm + 32 * i + 8 * q + 4 * lh;       // four consecutive rows; T % 4 == 0, so one clip
+          const int m = m0 + wm + 32 * i + 8 * q + 4 * lh;       // four consecutive rows: one clip and 8-byte aligned where T % 4 == 0
           const int clip = m / g.vt_T, t = m - clip * g.vt_T;
           const half4 v = to_half4(acc[i][j][4 * q] + bias, acc[i][j][4 * q + 1] + bias, acc[i][j][4 * q + 2] + bias,
                                    acc[i][j][4 * q + 3] + bias);
-          if (m < g.M && n < g.N) *reinterpret_cast<half4*>(C + ((long)clip * g.N + nc) * ENC_TP + t) = v;
+          if ((g.vt_T & 3) == 0) {
+            if (m < g.M && n < g.N) *reinterpret_cast<half4*>(C + ((long)clip * g.N + nc) * ENC_TP + t) = v;
+          } else if (n < g.N) {
+            vt_store_rows(C, v, m, g.M, g.vt_T, g.N, nc);
+          }
         }
       }
   }
@@ -407,10 +421,14 @@ __device__ __forceinline__ void ep_store(const HGemmArgs& g, const float* T, con
     for (int p = 0; p < 8; ++p) {
       const int nl = (lane >> 3) + 8 * p;                     // column of this wave's 64
       const float4 x = *reinterpret_cast<const float4*>(T + nl * EP_VLD + c4);
-      const int m = m0 + wm + rb + c4;                        // four consecutive rows; vt_T % 4 == 0, so one clip
+      const int m = m0 + wm + rb + c4;                        // four consecutive rows: one clip and 8-byte aligned where vt_T % 4 == 0
       const int clip = m / g.vt_T, t = m - clip * g.vt_T;
-      if (m < g.M && nl < nrem)
-        *reinterpret_cast<half4*>(C + ((long)clip * g.N + (n0 + wn + nl)) * ENC_TP + t) = to_half4(x.x, x.y, x.z, x.w);
+      if ((g.vt_T & 3) == 0) {
+        if (m < g.M && nl < nrem)
+          *reinterpret_cast<half4*>(C + ((long)clip * g.N + (n0 + wn + nl)) * ENC_TP + t) = to_half4(x.x, x.y, x.z, x.w);
+      } else if (nl < nrem) {
+        vt_store_rows(C, to_half4(x.x, x.y, x.z, x.w), m, g.M, g.vt_T, g.N, n0 + wn + nl);
+      }
     }
   }
 }

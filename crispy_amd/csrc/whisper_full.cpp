@@ -546,7 +546,7 @@ int BatchCall::prepare() {
   lang.assign(nb, 0);
   for (int k = 0; k < nb; ++k) lens[k] = (int)n[live[k]];
   detect = sp.multilingual && !(opts && opts->language_token > 0);
-  enc_clip = (size_t)h->hp.n_audio_ctx * h->hp.n_audio_state;
+  enc_clip = (size_t)h->audio_ctx * h->hp.n_audio_state;      // a clip's encoder output: [audio context][d]
   return CRISPY_OK;
 }
 
@@ -924,8 +924,10 @@ int BatchCall::align_round(const std::vector<int>& act, std::vector<Accepted>& a
     row.push_back(h->eot);
     const int nf = std::min(3000, seek_end[k] - seek[k]);
     // a window the DTW kernel cannot hold (more than ~370 tokens: a caller's max_new_tokens) keeps its transcript and
-    // gets no alignment -- times -1, no words -- rather than failing the call
-    if (!align_dtw_fits((int)(row.size() - n0), nf / 2)) continue;       // rows: <|notimestamps|> + the text
+    // gets no alignment -- times -1, no words -- rather than failing the call; so does one aligned over fewer than 4 keys
+    // (F = min(nf / 2, the audio context): crispy_asr_set_audio_ctx below 4)
+    const int F = std::min(nf / 2, h->audio_ctx);
+    if (F < 4 || !align_dtw_fits((int)(row.size() - n0), F)) continue;       // rows: <|notimestamps|> + the text
     who.push_back(a);
     rows.push_back(std::move(row));
     n_frames.push_back(nf);

@@ -139,8 +139,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
           v += extra[r];
           if (m >= g.M || n >= g.N) continue;
           if (hm) {
-            int t = hm_t0 + dm, b = hm_b0;      // a 128-row tile crosses at most one clip boundary (hm_rows >= 128)
-            if (t >= g.hm_rows) { t -= g.hm_rows; ++b; }
+            int t = hm_t0 + dm, b = hm_b0;      // a 128-row tile crosses at most one clip boundary where hm_rows >= 128 ...
+            if (g.hm_rows < GB_M) { b = m / g.hm_rows; t = m - b * g.hm_rows; }      // ... and several below (a reduced audio context)
+            else if (t >= g.hm_rows) { t -= g.hm_rows; ++b; }
             C[(long)b * g.N * g.hm_rows + (long)t * 64 + hm_col] = v;
           } else {
             C[(long)m * g.ldc + n] = v;

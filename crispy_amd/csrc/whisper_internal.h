@@ -144,6 +144,12 @@ struct DecWs {
 struct crispy_asr {
   int device = 0;
   crispy_asr_hparams hp{};
+  // The effective audio context (crispy_asr_set_audio_ctx; whisper.cpp's whisper_full_params.audio_ctx [UPSTREAM-RECALL]):
+  // encoder rows and cross-attention keys per clip of every call, 1 ... hp.n_audio_ctx.  `hp` stays the model's: the
+  // workspaces are sized by it, and the leading dimension of the alignment outputs is hp.n_audio_ctx whatever this says.
+  // Everything laid out by it (encoder output [clip][audio_ctx][d], cross K | V [layer][clip][K|V][head][audio_ctx][64])
+  // is rebuilt by every call from this value; the captured steps bake it in and are dropped by the setter.
+  int audio_ctx = 0;
   hipStream_t stream = nullptr;
   crispy_mel* mel = nullptr;
   std::map<std::string, crispy::asr::Tensor> tensors;   // as named by the model file

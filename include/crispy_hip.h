@@ -568,6 +568,32 @@ int crispy_asr_synchronize(crispy_asr *h);
  * Oracle: encoder_forward_f16(attn16=True), DecoderCache(f16=True, ln16=True, attn16=True). */
 int crispy_asr_set_precision(crispy_asr *h, int mode);
 
+/* The audio context: whisper.cpp's whisper_full_params.audio_ctx (`-ac N`; whisper-rs set_audio_ctx) [UPSTREAM-RECALL:
+ * everything said about upstream here is recalled, not checked against its source].  With n, 1 <= n <= n_audio_ctx, every
+ * encoder pass of the handle from the next call on runs over the first n of the model's 1500 positions and every decoder
+ * cross-attention reads n keys:
+ *   - the encoder's input is the 2 n mel frames [seek, seek + 2 n) of the window's log-mel, normalised as without the
+ *     setting; conv1 sees its own zero padding at frame 2 n, not the real frame that follows; conv2 yields n rows, rows
+ *     0 .. n - 1 of encoder.positional_embedding are added, all layers and ln_post run over n rows.  This is NOT rows
+ *     0 .. n - 1 of the full-context output (attention is over n keys);
+ *   - crispy_asr_encode writes, and crispy_asr_encode_device's d_out and every d_enc argument of this header carry,
+ *     [batch][n][n_audio_state] while the setting is on (wherever a comment says [batch][1500][..] or [batch][n_audio_ctx][..]);
+ *   - every decode form attends over n keys: greedy, timestamp-rule, fallback and beam passes, prompts, language detection
+ *     (the setting holds for every encoder pass of the handle; whether upstream's first call on a state detects the language
+ *     at the full context is not pinned), crispy_asr_token_probs_device and the alignment pass;
+ *   - crispy_asr_align_device: F = min(n_frames / 2, n) keys are aligned; n_frames may still be up to 2 * n_audio_ctx, and
+ *     d_probs / d_matrix keep their n_audio_ctx leading dimension.  In a transcribe call a window with F < 4 gets no
+ *     alignment (times -1, no words), as a window beyond the DTW limits does;
+ *   - unchanged: log-mel, the seek loop, timestamp rules, thresholds, the no-speech rule, segment and word times (a key is
+ *     still 20 ms).  A timestamp beyond 2 n frames is the model's business, as upstream.
+ * n = 0 or n = n_audio_ctx: not set -- the launches and the bits of a handle that never saw this call.  Every n from 1 on is
+ * supported, in every precision mode and decode form; the batch contract (a clip's result is its solo result bit for bit)
+ * holds at every n.  Switching waits for the handle's stream and drops the captured decode steps; workspaces stay sized for
+ * n_audio_ctx.  CRISPY_ERR_INVALID_ARG: n < 0 or n > n_audio_ctx, NULL h; CRISPY_ERR_BAD_MODEL: not finalized.
+ * crispy_asr_audio_ctx: the effective value, never 0 (n_audio_ctx while not set). */
+int crispy_asr_set_audio_ctx(crispy_asr *h, int n);
+int crispy_asr_audio_ctx(const crispy_asr *h, int *n);
+
 /* Stage entry point (parity tests): the last step of the decoder alone -- final LayerNorm and vocabulary projection
  * of d_x [batch][n_text_state] (device, f32) into d_logits [batch][n_vocab] (device, f32), in the current precision
  * mode.  Mode 1: LayerNorm output rounded to f16 against the f16 token embedding, f32 accumulation (ggml's mul_mat
