@@ -19,6 +19,7 @@
 // windows of the same high-passed signal, so neither is stored as state: they are views of xhp.
 #include <type_traits>
 #include "rn_common.h"
+#include "rn_scale.h"
 #include "rn_wave_sums.h"
 
 namespace crispy {
@@ -632,21 +633,15 @@ __device__ __forceinline__ float wave_max(float v) {
   u = max(u, dm(u, std::integral_constant<int, 0x141>{}));
   u = max(u, dm(u, std::integral_constant<int, 0x140>{}));      // every lane of a 16-lane row holds the row maximum
   unsigned m = (unsigned)__builtin_amdgcn_readlane((int)u, 0);
+  // scalar maxima (s_max_u32), kept apart: two nested ones are combined into a v_max3_u32, which has no scalar form
   m = max(m, (unsigned)__builtin_amdgcn_readlane((int)u, 16));
+  asm volatile("" : "+s"(m));
   m = max(m, (unsigned)__builtin_amdgcn_readlane((int)u, 32));
-  m = max(m, (unsigned)__builtin_amdgcn_readlane((int)u, 48));   // scalar maxima (s_max_u32): no VALU
+  asm volatile("" : "+s"(m));
+  m = max(m, (unsigned)__builtin_amdgcn_readlane((int)u, 48));
   return __uint_as_float(m);
 }
-// scale pair of a vector whose largest magnitude is m (wave-uniform): up = 2^s, dn = 2^-s
-struct RnScale { float up, dn; };
-__device__ __forceinline__ RnScale scale_of(float m) {
-  int eb = (__float_as_int(m) >> 23) & 0xff;       // m < 2^(eb - 126)
-  eb = min(max(eb, 64), 250);
-  RnScale r;
-  r.up = __int_as_float((283 - eb) << 23);         // 2^(30 - (eb - 126))
-  r.dn = __int_as_float((eb - 29) << 23);
-  return r;
-}
+// scale pair (RnScale, scale_of) and its power-of-two multiples (scale_shift): rn_scale.h
 __device__ __forceinline__ void digits_store(signed char* img, int i, float v, float up) {
   const int q = __float2int_rn(v * up);
   const unsigned r = ((unsigned)q + 0x00808080u) ^ 0x00808080u;
@@ -678,15 +673,19 @@ __device__ __forceinline__ RnScale image_i8(signed char* img, int lane, F f) {
 __device__ __forceinline__ rn_u4 wload8(__amdgpu_buffer_rsrc_t rs, int row16, int off16) {
   return __builtin_amdgcn_raw_buffer_load_b128(rs, row16, off16 * 16, 0);
 }
-// acc[r] += sa sum_k W[k][row[r]] qa[k] + sb sum_k U[k][row[r]] qb[k]; toff = (lane & 3) * RN_IMG8_LD
-template <int MK16, int NK16, int ROWS, int NR>
+// acc[r] += sa sum_k W[k][row[r]] qa[k] + sb sum_k U[k][row[r]] qb[k]; toff = (lane & 3) * RN_IMG8_LD; sa, sb: a `dn` of scale_of.
+// NCH: accumulator chains per row for one and two rows per lane.  A second chain hides the latency of dependent matrix
+// instructions when nothing else does (three-wave kernel: one wave per SIMD) and costs four integer adds per row and fold;
+// at four waves per SIMD (one-wave kernel) the other waves cover it.  Integer sums: exact in either association.
+constexpr int rn_chains(int nw) { return nw == 1 ? 1 : 2; }
+template <int MK16, int NK16, int ROWS, int NR, int NCH>
 __device__ __forceinline__ void dotn_i(__amdgpu_buffer_rsrc_t rs, int w_off, int u_off, const int (&row)[NR],
                                        const signed char* xa, const signed char* xb, int toff, float sa, float sb,
                                        float (&acc)[NR]) {
   constexpr int K16 = MK16 + NK16;
   constexpr int BLK = NR >= 3 ? RN_BLK3 : (NR == 2 ? RN_BLK2 : RN_BLK1);
   constexpr int NBLK = (K16 + BLK - 1) / BLK;
-  constexpr int NC = NR >= 3 ? 1 : 2;
+  constexpr int NC = NR >= 3 ? 1 : NCH;
   int row16[NR];
 #pragma unroll
   for (int r = 0; r < NR; ++r) row16[r] = row[r] * 16;
@@ -713,9 +712,9 @@ __device__ __forceinline__ void dotn_i(__amdgpu_buffer_rsrc_t rs, int w_off, int
       rn_i4 d = a4[r][0];
       if (NC == 2) d += a4[r][1];
       float f = (float)d[0] * s;
-      f = fmaf((float)d[1], s * 256.f, f);
-      f = fmaf((float)d[2], s * 65536.f, f);
-      f = fmaf((float)d[3], s * 16777216.f, f);
+      f = fmaf((float)d[1], scale_shift<8>(s), f);
+      f = fmaf((float)d[2], scale_shift<16>(s), f);
+      f = fmaf((float)d[3], scale_shift<24>(s), f);
       acc[r] += f;
 #pragma unroll
       for (int c = 0; c < NC; ++c) a4[r][c] = rn_i4{0, 0, 0, 0};
@@ -763,12 +762,12 @@ __device__ __forceinline__ void dotn_i(__amdgpu_buffer_rsrc_t rs, int w_off, int
   }
   fold(NK16 > 0 ? sb : sa);
 }
-template <int K16, int ROWS>
+template <int K16, int ROWS, int NCH>
 __device__ __forceinline__ float dot_i(__amdgpu_buffer_rsrc_t rs, int w_off, int row, const signed char* x, int toff,
                                        float s, float acc0) {
   const int rows[1] = {row};
   float acc[1] = {acc0};
-  dotn_i<K16, 0, ROWS, 1>(rs, w_off, w_off, rows, x, x, toff, s, s, acc);
+  dotn_i<K16, 0, ROWS, 1, NCH>(rs, w_off, w_off, rows, x, x, toff, s, s, acc);
   return acc[0];
 }
 // in_img / sin: digit image and 2^-s of the layer input (caller); st_img: the state's image, then h*r's at the same
@@ -792,7 +791,7 @@ __device__ __forceinline__ void gru_layer_i(__amdgpu_buffer_rsrc_t rs, int w_off
       rows[r] = min(lane + WAVE * r, 2 * N - 1);
       acc[r] = ld_u32(bias, (unsigned)rows[r]);
     }
-    dotn_i<MK16, NK16, ROWS, NRZ>(rs, w_off, u_off, rows, in_img, st_img, toff, sin, sst.dn, acc);
+    dotn_i<MK16, NK16, ROWS, NRZ, rn_chains(NW)>(rs, w_off, u_off, rows, in_img, st_img, toff, sin, sst.dn, acc);
 #pragma unroll
     for (int r = 0; r < NRZ; ++r) {
       const int row = lane + WAVE * r;
@@ -812,7 +811,7 @@ __device__ __forceinline__ void gru_layer_i(__amdgpu_buffer_rsrc_t rs, int w_off
       rows[r] = 2 * N + min(lane + WAVE * r, N - 1);
       acc[r] = ld_u32(bias, (unsigned)rows[r]);
     }
-    dotn_i<MK16, NK16, ROWS, NRC>(rs, w_off, u_off, rows, in_img, st_img, toff, sin, sst.dn, acc);
+    dotn_i<MK16, NK16, ROWS, NRC, rn_chains(NW)>(rs, w_off, u_off, rows, in_img, st_img, toff, sin, sst.dn, acc);
 #pragma unroll
     for (int r = 0; r < NRC; ++r) {
       const int i = lane + WAVE * r;
@@ -878,27 +877,58 @@ constexpr int U_G = 0, U_R = 24, U_VAD = 46, U_LY = 48;
 //   U [ 48, 192) digit image of the layer input (4 x 144 B; Ly before it), then the falling-half band partials
 constexpr int PL_FEAT = 800, PL_Z = 842, PL_DENSE = 938, PL_A_FREE = 800, PL_U_FREE = 48;
 
+// Value of lane `l - off` for the lanes l >= off of a wave prefix sum (the others get a lane they ignore).  ds_bpermute
+// takes the source lane from bits [7:2] of address + offset field, so the constant 4 * (64 - off) wraps to l - off and
+// rides in the instruction; __shfl_up spent four vector instructions per step on a clamped address.  lane4 = 4 * lane.
+__device__ __forceinline__ float lane_up(float v, int lane4, int off) {
+  return __int_as_float(__builtin_amdgcn_ds_bpermute(lane4 + 4 * (WAVE - off), __float_as_int(v)));
+}
+
 // top-2 bookkeeping of find_best_pitch as an ordering on (num, den, idx)
 struct Cand {
   float num, den;
   int idx;
 };
+// The three tests are taken unconditionally and combined as lane masks (`|`, `&`: no short circuit), so a caller that
+// selects on the result compiles to compares, scalar mask logic and v_cndmask -- as `||` / `&&` every use was two
+// divergent regions with phi copies.  Same products, same comparisons.
 __device__ __forceinline__ bool cand_better(const Cand& a, const Cand& b) {
   const float l = a.num * b.den, r = b.num * a.den;
-  return (l > r) || (!(r > l) && a.idx < b.idx);
+  const bool gt = l > r, ngt = !(r > l), lt = a.idx < b.idx;
+  return gt | (ngt & lt);
 }
-__device__ __forceinline__ Cand wave_best(Cand c) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    Cand o;
-    o.num = __shfl_xor(c.num, off, WAVE);
-    o.den = __shfl_xor(c.den, off, WAVE);
-    o.idx = __shfl_xor(c.idx, off, WAVE);
-    if (cand_better(o, c)) c = o;
+__device__ __forceinline__ Cand cand_pick(bool take_a, const Cand& a, const Cand& b) {
+  return Cand{take_a ? a.num : b.num, take_a ? a.den : b.den, take_a ? a.idx : b.idx};
+}
+// value of lane `l ^ OFF`, OFF < 32: ds_swizzle in bit-mask mode (and 0x1f, or 0, xor OFF) -- the pattern is in the
+// instruction, where __shfl_xor spent four vector instructions per value on a ds_bpermute address
+template <int OFF>
+__device__ __forceinline__ int lane_xor(int v) {
+  return __builtin_amdgcn_ds_swizzle(v, (OFF << 10) | 0x1f);
+}
+template <int OFF>
+__device__ __forceinline__ Cand cand_xor(const Cand& c) {
+  return Cand{__int_as_float(lane_xor<OFF>(__float_as_int(c.num))), __int_as_float(lane_xor<OFF>(__float_as_int(c.den))),
+              lane_xor<OFF>(c.idx)};
+}
+// Arg-max of the ordering over the wave: lane l meets lane l ^ off, off = 32, 16, 8, 4, 2, 1 (the ordering is not
+// transitive in floating point, so the tree is part of the result); lane 0's winner is returned as scalars.
+// half_addr: 4 * (lane ^ 32), the ds_bpermute address of the one step that crosses the 32-lane halves.
+__device__ __forceinline__ Cand wave_best(Cand c, int half_addr) {
+  {
+    const Cand o = {__int_as_float(__builtin_amdgcn_ds_bpermute(half_addr, __float_as_int(c.num))),
+                    __int_as_float(__builtin_amdgcn_ds_bpermute(half_addr, __float_as_int(c.den))),
+                    __builtin_amdgcn_ds_bpermute(half_addr, c.idx)};
+    c = cand_pick(cand_better(o, c), o, c);
   }
-  c.num = __shfl(c.num, 0, WAVE);
-  c.den = __shfl(c.den, 0, WAVE);
-  c.idx = __shfl(c.idx, 0, WAVE);
+  { const Cand o = cand_xor<16>(c); c = cand_pick(cand_better(o, c), o, c); }
+  { const Cand o = cand_xor<8>(c); c = cand_pick(cand_better(o, c), o, c); }
+  { const Cand o = cand_xor<4>(c); c = cand_pick(cand_better(o, c), o, c); }
+  { const Cand o = cand_xor<2>(c); c = cand_pick(cand_better(o, c), o, c); }
+  { const Cand o = cand_xor<1>(c); c = cand_pick(cand_better(o, c), o, c); }
+  c.num = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.num), 0));
+  c.den = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.den), 0));
+  c.idx = __builtin_amdgcn_readlane(c.idx, 0);
   return c;
 }
 
@@ -1239,9 +1269,10 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
             run = fmaf(v, v, run);
           }
           float incl = run;
+          const int up_addr = lane << 2;
   #pragma unroll
           for (int off = 1; off < WAVE; off <<= 1) {
-            const float o = __shfl_up(incl, off, WAVE);
+            const float o = lane_up(incl, up_addr, off);
             if (lane >= off) incl += o;
           }
           const float excl = incl - run;
@@ -1256,29 +1287,30 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
         int nvalid = 0;
   #pragma unroll
         for (int rr = 0; rr < 3; ++rr) {
-          const int lag = 3 * lane + rr;
-          if (lag < 147 && xc[rr] > 0.f) {
-            const float syy = fmaxf(1.f, 1.f + (pre[lag + 240] - pre[lag]));
-            const float x16 = xc[rr] * 1e-12f;
-            const Cand c = {x16 * x16, syy, lag};
-            ++nvalid;
-            if (cand_better(c, c0)) { c1 = c0; c0 = c; }
-            else if (cand_better(c, c1)) c1 = c;
-          }
+          // Every lane forms its candidate (lanes past 48 from lane 48's prefix sums: in range, never valid) and the
+          // insertion is selects under `valid`: as `if` / `else if` it was three divergent regions per lag.
+          const int lag = 3 * lane + rr, lagc = 3 * min(lane, 48) + rr;
+          const bool valid = lag < 147 && xc[rr] > 0.f;
+          const float syy = fmaxf(1.f, 1.f + (pre[lagc + 240] - pre[lagc]));
+          const float x16 = xc[rr] * 1e-12f;
+          const Cand c = {x16 * x16, syy, lag};
+          nvalid += valid ? 1 : 0;
+          const bool b0 = valid & cand_better(c, c0), b1 = valid & cand_better(c, c1);
+          c1 = cand_pick(b0, c0, cand_pick(b1, c, c1));
+          c0 = cand_pick(b0, c, c0);
         }
         const int total_valid = __popcll(__ballot(nvalid > 0)) == 0 ? 0 : (int)wave_sum((float)nvalid);
-        const Cand w0 = wave_best(c0);
+        const int half_addr = (lane ^ 32) << 2;
+        const Cand w0 = wave_best(c0, half_addr);
         const Cand mine = (c0.idx == w0.idx) ? c1 : c0;   // the winner's lane offers its runner-up
-        const Cand w1 = wave_best(mine);
+        const Cand w1 = wave_best(mine, half_addr);
         if (total_valid == 0) { best0 = 0; best1 = 1; }
         else if (total_valid == 1) { best0 = w0.idx; best1 = 0; }
         else { best0 = w0.idx; best1 = w1.idx; }
       }
-      // wave_best hands every lane the same winners, but through ds_bpermute: as vector values the ten fine lags, their
-      // range tests and later T0 and the candidate lags of remove_doubling were computed in every lane.  From here the
-      // lag arithmetic runs on the scalar unit; per lag only `lane + scalar offset` is left.
-      best0 = __builtin_amdgcn_readfirstlane(best0);
-      best1 = __builtin_amdgcn_readfirstlane(best1);
+      // wave_best returns lane 0's winners with v_readlane, so best0 and best1 are scalars already and the lag arithmetic from
+      // here on -- the ten fine lags, their range tests, later T0 and the candidate lags of remove_doubling -- runs on the
+      // scalar unit; per lag only `lane + scalar offset` is left.
       rn_sync<NW>();
       STAMP(2)
 
@@ -1368,9 +1400,10 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
             loc[q] = run;
           }
           float incl = run;
+          const int up_addr = lane << 2;
   #pragma unroll
           for (int off = 1; off < WAVE; off <<= 1) {
-            const float o = __shfl_up(incl, off, WAVE);
+            const float o = lane_up(incl, up_addr, off);
             if (lane >= off) incl += o;
           }
           const float excl = incl - run;
@@ -1651,7 +1684,7 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
         rn_sync<NW>();
         {
           const int row = min(lane, 23);
-          const float acc = dot_i<rn_k16(42), 24>(wrs, RnPack8::ID_W, row, in_img, toff, sc.dn, wpf[RnPack::ID_B + row]);
+          const float acc = dot_i<rn_k16(42), 24, rn_chains(NW)>(wrs, RnPack8::ID_W, row, in_img, toff, sc.dn, wpf[RnPack::ID_B + row]);
           const float d = tansig_approx(S * acc, tansig);
           if (lane < 24) dense[lane] = d;
         }
@@ -1684,7 +1717,7 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
         rn_sync<NW>();
         {
           const int row = min(lane, RN_NB - 1);
-          const float acc = dot_i<rn_k16(96), RN_NB>(wrs, RnPack8::DO_W, row, st_img, toff, sc.dn, wpf[RnPack::DO_B + row]);
+          const float acc = dot_i<rn_k16(96), RN_NB, rn_chains(NW)>(wrs, RnPack8::DO_W, row, st_img, toff, sc.dn, wpf[RnPack::DO_B + row]);
           const float gv = sigmoid_approx(S * acc, tansig);
           if (lane < RN_NB) SL.U[U_G + lane] = gv;
         }
