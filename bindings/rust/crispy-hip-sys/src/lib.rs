@@ -28,6 +28,7 @@ pub const CRISPY_ERR_OOM: c_int = -4;
 pub const CRISPY_ERR_BAD_MODEL: c_int = -5;
 pub const CRISPY_ERR_UNSUPPORTED: c_int = -6;
 pub const CRISPY_ERR_CANCELLED: c_int = -7;
+pub const CRISPY_ERR_INTERNAL: c_int = -8;
 /// Longest clip of one transcribe call: 2 h at 16 kHz (`CRISPY_ASR_MAX_SAMPLES`).
 pub const CRISPY_ASR_MAX_SAMPLES: usize = 115_200_000;
 
@@ -179,6 +180,16 @@ pub struct crispy_asr_result {
 }
 
 /// One word of a result (`dtw_token_timestamps`): seconds from the start of the chunk, index of its first token.
+/// `crispy_diar_info`: what `crispy_diar_cluster*` decided for one recording (`info` is `crispy_diar_info[batch]`).
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
+pub struct crispy_diar_info {
+    pub p_star: c_int,
+    pub k: c_int,
+    pub ratio: c_float,
+    pub gap: c_float,
+    pub p_max: c_int,
+}
 #[repr(C)]
 #[derive(Debug, Clone, Copy)]
 pub struct crispy_asr_word {
@@ -303,6 +314,19 @@ extern "C" {
     pub fn crispy_resampler_out_len(n_in: c_long) -> c_long;
     pub fn crispy_resampler_process_device(h: *mut crispy_resampler, d_in: *const c_float, in_stride: c_long, n_in: c_long, batch: c_int, scale: c_float, wav_s16: c_int, d_out: *mut c_float, out_stride: c_long, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_resampler_synchronize(h: *mut crispy_resampler) -> c_int;
+    // speaker clustering and diarized text (managers/diarization.rs:276-724); the handle is a `void *`
+    pub fn crispy_diar_create(device: c_int, out: *mut *mut c_void) -> c_int;
+    pub fn crispy_diar_destroy(h: *mut c_void);
+    pub fn crispy_diar_cluster(h: *mut c_void, emb: *const c_float, n: *const c_int, batch: c_int, dim: c_int, max_speakers: c_int, labels: *mut c_int, info: *mut c_void) -> c_int;
+    pub fn crispy_diar_cluster_device(h: *mut c_void, d_emb: *const c_float, n: *const c_int, batch: c_int, dim: c_int, max_speakers: c_int, d_labels: *mut c_int, info: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_diar_affinity_device(h: *mut c_void, d_emb: *const c_float, n: c_int, dim: c_int, d_aff: *mut c_float) -> c_int;
+    pub fn crispy_diar_laplacian_device(h: *mut c_void, d_aff: *const c_float, n: c_int, p: c_int, d_lap: *mut c_float) -> c_int;
+    pub fn crispy_diar_eigh_device(h: *mut c_void, d_mats: *const c_float, n: c_int, n_mats: c_int, d_evals: *mut c_float, d_evecs: *mut c_float) -> c_int;
+    pub fn crispy_diar_chunk_plan(start: *const f64, end: *const f64, n_samples: *const c_long, n_segments: c_long, sample_rate: c_int, out_start: *mut f64, out_end: *mut f64, out_segment: *mut c_long, out_first: *mut c_long, out_len: *mut c_long, cap: c_long) -> c_long;
+    pub fn crispy_diar_speaker_segments(start: *const f64, end: *const f64, labels: *const c_int, n: c_long, merge_gap: f64, out_start: *mut f64, out_end: *mut f64, out_speaker: *mut c_int, cap: c_long) -> c_long;
+    pub fn crispy_diar_find_speaker(time: f64, seg_start: *const f64, seg_end: *const f64, seg_speaker: *const c_int, n_segments: c_long) -> c_int;
+    pub fn crispy_diar_format_text(t0: *const f64, t1: *const f64, text: *const *const c_char, n_words: c_long, seg_start: *const f64, seg_end: *const f64, seg_speaker: *const c_int, n_segments: c_long, out: *mut c_char, cap: usize, needed: *mut usize) -> c_int;
+    pub fn crispy_diar_format_result(r: *const crispy_asr_result, chunk_offset: f64, seg_start: *const f64, seg_end: *const f64, seg_speaker: *const c_int, n_segments: c_long, out: *mut c_char, cap: usize, needed: *mut usize) -> c_int;
 }
 
 // ------------------------------------------------------------------------------------------------------------

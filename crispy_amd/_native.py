@@ -62,7 +62,18 @@ ASR_SYMBOLS = ("crispy_asr_create", "crispy_asr_set_tensor", "crispy_asr_finaliz
                "crispy_asr_set_audio_ctx", "crispy_asr_audio_ctx")
 RS_SYMBOLS = ("crispy_resampler_create", "crispy_resampler_destroy", "crispy_resampler_out_len",
               "crispy_resampler_process_device", "crispy_resampler_synchronize")
-ALL_SYMBOLS = RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS
+DIAR_SYMBOLS = ("crispy_diar_create", "crispy_diar_destroy", "crispy_diar_cluster", "crispy_diar_cluster_device",
+                "crispy_diar_affinity_device", "crispy_diar_laplacian_device", "crispy_diar_eigh_device",
+                "crispy_diar_chunk_plan", "crispy_diar_speaker_segments", "crispy_diar_find_speaker",
+                "crispy_diar_format_text", "crispy_diar_format_result")
+ALL_SYMBOLS = RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS + DIAR_SYMBOLS
+DIAR_MAX_N, DIAR_MAX_DIM, DIAR_MAX_BATCH, DIAR_LDS_N = 2048, 1024, 64, 192
+
+
+class DiarInfo(C.Structure):
+    """crispy_diar_info"""
+    _fields_ = [("p_star", C.c_int), ("k", C.c_int), ("ratio", C.c_float), ("gap", C.c_float), ("p_max", C.c_int)]
+
 
 class AsrSpecials(C.Structure):
     """crispy_asr_specials"""
@@ -107,6 +118,7 @@ class AsrResult(C.Structure):
 
 
 ERR_CANCELLED = -7
+ERR_INTERNAL = -8
 # crispy_asr_progress_fn: void (*)(size_t samples_done, size_t samples_total, void *user)
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_size_t, C.c_size_t, C.c_void_p)
 
@@ -286,6 +298,23 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_resampler_process_device.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_float,
                                                   C.c_int, C.c_void_p, C.c_long, C.c_void_p]
     L.crispy_resampler_synchronize.argtypes = [C.c_void_p]
+    f64p, i32p, szp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_size_t)
+    L.crispy_diar_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.crispy_diar_destroy.argtypes = [C.c_void_p]
+    L.crispy_diar_destroy.restype = None
+    L.crispy_diar_cluster.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.crispy_diar_cluster_device.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.crispy_diar_affinity_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.crispy_diar_laplacian_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.crispy_diar_eigh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.crispy_diar_chunk_plan.argtypes = [f64p, f64p, lp, C.c_long, C.c_int, f64p, f64p, lp, lp, lp, C.c_long]
+    L.crispy_diar_chunk_plan.restype = C.c_long
+    L.crispy_diar_speaker_segments.argtypes = [f64p, f64p, i32p, C.c_long, C.c_double, f64p, f64p, i32p, C.c_long]
+    L.crispy_diar_speaker_segments.restype = C.c_long
+    L.crispy_diar_find_speaker.argtypes = [C.c_double, f64p, f64p, i32p, C.c_long]
+    L.crispy_diar_format_text.argtypes = [f64p, f64p, C.POINTER(C.c_char_p), C.c_long, f64p, f64p, i32p, C.c_long,
+                                          C.c_char_p, C.c_size_t, szp]
+    L.crispy_diar_format_result.argtypes = [C.c_void_p, C.c_double, f64p, f64p, i32p, C.c_long, C.c_char_p, C.c_size_t, szp]
     return L
 
 

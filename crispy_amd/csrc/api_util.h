@@ -3,6 +3,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdlib>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -22,6 +23,11 @@ bool device_is_gfx950(int dev);
 // (std::bad_alloc / std::length_error -> CRISPY_ERR_OOM, anything else -> CRISPY_ERR_HIP), records a message and
 // returns the status.  Never throws (the message buffer is a fixed thread-local array).
 int fail_exception(const char* where) noexcept;
+
+// Rust's str::trim(): Unicode White_Space off both ends of a UTF-8 string (the chunk texts of a recording, the words and
+// the result of the diarized text).
+bool unicode_space(unsigned cp);
+std::string trim_unicode(const std::string& s);
 
 // Environment variables the library reads -- two kinds, nothing else calls getenv:
 //  * test hooks (test_env): read in every build and listed under "Environment" in include/crispy_hip.h.  They select

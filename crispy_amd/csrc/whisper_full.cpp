@@ -1026,42 +1026,6 @@ int transcribe_batch_impl(crispy_asr* h, const float* const* pcm, const size_t* 
   return CRISPY_OK;
 }
 
-// Rust's str::trim(): the code points with the White_Space property, off both ends of a UTF-8 string
-// (managers/transcription.rs:187 trims every chunk's text; commands/transcription.rs:276 tests `trim().is_empty()`)
-bool unicode_space(unsigned cp) {
-  return (cp >= 9 && cp <= 13) || cp == 0x20 || cp == 0x85 || cp == 0xA0 || cp == 0x1680 || (cp >= 0x2000 && cp <= 0x200A) ||
-         cp == 0x2028 || cp == 0x2029 || cp == 0x202F || cp == 0x205F || cp == 0x3000;
-}
-std::string trim_unicode(const std::string& s) {
-  auto decode = [&](size_t i, size_t* len) -> unsigned {      // one code point at byte i (malformed bytes stand for themselves)
-    const unsigned char c = (unsigned char)s[i];
-    auto cont = [&](size_t k) { return i + k < s.size() && ((unsigned char)s[i + k] & 0xC0) == 0x80; };
-    if (c < 0x80) { *len = 1; return c; }
-    if ((c & 0xE0) == 0xC0 && cont(1)) { *len = 2; return ((c & 0x1Fu) << 6) | ((unsigned char)s[i + 1] & 0x3Fu); }
-    if ((c & 0xF0) == 0xE0 && cont(1) && cont(2)) {
-      *len = 3;
-      return ((c & 0x0Fu) << 12) | (((unsigned char)s[i + 1] & 0x3Fu) << 6) | ((unsigned char)s[i + 2] & 0x3Fu);
-    }
-    *len = 1;
-    return 0xFFFFFFFFu;
-  };
-  size_t a = 0, b = s.size();
-  while (a < b) {
-    size_t len = 1;
-    if (!unicode_space(decode(a, &len))) break;
-    a += len;
-  }
-  while (b > a) {
-    size_t k = b - 1;
-    while (k > a && ((unsigned char)s[k] & 0xC0) == 0x80 && b - k < 3) --k;      // back to the lead byte of the last code point
-    size_t len = 1;
-    const unsigned cp = decode(k, &len);
-    if (k + len != b || !unicode_space(cp)) break;
-    b = k;
-  }
-  return s.substr(a, b - a);
-}
-
 }  // namespace
 }  // namespace asr
 }  // namespace crispy

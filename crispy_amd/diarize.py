@@ -1,0 +1,161 @@
+"""Speaker clustering and diarized text over the C ABI (crispy_diar_*, include/crispy_hip.h): the reference's `nme_sc`, the
+tail of `run_diarization` and `format_diarized_text` (src-tauri/src/managers/diarization.rs:276-724).  Embeddings are the
+caller's; there is no CPU path for the clustering.  The host functions (`chunk_plan`, `speaker_segments`, `find_speaker`,
+`format_diarized_text`) need no device."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _native as N
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _p(a, ty):
+    return a.ctypes.data_as(C.POINTER(ty)) if a.size else None
+
+
+class Diarizer:
+    """A crispy_diar handle: its own stream and a scratch that grows on demand."""
+
+    def __init__(self, device: int = 0, lib=None):
+        self._L = lib or N.lib()
+        self._h = C.c_void_p()
+        N.check(self._L.crispy_diar_create(int(device), C.byref(self._h)), self._L)
+
+    def close(self):
+        if self._h:
+            self._L.crispy_diar_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def cluster(self, recordings, max_speakers: int):
+        """nme_sc for a list of [n_i, dim] f32 arrays in one call -> (list of int32 label arrays, list of info dicts)."""
+        recs = [np.ascontiguousarray(r, dtype=np.float32) for r in recordings]
+        dim = recs[0].shape[1]
+        n = np.array([r.shape[0] for r in recs], np.int32)
+        emb = np.ascontiguousarray(np.concatenate([r.reshape(-1, dim) for r in recs], 0))
+        labels = np.zeros(int(n.sum()), np.int32)
+        info = (N.DiarInfo * len(recs))()
+        N.check(self._L.crispy_diar_cluster(self._h, emb.ctypes.data, _p(n, C.c_int), len(recs), dim, int(max_speakers),
+                                            labels.ctypes.data, C.cast(info, C.c_void_p)), self._L)
+        off = np.concatenate([[0], np.cumsum(n)])
+        return ([labels[off[i]:off[i + 1]].copy() for i in range(len(recs))],
+                [dict(p_star=x.p_star, k=x.k, ratio=x.ratio, gap=x.gap, p_max=x.p_max) for x in info])
+
+    def cluster_device(self, emb, n, max_speakers: int, stream=None):
+        """The same on a CUDA f32 tensor [sum n, dim] -> (int32 CUDA tensor [sum n], DiarInfo array)."""
+        import torch
+        n = np.ascontiguousarray(n, dtype=np.int32)
+        labels = torch.zeros(int(n.sum()), dtype=torch.int32, device=emb.device)
+        info = (N.DiarInfo * len(n))()
+        N.check(self._L.crispy_diar_cluster_device(self._h, emb.data_ptr(), _p(n, C.c_int), len(n), emb.shape[1], int(max_speakers),
+                                                   labels.data_ptr(), C.cast(info, C.c_void_p), stream), self._L)
+        return labels, info
+
+    def affinity(self, emb):
+        import torch
+        out = torch.empty((emb.shape[0], emb.shape[0]), dtype=torch.float32, device=emb.device)
+        N.check(self._L.crispy_diar_affinity_device(self._h, emb.data_ptr(), emb.shape[0], emb.shape[1], out.data_ptr()), self._L)
+        return out
+
+    def laplacian(self, aff, p: int):
+        import torch
+        out = torch.empty_like(aff)
+        N.check(self._L.crispy_diar_laplacian_device(self._h, aff.data_ptr(), aff.shape[0], int(p), out.data_ptr()), self._L)
+        return out
+
+    def eigh(self, mats, vectors: bool = True):
+        """mats: CUDA f32 [n_mats, n, n] symmetric -> (evals [n_mats, n] ascending, evecs [n_mats, n, n] or None)."""
+        import torch
+        m, n = mats.shape[0], mats.shape[1]
+        ev = torch.empty((m, n), dtype=torch.float32, device=mats.device)
+        vec = torch.empty((m, n, n), dtype=torch.float32, device=mats.device) if vectors else None
+        N.check(self._L.crispy_diar_eigh_device(self._h, mats.data_ptr(), n, m, ev.data_ptr(), vec.data_ptr() if vectors else None), self._L)
+        return ev, vec
+
+
+def nme_sc(embeddings, max_speakers: int, device: int = 0) -> np.ndarray:
+    """`nme_sc(&embeddings, max_speakers)` (diarization.rs:541): raw labels of one recording's [n, dim] embeddings."""
+    d = Diarizer(device)
+    try:
+        return d.cluster([embeddings], max_speakers)[0][0]
+    finally:
+        d.close()
+
+
+def chunk_plan(segments, sample_rate: int = 16000):
+    """The ~4 s split of run_diarization (:311-338).  segments: (start, end, n_samples) triples ->
+    list of (start, end, segment index, first sample, n samples)."""
+    L = N.lib()
+    s, e = _f64([x[0] for x in segments]), _f64([x[1] for x in segments])
+    ns = np.ascontiguousarray([x[2] for x in segments], dtype=np.int64)
+    args = (_p(s, C.c_double), _p(e, C.c_double), _p(ns, C.c_long), len(segments), int(sample_rate))
+    cnt = L.crispy_diar_chunk_plan(*args, None, None, None, None, None, 0)
+    if cnt < 0:
+        N.check(int(cnt), L)
+    os_, oe = np.zeros(cnt), np.zeros(cnt)
+    og, of, ol = (np.zeros(cnt, np.int64) for _ in range(3))
+    if cnt:
+        L.crispy_diar_chunk_plan(*args, _p(os_, C.c_double), _p(oe, C.c_double), _p(og, C.c_long), _p(of, C.c_long), _p(ol, C.c_long), cnt)
+    return [(float(os_[i]), float(oe[i]), int(og[i]), int(of[i]), int(ol[i])) for i in range(cnt)]
+
+
+def speaker_segments(starts, ends, labels, merge_gap: float):
+    """run_diarization's tail (:373-400): chunk times and raw labels -> merged [(start, end, speaker number >= 1)]."""
+    L = N.lib()
+    s, e, lb = _f64(starts), _f64(ends), np.ascontiguousarray(labels, dtype=np.int32)
+    n = len(s)
+    os_, oe, ow = np.zeros(n), np.zeros(n), np.zeros(n, np.int32)
+    cnt = L.crispy_diar_speaker_segments(_p(s, C.c_double), _p(e, C.c_double), _p(lb, C.c_int), n, float(merge_gap),
+                                         _p(os_, C.c_double), _p(oe, C.c_double), _p(ow, C.c_int), n)
+    if cnt < 0:
+        N.check(int(cnt), L)
+    return [(float(os_[i]), float(oe[i]), int(ow[i])) for i in range(cnt)]
+
+
+def _segs(segments):
+    s, e = _f64([x[0] for x in segments]), _f64([x[1] for x in segments])
+    w = np.ascontiguousarray([x[2] for x in segments], dtype=np.int32)
+    return s, e, w, (_p(s, C.c_double), _p(e, C.c_double), _p(w, C.c_int), len(segments))
+
+
+def speaker_name(s: int) -> str:
+    return "Speaker ?" if s == 0 else f"Speaker {s}"
+
+
+def find_speaker(time: float, segments) -> int:
+    """find_speaker_at_time (:703-724); 0 stands for "Speaker ?"."""
+    *_keep, args = _segs(segments)
+    return int(N.lib().crispy_diar_find_speaker(float(time), *args))
+
+
+def _text(call):
+    L = N.lib()
+    need = C.c_size_t(0)
+    N.check(call(None, 0, C.byref(need)), L)
+    buf = C.create_string_buffer(need.value)
+    N.check(call(buf, need.value, C.byref(need)), L)
+    return buf.value.decode("utf-8")
+
+
+def format_diarized_text(words, segments) -> str:
+    """format_diarized_text (:657-700).  words: (t0, t1, text) triples; segments: (start, end, speaker number)."""
+    t0, t1 = _f64([w[0] for w in words]), _f64([w[1] for w in words])
+    texts = (C.c_char_p * max(len(words), 1))(*[w[2].encode("utf-8") for w in words])
+    *_keep, sa = _segs(segments)
+    L = N.lib()
+    return _text(lambda out, cap, need: L.crispy_diar_format_text(_p(t0, C.c_double), _p(t1, C.c_double), texts, len(words), *sa,
+                                                                  out, cap, need))
+
+
+def format_result(result_ptr, chunk_offset: float, segments) -> str:
+    """The same over the words of a `crispy_asr_result *` (a transcribe call with dtw_token_timestamps)."""
+    *_keep, sa = _segs(segments)
+    L = N.lib()
+    return _text(lambda out, cap, need: L.crispy_diar_format_result(result_ptr, float(chunk_offset), *sa, out, cap, need))

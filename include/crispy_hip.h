@@ -55,7 +55,8 @@ typedef enum crispy_status {
   CRISPY_ERR_OOM = -4,
   CRISPY_ERR_BAD_MODEL = -5,
   CRISPY_ERR_UNSUPPORTED = -6,
-  CRISPY_ERR_CANCELLED = -7 /* crispy_asr_transcribe_recording / _hooks: the caller's cancel flag was set; no result */
+  CRISPY_ERR_CANCELLED = -7, /* crispy_asr_transcribe_recording / _hooks: the caller's cancel flag was set; no result */
+  CRISPY_ERR_INTERNAL = -8   /* crispy_diar_*: the eigensolver did not converge within its sweep cap; no result */
 } crispy_status;
 
 #define CRISPY_RN_FRAME_SIZE 480      /* nnnoiseless::FRAME_SIZE (audio.rs:4) */
@@ -974,6 +975,103 @@ int crispy_resampler_process_device(crispy_resampler *h, const float *d_in, long
                                     int batch, float scale, int wav_s16, float *d_out,
                                     long out_stride, void *hip_stream);
 int crispy_resampler_synchronize(crispy_resampler *h);
+
+/* ------------------------------------------------------------------------------------------
+ * Speaker clustering and diarized text: src-tauri/src/managers/diarization.rs:276-724 from "embeddings + chunk times"
+ * on -- nme_sc (cosine_similarity, pruned_normalized_laplacian, max_eigengap, kmeans), the relabel / sort / merge tail of
+ * run_diarization, find_speaker_at_time and format_diarized_text.  No neural network: the segmentation and embedding
+ * models stay with the host, which hands over one embedding row per speech chunk.
+ *
+ * The handle is a `void *` (as crispy_asr_result::words is): the set of opaque types every binding mirrors is closed.
+ * It owns a stream and a scratch that grows on demand and is kept; it is not re-entrant.
+ *
+ * Device work of crispy_diar_cluster for a recording of n > 2 chunks (p_max = min(n-1, 2*max(floor(sqrt(n)), 2)),
+ * kmax = min(max(max_speakers, 1), n-1)):
+ *   affinity     f32, each pair's dot / norms summed in index order over dim without fused multiply-adds, correctly
+ *                rounded division and square root: bit for bit cosine_similarity.
+ *   ranking      rank[i][j] = neighbours of row i that a stable descending sort puts before j (ties: lower index
+ *                first), once per recording; "j is among the p largest of row i or i among those of row j" is then
+ *                min(rank[i][j], rank[j][i]) < p for every p of the sweep.
+ *   Laplacians   all p = 1 ... p_max side by side, bit for bit pruned_normalized_laplacian.
+ *   eigenvalues  cyclic Jacobi in the round-robin ordering (floor(n/2) disjoint rotations per step, every 2x2 block of a
+ *                step updated independently), all Laplacians of all recordings of a call side by side, in one of two
+ *                forms chosen by n alone:  n <= 192: one workgroup per matrix, the matrix in LDS (147 KB of the 160);
+ *                193 ... 2048: the matrix in global memory, one launch pair per rotation set for all matrices.
+ *                The off-diagonal norm is tested before every sweep; once it is <= n * 2^-24 * the diagonal's norm the
+ *                matrix gets one last sweep (the convergence is quadratic: that sweep leaves rounding only) and is
+ *                done.  40 sweeps without passing the test fail the call with CRISPY_ERR_INTERNAL.  Rotations are
+ *                worked out in double and applied in f32.  A matrix's result does not depend on what else is in
+ *                the launch.
+ *   decision     max_eigengap over the kmax + 1 smallest eigenvalues (first maximum), ratio = (p/n) / max(gap, 1e-6)
+ *                in f32, the first smallest ratio gives p* and k; k <= 1: all labels 0 and no second solve.
+ *   vectors      one more solve at p* with the rotations accumulated, the k vectors of the smallest eigenvalues,
+ *                rows normalised when their norm is > 1e-9.
+ *   k-means      one workgroup per recording: farthest-point seeding from point 0, at most 50 Lloyd iterations, sums in
+ *                point order, strict comparisons, empty clusters keep their centre.
+ * Scratch: recordings are taken in turns whose device scratch stays below 2 GB; per recording n*n*(4+2+2) bytes for the
+ * affinity and the rankings plus 4*n*n per Laplacian of the sweep (n = 2048: 91 Laplacians, 1.6 GB; n = 300: 13 MB).
+ *
+ * Limits: 0 <= n[i] <= 2048, 1 <= dim <= 1024, 1 <= batch <= 64; max_speakers < 1 counts as 1 (:292, :550);
+ * n[i] <= 2 gives zeros (:367, :547).  A non-finite embedding value is CRISPY_ERR_INVALID_ARG (the reference's
+ * partial_cmp(..).unwrap_or(Equal) leaves the order of NaNs unspecified).  Limits are checked before any launch.
+ * A recording's labels and info are the same bytes alone and in any batch.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct crispy_diar_info {
+  int p_star;   /* the pruning parameter that minimised the ratio (0 for n <= 2) */
+  int k;        /* speakers: clamp(eigengap position, 1, kmax) (1 for n <= 2, 0 for n == 0) */
+  float ratio;  /* (p_star / n) / max(gap, 1e-6) */
+  float gap;    /* the largest eigengap at p_star */
+  int p_max;    /* p ran over 1 ... p_max (0 for n <= 2) */
+} crispy_diar_info;
+
+int crispy_diar_create(int device, void **out);
+void crispy_diar_destroy(void *h);
+/* nme_sc for `batch` recordings.  emb: host f32, the recordings' rows concatenated [sum n][dim]; n: host [batch];
+ * labels: host [sum n], the raw nme_sc labels (not yet in order of appearance: crispy_diar_speaker_segments does that);
+ * info: nullable, crispy_diar_info[batch].  Returns when the labels are there. */
+int crispy_diar_cluster(void *h, const float *emb, const int *n, int batch, int dim, int max_speakers, int *labels, void *info);
+/* The same with d_emb and d_labels on the device (n and info stay host arrays); the work is enqueued on hip_stream
+ * (NULL = the handle's own) and the call returns after it is complete -- the solver reads its convergence flags back. */
+int crispy_diar_cluster_device(void *h, const float *d_emb, const int *n, int batch, int dim, int max_speakers, int *d_labels,
+                               void *info, void *hip_stream);
+/* Stage entry points, for tests and profiling; device pointers, the handle's stream, complete on return.
+ *   affinity   d_emb [n][dim] -> d_aff [n][n] (zero diagonal); 1 <= n <= 2048, 1 <= dim <= 1024
+ *   laplacian  d_aff [n][n] (symmetric, as affinity writes it) and p >= 1 -> d_lap [n][n]
+ *   eigh       n_mats symmetric f32 matrices d_mats [n_mats][n][n] (left as they are) -> d_evals [n_mats][n] ascending and,
+ *              unless d_evecs is NULL, d_evecs [n_mats][n][n]: column c of a matrix belongs to its eigenvalue c.
+ *              1 <= n <= 2048, n_mats >= 1, n_mats * n * n * 4 bytes (x 2 with vectors) <= 2 GB */
+int crispy_diar_affinity_device(void *h, const float *d_emb, int n, int dim, float *d_aff);
+int crispy_diar_laplacian_device(void *h, const float *d_aff, int n, int p, float *d_lap);
+int crispy_diar_eigh_device(void *h, const float *d_mats, int n, int n_mats, float *d_evals, float *d_evecs);
+
+/* Host functions: no device, no handle.  Speakers are numbers: s >= 1 is "Speaker s", 0 is "Speaker ?".
+ *   crispy_diar_chunk_plan: run_diarization's split of speech segments into ~4 s chunks (:311-338).  Segment i spans
+ *     start[i] ... end[i] seconds and holds n_samples[i] samples; a segment longer than 4 s becomes ceil(dur / 4) chunks of
+ *     n_samples / chunks samples (the last takes the rest).  Chunk c is out_start / out_end[c] seconds and the samples
+ *     out_first[c] ... out_first[c] + out_len[c] of its segment out_segment[c].  Returns the number of chunks; entries
+ *     beyond `cap` are not written (call with cap 0 to size).  Non-finite times or sample_rate <= 0: INVALID_ARG.
+ *   crispy_diar_speaker_segments: :373-400 -- labels renumbered in order of first appearance (the first to speak is
+ *     Speaker 1), a stable sort by start, then merge_consecutive_segments: same speaker and max(start - last.end, 0) <=
+ *     merge_gap extends the last segment to max(end, last.end).  Returns the number of merged segments (cap as above).
+ *   crispy_diar_find_speaker: find_speaker_at_time (:703-724) -- the first segment with start <= time <= end, else the
+ *     segment at the smallest distance (first of equals), 0 for an empty list; a negative status for NULL segments.
+ *   crispy_diar_format_text: format_diarized_text (:657-700), byte for byte.  Words (t0, t1, text) whose text is blank
+ *     after Rust's trim are skipped; a word belongs to the speaker at (t0 + t1) / 2; a change of speaker starts
+ *     "\n[Speaker s|t0]" with t0 as Rust's {:.1} (the exact decimal value, half to even), the lines are joined with "\n"
+ *     and the whole is trimmed.  Without segments or without words: the texts, untrimmed, joined with one space.
+ *     Writes at most cap bytes including the NUL; *needed (nullable) = the bytes the full text takes with its NUL;
+ *     a result that does not fit is CRISPY_ERR_INVALID_ARG with *needed set (call with out NULL / cap 0 to size).
+ *   crispy_diar_format_result: the same over the words of a crispy_asr_result (opts.dtw_token_timestamps), their
+ *     times as f64 plus chunk_offset seconds: from crispy_asr_transcribe to diarized text in two calls. */
+long crispy_diar_chunk_plan(const double *start, const double *end, const long *n_samples, long n_segments, int sample_rate,
+                            double *out_start, double *out_end, long *out_segment, long *out_first, long *out_len, long cap);
+long crispy_diar_speaker_segments(const double *start, const double *end, const int *labels, long n, double merge_gap,
+                                  double *out_start, double *out_end, int *out_speaker, long cap);
+int crispy_diar_find_speaker(double time, const double *seg_start, const double *seg_end, const int *seg_speaker, long n_segments);
+int crispy_diar_format_text(const double *t0, const double *t1, const char *const *text, long n_words, const double *seg_start,
+                            const double *seg_end, const int *seg_speaker, long n_segments, char *out, size_t cap, size_t *needed);
+int crispy_diar_format_result(const crispy_asr_result *r, double chunk_offset, const double *seg_start, const double *seg_end,
+                              const int *seg_speaker, long n_segments, char *out, size_t cap, size_t *needed);
 
 #ifdef __cplusplus
 }
