@@ -31,6 +31,10 @@ constexpr int kChunkFrames = 250;   // workspace bound: frames of high-passed si
 // ahead on the helper stream.  Measured per 100-frame step with the final kernels (4096 streams): 8 -> 8.2 ms,
 // 10 -> 8.0, 12 -> 7.68, 16 -> 7.75, 20 -> 7.85, 30 -> 8.03; a longer ramp (3, 8, 20, 48) with 48-frame sub-chunks
 // shortens the frame-kernel sum by 1.5 % (five launch tails instead of ten) but waits 0.8 ms for the high-pass.
+// With the rotating wave priorities (rn_prio.h: waves idle for 8.8 % of a 12-frame launch instead of 15.8 %) the sweep was
+// run again with ramps that grow <= 1.5x per step: 12 -> 5.11 - 5.22 ms per step (ramp 3, 4, 5, 7, 10) and 5.13 - 5.15
+// (3, 4, 6, 9), 16 -> 5.10 - 5.13, 20 -> 5.11 - 5.18, 24 -> 5.10 - 5.15: inside the spread of 12 itself, so 12 stays
+// (NOTEBOOK section 26).
 #ifndef RN_SUB_FRAMES
 #define RN_SUB_FRAMES 12
 #endif

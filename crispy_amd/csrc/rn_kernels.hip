@@ -19,6 +19,7 @@
 // windows of the same high-passed signal, so neither is stored as state: they are views of xhp.
 #include <type_traits>
 #include "rn_common.h"
+#include "rn_prio.h"
 #include "rn_scale.h"
 #include "rn_wave_sums.h"
 
@@ -31,16 +32,35 @@ constexpr int WAVE = 64;
 #ifdef RN_PROFILE
 // Stage stamps accumulate straight into the debug buffer (one lane, global read-modify-write): 24 counters in
 // registers pushed the frame loop into scratch, which this compiler does not handle safely (see dotn_h).
+// Counters 14 .. 19 (tools/launch_tail.py) are bit patterns, written once per launch by lane 0: the constant-rate clock
+// (s_memrealtime, 100 MHz, low 32 bits) when the wave enters the frame loop [14] and when it leaves it [15], the shader
+// clock (s_memtime) at the same two points [16], [17], HW_ID [18] and XCC_ID [19].
 #define RN_PROF_DECL long long tprev_ = clock64(); \
-  float* profp_ = (DBG && a.dbg) ? a.dbg + (long)blockIdx.x * RN_DBG_FLOATS + 3824 : nullptr;
+  float* profp_ = (DBG && a.dbg) ? a.dbg + (long)blockIdx.x * RN_DBG_FLOATS + 3824 : nullptr; \
+  rn_prof_mark(profp_, 14);
+#define RN_PROF_LEAVE rn_prof_mark(profp_, 15);
 #define STAMP(k) { const long long tn_ = clock64(); if (profp_ && threadIdx.x == 0) profp_[k] += (float)(tn_ - tprev_); tprev_ = tn_; }
+__device__ __forceinline__ void rn_prof_mark(float* p, int k) {
+  if (p && threadIdx.x == 0) {
+    unsigned* u = reinterpret_cast<unsigned*>(p);
+    unsigned hw, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    u[k] = (unsigned)__builtin_amdgcn_s_memrealtime();
+    u[k + 2] = (unsigned)__builtin_amdgcn_s_memtime();
+    u[18] = hw;
+    u[19] = xcc;
+  }
+}
 #elif defined(RN_STOP_AFTER)
 // Diagnostic builds (tools/lds_by_stage.sh): the frame ends at stamp RN_STOP_AFTER, so that the difference of a hardware
 // counter between two such builds is what one stage contributes.  Results are meaningless; never shipped.
 #define RN_PROF_DECL
+#define RN_PROF_LEAVE
 #define STAMP(k) { if ((k) == RN_STOP_AFTER) { __syncthreads(); continue; } }
 #else
 #define RN_PROF_DECL
+#define RN_PROF_LEAVE
 #define STAMP(k)
 #endif
 
@@ -1000,6 +1020,19 @@ __device__ __forceinline__ float2* rn_lds_sa(RnLdsT<1>& L) { return L.s[0].A; }
 __device__ __forceinline__ float2* rn_lds_lp(RnLdsT<3>& L) { return L.pb; }
 __device__ __forceinline__ float2* rn_lds_sa(RnLdsT<3>& L) { return L.pa; }
 
+// This wave's issue priority for frame t of a launch of T frames (rn_prio.h).  HW_ID is read again on every call instead
+// of being kept: the scalar file of the frame loop already spills into VGPR lanes.  s_setprio takes an immediate, so the
+// rule's value is a four-way scalar branch.
+__device__ __forceinline__ void rn_set_prio(int t, int T) {
+  unsigned hw;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+  const int pr = rn_prio_at(hw & 15u, t, T);
+  if (pr == 0) __builtin_amdgcn_s_setprio(0);
+  else if (pr == 1) __builtin_amdgcn_s_setprio(1);
+  else if (pr == 2) __builtin_amdgcn_s_setprio(2);
+  else __builtin_amdgcn_s_setprio(3);
+}
+
 template <bool DBG, int NW>
 __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
   __shared__ RnLdsT<NW> L;
@@ -1010,17 +1043,13 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
   int lane = lane0;
   const RnTables* tab = a.tab;
   const float* xs = a.xhp + (long)b * a.xhp_stride;
-  if constexpr (NW == 1) {
-    // Different issue priorities per wave slot, so that the four waves of a SIMD drift out of phase without anyone
-    // sleeping: -0.8 % per step over three alternating 30-step runs (by SIMD, or by slot + SIMD parity: no change).
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    const unsigned pr = hw & 3u;
-    if (pr == 0) __builtin_amdgcn_s_setprio(0);
-    else if (pr == 1) __builtin_amdgcn_s_setprio(1);
-    else if (pr == 2) __builtin_amdgcn_s_setprio(2);
-    else __builtin_amdgcn_s_setprio(3);
-  }
+  // Different issue priorities for the four waves of a SIMD, so that they drift out of phase without anyone sleeping.
+  // Which wave holds which priority is rn_prio.h's rule.  Fixed per slot for the whole launch (mode 1, set here once) was
+  // -0.8 % per step while the kernel was latency-bound; with the vector issue port full it makes the priority-3 wave of
+  // a SIMD leave at 75 % of a 12-frame launch and the priority-0 wave at 94 %, alone on its SIMD at the end (NOTEBOOK
+  // section 26).  Rotating the priorities by one every frame (mode 2, at the top of the frame loop) keeps the de-phasing
+  // and evens the progress: waves idle for 8.8 % of a launch instead of 15.8 %, -4.4 % per step.
+  if constexpr (NW == 1 && kRnPrioMode == 1) rn_set_prio(0, a.T);
 
 #if RN_POISON_LDS
   // Checker build (`make variants` -> libcrispy_hip_poison.so, tests/test_gpu_rnnoise.py): LDS is not cleared between
@@ -1061,6 +1090,7 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
   for (int tick = 0; tick < a.T + (NW - 1); ++tick) {
     const int t = tick - wave;
     if (NW == 1 || (t >= 0 && t < a.T)) {
+    if constexpr (NW == 1 && kRnPrioMode >= 2) rn_set_prio(t, a.T);
     RnSlot& SL = L.s[NW == 1 ? 0 : (t & 1)];
     float* lp = reinterpret_cast<float*>(rn_lds_lp(L));   // 864 floats during the pitch phase
     float* Sa = reinterpret_cast<float*>(rn_lds_sa(L));   // pitch-phase scratch
@@ -1890,6 +1920,7 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
     }      // this wave has a frame in this tick
     if constexpr (NW > 1) __syncthreads();
   }
+  RN_PROF_LEAVE
 
   // ---- store per-stream state (NW = 3: by the wave that owns it) ----
   if (own_c) {
