@@ -322,6 +322,8 @@ extern "C" {
     pub fn crispy_diar_affinity_device(h: *mut c_void, d_emb: *const c_float, n: c_int, dim: c_int, d_aff: *mut c_float) -> c_int;
     pub fn crispy_diar_laplacian_device(h: *mut c_void, d_aff: *const c_float, n: c_int, p: c_int, d_lap: *mut c_float) -> c_int;
     pub fn crispy_diar_eigh_device(h: *mut c_void, d_mats: *const c_float, n: c_int, n_mats: c_int, d_evals: *mut c_float, d_evecs: *mut c_float) -> c_int;
+    pub fn crispy_diar_decide_device(h: *mut c_void, d_evals: *const c_float, n: c_int, p_max: c_int, max_speakers: c_int, info: *mut c_void) -> c_int;
+    pub fn crispy_diar_kmeans_device(h: *mut c_void, d_vecs: *const c_float, n: c_int, k: c_int, d_labels: *mut c_int, d_points: *mut c_float, d_centers: *mut c_float) -> c_int;
     pub fn crispy_diar_chunk_plan(start: *const f64, end: *const f64, n_samples: *const c_long, n_segments: c_long, sample_rate: c_int, out_start: *mut f64, out_end: *mut f64, out_segment: *mut c_long, out_first: *mut c_long, out_len: *mut c_long, cap: c_long) -> c_long;
     pub fn crispy_diar_speaker_segments(start: *const f64, end: *const f64, labels: *const c_int, n: c_long, merge_gap: f64, out_start: *mut f64, out_end: *mut f64, out_speaker: *mut c_int, cap: c_long) -> c_long;
     pub fn crispy_diar_find_speaker(time: f64, seg_start: *const f64, seg_end: *const f64, seg_speaker: *const c_int, n_segments: c_long) -> c_int;

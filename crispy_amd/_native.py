@@ -64,7 +64,8 @@ RS_SYMBOLS = ("crispy_resampler_create", "crispy_resampler_destroy", "crispy_res
               "crispy_resampler_process_device", "crispy_resampler_synchronize")
 DIAR_SYMBOLS = ("crispy_diar_create", "crispy_diar_destroy", "crispy_diar_cluster", "crispy_diar_cluster_device",
                 "crispy_diar_affinity_device", "crispy_diar_laplacian_device", "crispy_diar_eigh_device",
-                "crispy_diar_chunk_plan", "crispy_diar_speaker_segments", "crispy_diar_find_speaker",
+                "crispy_diar_decide_device", "crispy_diar_kmeans_device", "crispy_diar_chunk_plan",
+                "crispy_diar_speaker_segments", "crispy_diar_find_speaker",
                 "crispy_diar_format_text", "crispy_diar_format_result")
 ALL_SYMBOLS = RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS + DIAR_SYMBOLS
 DIAR_MAX_N, DIAR_MAX_DIM, DIAR_MAX_BATCH, DIAR_LDS_N = 2048, 1024, 64, 192
@@ -307,6 +308,8 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_diar_affinity_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.crispy_diar_laplacian_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.crispy_diar_eigh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.crispy_diar_decide_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.crispy_diar_kmeans_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.crispy_diar_chunk_plan.argtypes = [f64p, f64p, lp, C.c_long, C.c_int, f64p, f64p, lp, lp, lp, C.c_long]
     L.crispy_diar_chunk_plan.restype = C.c_long
     L.crispy_diar_speaker_segments.argtypes = [f64p, f64p, i32p, C.c_long, C.c_double, f64p, f64p, i32p, C.c_long]

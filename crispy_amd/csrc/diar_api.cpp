@@ -439,6 +439,59 @@ int crispy_diar_eigh_device(void* hv, const float* d_mats, int n, int n_mats, fl
 }
 CRISPY_CATCH_RET("crispy_diar_eigh_device")
 
+int crispy_diar_decide_device(void* hv, const float* d_evals, int n, int p_max, int max_speakers, void* info) try {
+  crispy_diar* h = static_cast<crispy_diar*>(hv);
+  if (!h || !info) return fail(CRISPY_ERR_INVALID_ARG, "crispy_diar_decide_device: NULL handle or info");
+  if (n < 0 || n > kMaxN || p_max < 0 || p_max > kMaxN)
+    return fail(CRISPY_ERR_INVALID_ARG, "crispy_diar_decide_device: n %d or p_max %d outside 0 ... %d", n, p_max, kMaxN);
+  crispy_diar_info out{0, n > 0 ? 1 : 0, 0.0f, 0.0f, 0};
+  if (n > 2 && p_max > 0) {
+    if (!d_evals) return fail(CRISPY_ERR_INVALID_ARG, "crispy_diar_decide_device: NULL eigenvalues");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(h->descs.grow(4096));
+    HIP_TRY(h->infos.grow((size_t)kMaxBatch * sizeof(crispy_diar_info)));
+    const ClusterDesc cd{d_evals, nullptr, nullptr, nullptr, nullptr, n, std::min(std::max(max_speakers, 1), n - 1), p_max, 0};
+    ClusterDesc* d_cd = reinterpret_cast<ClusterDesc*>(h->descs.p + 256);
+    crispy_diar_info* d_infos = h->infos.as<crispy_diar_info>();
+    HIP_TRY(hipMemcpyAsync(d_cd, &cd, sizeof cd, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_infos, &out, sizeof out, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(launch_decide(d_cd, 1, d_infos, h->stream));
+    HIP_TRY(hipMemcpyAsync(&out, d_infos, sizeof out, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  std::memcpy(info, &out, sizeof out);
+  return CRISPY_OK;
+}
+CRISPY_CATCH_RET("crispy_diar_decide_device")
+
+int crispy_diar_kmeans_device(void* hv, const float* d_vecs, int n, int k, int* d_labels, float* d_points, float* d_centers) try {
+  crispy_diar* h = static_cast<crispy_diar*>(hv);
+  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "crispy_diar_kmeans_device: NULL handle");
+  if (n < 0 || n > kMaxN || k < 1) return fail(CRISPY_ERR_INVALID_ARG, "crispy_diar_kmeans_device: n %d outside 0 ... %d or k %d < 1", n, kMaxN, k);
+  if (n == 0) return CRISPY_OK;
+  if (!d_vecs || !d_labels) return fail(CRISPY_ERR_INVALID_ARG, "crispy_diar_kmeans_device: NULL vectors or labels");
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t kk = k < n ? (size_t)k : 0;      // k >= n reads no point and keeps no centre
+  Carve c;
+  c.take<float>((size_t)n * kk); c.take<float>(kk * kk);
+  HIP_TRY(h->scratch.grow(c.used));
+  c = Carve{h->scratch.p, 0};
+  float* pts = c.take<float>((size_t)n * kk);
+  float* centers = c.take<float>(kk * kk);
+  HIP_TRY(h->descs.grow(4096));
+  HIP_TRY(h->infos.grow((size_t)kMaxBatch * sizeof(crispy_diar_info)));
+  const ClusterDesc cd{nullptr, d_vecs, d_points ? d_points : pts, d_centers ? d_centers : centers, d_labels, n, k, 0, 0};
+  const crispy_diar_info in{0, k, 0.0f, 0.0f, 0};
+  ClusterDesc* d_cd = reinterpret_cast<ClusterDesc*>(h->descs.p + 256);
+  crispy_diar_info* d_infos = h->infos.as<crispy_diar_info>();
+  HIP_TRY(hipMemcpyAsync(d_cd, &cd, sizeof cd, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(d_infos, &in, sizeof in, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(launch_kmeans(d_cd, 1, d_infos, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return CRISPY_OK;
+}
+CRISPY_CATCH_RET("crispy_diar_kmeans_device")
+
 long crispy_diar_chunk_plan(const double* start, const double* end, const long* n_samples, long n_segments, int sample_rate,
                             double* out_start, double* out_end, long* out_segment, long* out_first, long* out_len, long cap) try {
   if (n_segments < 0 || cap < 0 || sample_rate <= 0) return fail(CRISPY_ERR_INVALID_ARG, "crispy_diar_chunk_plan: negative count or sample_rate <= 0");

@@ -113,39 +113,43 @@ __global__ void eig_init_kernel(EigDesc* __restrict__ descs) {
 
 // The sum of one value per thread, in an order that depends on the workgroup's size alone.
 template <int NT>
-__device__ float block_sum(float v, float* red) {
+__device__ double block_sum(double v, double* red) {
   red[threadIdx.x] = v;
   __syncthreads();
   for (int s = NT / 2; s > 0; s >>= 1) {
     if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
     __syncthreads();
   }
-  const float r = red[0];
+  const double r = red[0];
   __syncthreads();
   return r;
 }
-__device__ inline bool converged(float off2, float diag2, int n) {
-  const float tol = (float)n * kEps;
+// off <= n * eps * diag on the sums of squares.  The squares and their sums are double: the square of any finite f32 lies
+// inside its range, so the test reads the same whatever the scale of the matrix (in f32 the squares of entries above
+// 1.8e19 are inf and those of entries below 1e-23 are 0, and either way the test passed at once).
+__device__ inline bool converged(double off2, double diag2, int n) {
+  const double tol = (double)n * (double)kEps;
   return off2 <= tol * tol * diag2;
 }
 
 // Form 1: one workgroup per matrix of order <= kLdsN, the matrix in LDS (the vectors, where wanted, in global memory).
 constexpr int kLdsThreads = 512;
+constexpr size_t kLdsRedAt = ((size_t)kLdsN * kLdsN + 3 * (kLdsN / 2 + 1) + 1) / 2 * 2;      // in floats, even: red is double
 __global__ __launch_bounds__(kLdsThreads) void eig_lds_kernel(EigDesc* __restrict__ descs) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   EigDesc& d = descs[blockIdx.x];
   const int n = d.n, m = rr_steps(n), K = rr_pairs(n), tid = threadIdx.x;
   float* a = lds;                        // [n][n]
   float* cs = a + (size_t)kLdsN * kLdsN;  // [K][3]: c, s, t
-  float* red = cs + 3 * (kLdsN / 2 + 1);  // [kLdsThreads]
+  double* red = reinterpret_cast<double*>(lds + kLdsRedAt);  // [kLdsThreads]
   for (int e = tid; e < n * n; e += kLdsThreads) a[e] = d.A[e];
   __syncthreads();
   int status = 1;
   bool last = false;      // the convergence test has passed: one more sweep, which takes the off-diagonal to rounding level
   for (int sweep = 0; sweep <= kMaxSweeps; ++sweep) {
-    float off2 = 0.0f, diag2 = 0.0f;
+    double off2 = 0.0, diag2 = 0.0;
     for (int e = tid; e < n * n; e += kLdsThreads) {
-      const float v = a[e] * a[e];
+      const double v = (double)a[e] * (double)a[e];
       if (e / n == e % n) diag2 += v; else off2 += v;
     }
     off2 = block_sum<kLdsThreads>(off2, red);
@@ -201,14 +205,14 @@ __global__ __launch_bounds__(kLdsThreads) void eig_lds_kernel(EigDesc* __restric
 // set one eig_cs_kernel and one eig_apply_kernel over all matrices (a matrix that is done or has fewer steps sits out).
 constexpr int kNormThreads = 1024;
 __global__ __launch_bounds__(kNormThreads) void eig_norm_kernel(EigDesc* __restrict__ descs, int* __restrict__ n_active) {
-  __shared__ float red[kNormThreads];
+  __shared__ double red[kNormThreads];
   EigDesc& d = descs[blockIdx.x];
   if (!d.active) return;
   const int n = d.n;
-  float off2 = 0.0f, diag2 = 0.0f;
+  double off2 = 0.0, diag2 = 0.0;
   for (int i = 0; i < n; ++i)
     for (int j = threadIdx.x; j < n; j += kNormThreads) {
-      const float v = d.A[(size_t)i * n + j];
+      const double v = d.A[(size_t)i * n + j];
       if (i == j) diag2 += v * v; else off2 += v * v;
     }
   off2 = block_sum<kNormThreads>(off2, red);
@@ -339,8 +343,8 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_kernel(const ClusterDesc* _
   __shared__ int changed;
   const ClusterDesc& c = recs[blockIdx.x];
   const int n = c.n, k = infos[c.index].k, tid = threadIdx.x;
-  if (n <= 2 || k <= 1) {
-    for (int i = tid; i < n; i += kKmThreads) c.labels[i] = 0;
+  if (k <= 1 || k >= n) {      // (:476-481) before a point is read: a recording of a cluster call has 1 <= k < n
+    for (int i = tid; i < n; i += kKmThreads) c.labels[i] = k <= 1 ? 0 : i;
     return;
   }
   float* pts = c.pts;          // [n][k]
@@ -358,10 +362,6 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_kernel(const ClusterDesc* _
     }
     mind[i] = FLT_MAX;
     c.labels[i] = 0;
-  }
-  if (k >= n) {
-    for (int i = tid; i < n; i += kKmThreads) c.labels[i] = i;
-    return;
   }
   __syncthreads();
   for (int d = tid; d < k; d += kKmThreads) ctr[d] = pts[d];
@@ -448,7 +448,7 @@ hipError_t launch_eig_init(EigDesc* d_descs, int count, hipStream_t st) {
   eig_init_kernel<<<dim3(64, count), 256, 0, st>>>(d_descs);
   return hipGetLastError();
 }
-size_t eig_lds_bytes() { return ((size_t)kLdsN * kLdsN + 3 * (kLdsN / 2 + 1) + kLdsThreads) * sizeof(float); }
+size_t eig_lds_bytes() { return kLdsRedAt * sizeof(float) + kLdsThreads * sizeof(double); }
 hipError_t launch_eig_lds(EigDesc* d_descs, int count, hipStream_t st) {
   const hipError_t e = lds_limit(reinterpret_cast<const void*>(eig_lds_kernel), eig_lds_bytes());
   if (e != hipSuccess) return e;

@@ -79,6 +79,29 @@ class Diarizer:
         N.check(self._L.crispy_diar_eigh_device(self._h, mats.data_ptr(), n, m, ev.data_ptr(), vec.data_ptr() if vectors else None), self._L)
         return ev, vec
 
+    def decide(self, evals, n: int, max_speakers: int) -> dict:
+        """The eigengap decision alone.  evals: CUDA f32 [p_max, n], row p - 1 ascending, or None -> info dict."""
+        p_max = 0 if evals is None else evals.shape[0]
+        info = N.DiarInfo()
+        N.check(self._L.crispy_diar_decide_device(self._h, evals.data_ptr() if p_max and n else None, int(n), p_max, int(max_speakers),
+                                                  C.cast(C.pointer(info), C.c_void_p)), self._L)
+        return dict(p_star=info.p_star, k=info.k, ratio=info.ratio, gap=info.gap, p_max=info.p_max)
+
+    def kmeans(self, vecs, k: int, details: bool = False):
+        """Spectral rows and k-means alone.  vecs: CUDA f32 [n, n] (the first k columns are read) -> int32 CUDA labels [n],
+        with `details` also the normalised points [n, k] and the final centres [k, k] (None where k <= 1 or k >= n)."""
+        import torch
+        n = vecs.shape[0]
+        labels = torch.zeros(n, dtype=torch.int32, device=vecs.device)
+        pts = ctr = None
+        if details and 1 < k < n:
+            pts = torch.zeros((n, k), dtype=torch.float32, device=vecs.device)
+            ctr = torch.zeros((k, k), dtype=torch.float32, device=vecs.device)
+        N.check(self._L.crispy_diar_kmeans_device(self._h, vecs.data_ptr() if n else None, n, int(k), labels.data_ptr() if n else None,
+                                                  pts.data_ptr() if pts is not None else None,
+                                                  ctr.data_ptr() if ctr is not None else None), self._L)
+        return (labels, pts, ctr) if details else labels
+
 
 def nme_sc(embeddings, max_speakers: int, device: int = 0) -> np.ndarray:
     """`nme_sc(&embeddings, max_speakers)` (diarization.rs:541): raw labels of one recording's [n, dim] embeddings."""

@@ -997,7 +997,8 @@ int crispy_resampler_synchronize(crispy_resampler *h);
  *                step updated independently), all Laplacians of all recordings of a call side by side, in one of two
  *                forms chosen by n alone:  n <= 192: one workgroup per matrix, the matrix in LDS (147 KB of the 160);
  *                193 ... 2048: the matrix in global memory, one launch pair per rotation set for all matrices.
- *                The off-diagonal norm is tested before every sweep; once it is <= n * 2^-24 * the diagonal's norm the
+ *                The off-diagonal norm is tested before every sweep (squares summed in double, so no scale of the
+ *                matrix overflows or underflows the test); once it is <= n * 2^-24 * the diagonal's norm the
  *                matrix gets one last sweep (the convergence is quadratic: that sweep leaves rounding only) and is
  *                done.  40 sweeps without passing the test fail the call with CRISPY_ERR_INTERNAL.  Rotations are
  *                worked out in double and applied in f32.  A matrix's result does not depend on what else is in
@@ -1039,10 +1040,25 @@ int crispy_diar_cluster_device(void *h, const float *d_emb, const int *n, int ba
  *   laplacian  d_aff [n][n] (symmetric, as affinity writes it) and p >= 1 -> d_lap [n][n]
  *   eigh       n_mats symmetric f32 matrices d_mats [n_mats][n][n] (left as they are) -> d_evals [n_mats][n] ascending and,
  *              unless d_evecs is NULL, d_evecs [n_mats][n][n]: column c of a matrix belongs to its eigenvalue c.
- *              1 <= n <= 2048, n_mats >= 1, n_mats * n * n * 4 bytes (x 2 with vectors) <= 2 GB */
+ *              1 <= n <= 2048, n_mats >= 1, n_mats * n * n * 4 bytes (x 2 with vectors) <= 2 GB.  Any finite entries:
+ *              the convergence test sums its squares in double, so it reads the same at every scale.  The eigenvalues
+ *              are within n * 2^-24 * |A|_2 where that bound is a normal f32 (|A|_2 above about 1e-30 / n) and |A|_2 * n
+ *              stays below the f32 maximum; a NaN or infinite entry ends in CRISPY_ERR_INTERNAL after the 40 sweeps.
+ *   decide     the decision of crispy_diar_cluster on given eigenvalues: d_evals [p_max][n], row p - 1 the ascending
+ *              eigenvalues at p (read as they are: nothing is sorted here) -> *info (host, one crispy_diar_info).
+ *              0 <= n <= 2048, 0 <= p_max <= 2048, kmax from max_speakers as above; n <= 2 or p_max == 0 gives the
+ *              zero info (k = 1, or 0 for n == 0) without a launch.
+ *   kmeans     the spectral rows and k-means of crispy_diar_cluster on given vectors: d_vecs [n][n], of which the first
+ *              k columns are read -> d_labels [n]; d_points [n][k] (the rows, normalised where their norm is > 1e-9) and
+ *              d_centers [k][k] (the final centres) are nullable.  0 <= n <= 2048 (0 writes nothing), k >= 1; k == 1
+ *              gives zeros and k >= n gives 0 ... n-1 (kmeans, :476-481), and neither reads d_vecs or writes points
+ *              or centres.
+ *   decide and kmeans launch the kernels of crispy_diar_cluster themselves, on one recording. */
 int crispy_diar_affinity_device(void *h, const float *d_emb, int n, int dim, float *d_aff);
 int crispy_diar_laplacian_device(void *h, const float *d_aff, int n, int p, float *d_lap);
 int crispy_diar_eigh_device(void *h, const float *d_mats, int n, int n_mats, float *d_evals, float *d_evecs);
+int crispy_diar_decide_device(void *h, const float *d_evals, int n, int p_max, int max_speakers, void *info);
+int crispy_diar_kmeans_device(void *h, const float *d_vecs, int n, int k, int *d_labels, float *d_points, float *d_centers);
 
 /* Host functions: no device, no handle.  Speakers are numbers: s >= 1 is "Speaker s", 0 is "Speaker ?".
  *   crispy_diar_chunk_plan: run_diarization's split of speech segments into ~4 s chunks (:311-338).  Segment i spans

@@ -19,17 +19,22 @@ def bar(n):
 
 
 def affinity(emb):
+    """cosine_similarity (:412-414) of every pair, zero diagonal.  Where the quotient of cosine_distance (:625) is a NaN --
+    finite rows whose norms overflow give inf / inf -- Rust's f32::max returns its other argument: (1 - NaN).max(0.0) = 0,
+    the distance is 0 and the similarity (1 - 0).clamp(0, 1) = 1.  np.fmax has that rule (np.maximum would hand the NaN
+    on); for every other value the two agree, so nothing else changes by a bit."""
     emb = np.asarray(emb, F)
     n, dim = emb.shape
     dot = np.zeros((n, n), F)
     nrm = np.zeros(n, F)
-    for d in range(dim):
-        c = emb[:, d]
-        dot = dot + np.multiply.outer(c, c)
-        nrm = nrm + c * c
+    with np.errstate(over="ignore", invalid="ignore"):
+        for d in range(dim):
+            c = emb[:, d]
+            dot = dot + np.multiply.outer(c, c)
+            nrm = nrm + c * c
     na, nb = nrm[:, None], nrm[None, :]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        dist = np.maximum(F(1) - dot / (np.sqrt(na) * np.sqrt(nb)), F(0))
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        dist = np.fmax(F(1) - dot / (np.sqrt(na) * np.sqrt(nb)), F(0))
     dist = np.where((na == 0) | (nb == 0), F(1), dist).astype(F)
     sim = np.clip(F(1) - dist, F(0), F(1)).astype(F)
     np.fill_diagonal(sim, F(0))
@@ -90,16 +95,59 @@ def _sq_dist(pts, c):
     return s
 
 
-def kmeans(points, k):
+def decide(evals, n, p_max, max_speakers, trace=False):
+    """The sweep's decision (:570-582) on given eigenvalues: evals[p - 1] the f32 eigenvalues at p, taken as they are.
+    -> (p_star, k, ratio, gap), ratio and gap f32; with `trace` also the list of every p's ratio.  n <= 2 or p_max <= 0:
+    the zero decision (0, 1 or 0 for n == 0, 0, 0)."""
+    if n <= 2 or p_max <= 0:
+        out = (0, 1 if n else 0, F(0), F(0))
+        return out + ([],) if trace else out
+    kmax = min(max(max_speakers, 1), n - 1)
+    best, ratios = None, []
+    for p in range(1, p_max + 1):
+        k, gap = max_eigengap(np.asarray(evals[p - 1], F), kmax)
+        ratio = F(F(p) / F(n)) / max(gap, F(1e-6))
+        ratios.append(ratio)
+        if best is None or ratio < best[0]:
+            best = (ratio, p, k, gap)
+    ratio, p_star, k, gap = best
+    out = (p_star, min(max(k, 1), kmax), F(ratio), F(gap))
+    return out + (ratios,) if trace else out
+
+
+def spectral_rows(vecs, k):
+    """The first k columns of vecs [n][>= k], each row divided by its norm (sequential f32 sum of squares) where the norm
+    is > 1e-9 (:598-609) -> f32 [n][k]"""
+    x = np.array(np.asarray(vecs)[:, :k], F)
+    s = np.zeros(x.shape[0], F)
+    for c in range(k):
+        s = s + x[:, c] * x[:, c]
+    norm = np.sqrt(s)
+    big = norm > F(1e-9)
+    x[big] = x[big] / norm[big, None]
+    return x
+
+
+def kmeans(points, k, max_iter=50, details=False):
     """-> (labels, assignment margin over all iterations, seeding margin).  The seeding margin is, over the seeding steps,
     the distance of the chosen point minus the largest distance of a point that ends in ANOTHER cluster: choosing another
-    point of the same cluster leaves the order of the clusters, and so the numbering of the labels, as it is."""
+    point of the same cluster leaves the order of the clusters, and so the numbering of the labels, as it is.
+    `max_iter` is the cap on Lloyd iterations (the reference's 50).  With `details` a dict instead: those three as
+    labels / margin / seed_margin, `iterations` (assignment passes run, the one that changed nothing included), `points`
+    (f32, as given) and `centers` (f32 [k][dim], final; None where k <= 1 or k >= n)."""
     pts = np.asarray(points, F)
+    res = _kmeans(pts, k, max_iter)
+    if not details:
+        return res[:3]
+    return dict(labels=res[0], margin=res[1], seed_margin=res[2], iterations=res[3], points=pts, centers=res[4])
+
+
+def _kmeans(pts, k, max_iter):
     n = pts.shape[0]
     if k <= 1 or n == 0:
-        return np.zeros(n, np.int64), math.inf, math.inf
+        return np.zeros(n, np.int64), math.inf, math.inf, 0, None
     if k >= n:
-        return np.arange(n), math.inf, math.inf
+        return np.arange(n), math.inf, math.inf, 0, None
     dim = pts.shape[1]
     centers = [pts[0].copy()]
     steps = []
@@ -113,7 +161,10 @@ def kmeans(points, k):
     centers = np.array(centers, F)
     labels = np.zeros(n, np.int64)
     margin = math.inf
-    for _ in range(50):
+    iterations = 0
+    zero = np.zeros((1, dim), F)
+    for _ in range(max_iter):
+        iterations += 1
         dist = np.stack([_sq_dist(pts, centers[c]) for c in range(k)], 1)
         new = np.argmin(dist, 1)                 # first of equals == strict `<`
         srt = np.sort(dist.astype(np.float64), 1)
@@ -122,10 +173,8 @@ def kmeans(points, k):
         labels = new
         for c in range(k):
             members = np.nonzero(labels == c)[0]
-            if len(members):
-                s = np.zeros(dim, F)
-                for i in members:
-                    s = s + pts[i]
+            if len(members):      # 0 + p0 + p1 + ... in f32, in point order (an accumulate is sequential)
+                s = np.add.accumulate(np.concatenate([zero, pts[members]], 0), 0, dtype=F)[-1]
                 centers[c] = s / F(len(members))
         if not changed:
             break
@@ -134,7 +183,7 @@ def kmeans(points, k):
         other = d[labels != labels[best]]
         if len(other):
             seed_margin = min(seed_margin, float(d[best] - other.max()))
-    return labels, margin, seed_margin
+    return labels, margin, seed_margin, iterations, centers
 
 
 def eigh(lap, solver):
@@ -157,34 +206,21 @@ def nme_sc(emb, max_speakers, solver="f64"):
     aff = affinity(emb)
     p_max = p_max_of(n)
     order = neighbour_order(aff)
-    best = None
-    ratios, gap_margins = [], []
+    evs, gap_margins = [], []
     for p in range(1, p_max + 1):
         w, _ = eigh(pruned_normalized_laplacian(aff, p, order), solver)
-        k, gap = max_eigengap(w.astype(F), kmax)
-        ratio = F(F(p) / F(n)) / max(gap, F(1e-6))
+        evs.append(w.astype(F))
         g64 = np.sort(np.diff(w.astype(np.float64)[:min(kmax + 1, n)]))
         gap_margins.append(float(g64[-1] - g64[-2]) if len(g64) > 1 else math.inf)
-        ratios.append(float(ratio))
-        if best is None or ratio < best[0]:
-            best = (ratio, p, k, gap)
-    ratio, p_star, k, gap = best
-    k = min(max(k, 1), kmax)
-    rs = sorted(ratios)
+    p_star, k, ratio, gap, ratios = decide(evs, n, p_max, max_speakers, trace=True)
+    rs = sorted(float(r) for r in ratios)
     out.update(p_star=p_star, k=k, ratio=ratio, gap=gap, p_max=p_max, gap_margin=gap_margins[p_star - 1],
                ratio_margin=(rs[1] - rs[0]) / rs[0] if len(rs) > 1 else math.inf)
     if k <= 1:
         return out
     w, v = eigh(pruned_normalized_laplacian(aff, p_star, order), solver)
     idx = np.argsort(w, kind="stable")
-    spectral = v[:, idx[:k]].astype(F)
-    for r in range(n):
-        s = F(0)
-        for c in range(k):
-            s = s + spectral[r, c] * spectral[r, c]
-        norm = np.sqrt(s)
-        if norm > F(1e-9):
-            spectral[r] = spectral[r] / norm
+    spectral = spectral_rows(v[:, idx[:k]].astype(F), k)
     labels, margin, seed_margin = kmeans(spectral, k)
     out.update(labels=labels, kmeans_margin=margin, seed_margin=seed_margin)
     return out

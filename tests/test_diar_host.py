@@ -19,7 +19,7 @@ def test_symbols_are_declared_in_header_binding_and_rust():
     hdr = open(os.path.join(ROOT, "include", "crispy_hip.h")).read()
     rs = open(os.path.join(ROOT, "bindings", "rust", "crispy-hip-sys", "src", "lib.rs")).read()
     L = N.lib()
-    assert len(N.DIAR_SYMBOLS) == 12
+    assert len(N.DIAR_SYMBOLS) == 14
     for name in N.DIAR_SYMBOLS:
         assert re.search(r"\b%s\s*\(" % name, hdr) and ("pub fn %s(" % name) in rs, name
         assert name in N.ALL_SYMBOLS and hasattr(L, name) and getattr(L, name).argtypes, name
@@ -47,6 +47,8 @@ def test_device_entry_points_validate_before_any_device_work():
     assert L.crispy_diar_affinity_device(None, None, 3, 4, None) == -1
     assert L.crispy_diar_laplacian_device(None, None, 3, 1, None) == -1
     assert L.crispy_diar_eigh_device(None, None, 3, 1, None, None) == -1
+    assert L.crispy_diar_decide_device(None, None, 3, 1, 8, None) == -1 and b"NULL handle" in L.crispy_last_error()
+    assert L.crispy_diar_kmeans_device(None, None, 3, 2, None, None, None) == -1 and b"NULL handle" in L.crispy_last_error()
     L.crispy_diar_destroy(None)
     if L.crispy_device_count() == 0:
         h = C.c_void_p()

@@ -104,6 +104,61 @@ def test_kmeans_rules():
     assert O.kmeans(pts, 1)[0].tolist() == [0] * 5 and O.kmeans(pts, 5)[0].tolist() == [0, 1, 2, 3, 4]
 
 
+def test_affinity_follows_f32_max_where_a_nan_arises():
+    """:625 `(1.0 - (dot / ..)).max(0.0)`: f32::max returns the operand that is a number, so inf / inf gives distance 0 and
+    similarity 1; a norm that underflows to 0 takes the `== 0.0` branch (:622): distance 1, similarity 0."""
+    big, tiny, part = [1e20] * 3, [1e-25] * 3, [3e19, 1, -2]
+    aff = O.affinity(np.array([big, [-1e20] * 3, tiny, part, [1, 2, 3], [3, 2, 1]], np.float32))
+    assert np.isfinite(aff).all() and (aff == aff.T).all()
+    assert aff[0, 1] == 1 and aff[0, 3] == 1 and aff[1, 3] == 1      # NaN quotients, the opposite rows 0 and 1 included
+    assert not aff[2].any()                                          # 3e-50 is 0 in f32
+    assert not aff[[0, 1, 3], 4:].any()                              # finite / inf = 0: distance 1
+    assert abs(aff[4, 5] - 10 / 14) < 1e-6
+
+
+def test_decide_is_the_sweep_of_the_reference():
+    f = np.float32
+    assert O.decide([[0, .25, .75, 1.25, 1.25, 1.5]], 6, 1, 8) == (1, 2, f(1) / f(6) / f(.5), f(.5))      # first of two equal gaps
+    rows = [[0, .25, .25, .25, .25, .25], [0, 0, .5, .5, .5, .5]]
+    p, k, ratio, gap, ratios = O.decide(rows, 6, 2, 8, trace=True)
+    assert ratios[0].tobytes() == ratios[1].tobytes() and (p, k, gap) == (1, 1, f(.25))      # a tied ratio stays with the first p
+    assert O.decide(rows[::-1], 6, 2, 8)[:2] == (1, 2)
+    assert O.decide(np.full((3, 5), .75), 5, 3, 8) == (1, 1, f(f(1) / f(5)) / f(1e-6), f(0))      # the 1e-6 floor
+    assert O.decide([[2, 1.5, 1.4, .5, 0]], 5, 1, 8)[1:] == (2, f(.2) / f(1e-6), f(0))              # unsorted: taken as it is
+    ev = [[0, .1, .2, .35, .4, .5, 1.5, 1.6, 1.7, 1.8]]
+    assert [O.decide(ev, 10, 1, ms)[1] for ms in (3, 5, 6, 50, 0, -3)] == [3, 3, 6, 6, 1, 1]      # kmax hides the gap at 6
+    assert O.decide(ev, 2, 1, 8) == (0, 1, f(0), f(0)) and O.decide(ev, 0, 1, 8)[:2] == (0, 0) and O.decide(None, 9, 0, 8)[:2] == (0, 1)
+    r = O.nme_sc(O.gaussian_clusters(8, 3, 11, 64, 0.5), 8)
+    assert (r["p_star"], r["k"]) == (r["p_star"], 3) and r["ratio"].dtype == np.float32
+
+
+def test_spectral_rows_threshold():
+    v = np.array([[0, 0, 9], [5e-10, 0, 9], [2e-9, 0, 9], [3, 4, 9]], np.float32)
+    got = O.spectral_rows(v, 2)
+    assert got.dtype == np.float32 and np.array_equal(got, np.array([[0, 0], [5e-10, 0], [1, 0], [.6, .8]], np.float32))
+    assert O.spectral_rows(v, 0).shape == (4, 0)
+
+
+def test_kmeans_iteration_cap_and_details():
+    pts = np.array([[0, 0], [0, 0.1], [5, 5], [5, 5.1], [9, 0]], np.float32)
+    r = O.kmeans(pts, 3, details=True)
+    assert r["labels"].tolist() == [0, 0, 2, 2, 1] and r["iterations"] == 2 and r["points"] is not None
+    assert np.array_equal(r["centers"], np.array([[0, .05], [9, 0], [5, 5.05]], np.float32))
+    assert O.kmeans(pts, 3)[0].tolist() == r["labels"].tolist() and len(O.kmeans(pts, 3)) == 3
+    assert O.kmeans(pts, 5, details=True)["iterations"] == 0 and O.kmeans(pts, 5, details=True)["centers"] is None
+    # a slow run: points crowded at one end of an arc; the cap cuts it, and each further iteration moves labels
+    u = np.random.default_rng(5).random(2048)
+    th = np.sort(u * u) * (np.pi / 2)
+    arc = np.stack([np.cos(th), np.sin(th)], 1).astype(np.float32)
+    free = O.kmeans(arc, 8, 1000, details=True)
+    assert free["iterations"] == 61
+    for cap in (1, 49, 50):
+        capped = O.kmeans(arc, 8, cap, details=True)
+        assert capped["iterations"] == cap and (capped["labels"] != free["labels"]).any()
+    assert np.array_equal(O.kmeans(arc, 8)[0], O.kmeans(arc, 8, 50)[0])
+    assert np.array_equal(O.kmeans(arc, 8, 61)[0], free["labels"])
+
+
 def test_host_glue_reference_cases():
     assert O.speaker_segments([0.0, 1.1], [1.0, 2.0], [0, 0], 0.5) == [(0.0, 2.0, 1)]
     assert len(O.speaker_segments([0.0, 1.1], [1.0, 2.0], [0, 1], 0.5)) == 2
