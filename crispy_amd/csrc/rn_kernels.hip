@@ -94,6 +94,13 @@ __device__ __forceinline__ float dpp_add(float v) {
   asm volatile("" : "+v"(r));
   return r;
 }
+// v + (u of the permuted lane; 0 where the pattern has no source lane), pinned like dpp_add
+template <int CTRL>
+__device__ __forceinline__ float dpp_add_of(float v, float u) {
+  float r = v + dpp_mov<CTRL>(u);
+  asm volatile("" : "+v"(r));
+  return r;
+}
 // v's lane `l` (a constant) := the wave-uniform s; the other lanes keep their value.  One v_writelane_b32 (the compiler has no
 // builtin for it); s comes from an SGPR -- a v_readlane result or scalar arithmetic -- and the lane select is an immediate.
 template <class V>
@@ -113,8 +120,7 @@ __device__ __forceinline__ float wave_sum(float v) {
   v += dpp_mov<0x4E>(v);        // quad_perm [2,3,0,1]
   v += dpp_mov<0x141>(v);       // row_half_mirror
   v += dpp_mov<0x140>(v);       // row_mirror: every lane of a 16-lane row holds the row sum
-  v += dpp_mov<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
-  v += dpp_mov<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3
+  v = ws_join_rows(v);          // row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3 (rn_wave_sums.h)
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
@@ -235,24 +241,49 @@ __device__ __forceinline__ int fft_wr(int j, int r) {
 // second buffer is an immediate offset of the same ds_ instruction), the butterflies of a trip run back to back and
 // the pass has one barrier pair.  Per signal the arithmetic is that of the single form.
 template <int NW, int R, int NS, int NSIG>
-__device__ __forceinline__ void fft_pass_n(float2* const (&bufs)[NSIG], const float2* __restrict__ w960, int lane) {
+__device__ __forceinline__ void fft_pass_n(float2* const (&bufs)[NSIG], const RnTables* __restrict__ tab, int lane) {
   constexpr int M = 480 / R;
   constexpr int NBF = (M + WAVE - 1) / WAVE;
-  float2 o[NSIG][NBF][R];
+  // The last trip of the radix-3 (M = 160) and radix-5 (M = 96) passes has 32 butterflies: with two signals it ran twice
+  // on half a wave.  JOINT: lanes 0 - 31 run signal 0's last 32 butterflies and lanes 32 - 63 signal 1's in ONE trip
+  // (butterfly jm, per-lane buffer) -- five trips instead of six, three instead of four.  Per butterfly the arithmetic
+  // is the same.
+  constexpr bool JOINT = NSIG == 2 && NBF > 1 && M % WAVE == WAVE / 2;
+  constexpr int NFULL = JOINT ? NBF - 1 : NBF;
+  const int jm = M - WAVE / 2 + (lane & (WAVE / 2 - 1));
+  float2 o[NSIG][NFULL][R];
+  [[maybe_unused]] float2 om[R];
   // twiddles of every trip first (clamped butterfly index): one exposed table round trip per pass, not one per trip
-  // (Where NS divides the wave, k = j % NS is the same in every trip and so are the twiddles: one set.)
+  // (Where NS divides the wave, k = j % NS is the same in every trip and so are the twiddles: one set -- the joint trip's
+  // too: M - 32 is a multiple of NS there.)
   constexpr int NTW = (NS > 1 && WAVE % NS == 0) ? 1 : NBF;
+  static_assert(!JOINT || NTW == NBF || (M - WAVE / 2) % NS == 0, "the joint trip shares the twiddles of the full trips");
+  // They come from the row tables (RnTables::tw8 / tw3 / tw5: the values w960[k r (960 / (NS R))] of one k side by side):
+  // one row address per trip and 16-byte loads at immediate offsets, where indexing w960 was a product and a load per r.
   float2 tw[NTW][R];
   if (NS > 1) {
+    static_assert(NS == 1 || (R == 8 && NS == 4) || (R == 3 && NS == 32) || (R == 5 && NS == 96), "a row table per pass");
+    constexpr int RQ = R == 8 ? 4 : (R - 1) / 2;      // 16-byte loads per row; tw8's rows start at r = 0, the others at r = 1
+    // (laundered: the tables lie further from `tab` than a load's immediate offset reaches, and folded into one constant
+    // with the offset inside the row the distance turned every load's address into 64-bit vector arithmetic)
+    typedef const __attribute__((address_space(1))) float4* GRowPtr;
+    GRowPtr rowg = (GRowPtr)reinterpret_cast<const float4*>(R == 8 ? &tab->tw8[0][0] : (R == 3 ? &tab->tw3[0][0] : &tab->tw5[0][0]));
+    asm volatile("" : "+s"(rowg));
+    const float4* rows = (const float4*)rowg;
 #pragma unroll
     for (int nb = 0; nb < NTW; ++nb) {
-      const unsigned k = (unsigned)min(lane + WAVE * nb, M - 1) % NS;
+      const unsigned k = (unsigned)(JOINT && nb == NBF - 1 ? jm : min(lane + WAVE * nb, M - 1)) % NS;
 #pragma unroll
-      for (int r = 1; r < R; ++r) tw[nb][r] = ld_u32(w960, k * (unsigned)(r * (960 / (NS * R))));
+      for (int q = 0; q < RQ; ++q) {
+        const float4 t = ld_u32(rows, k * (unsigned)RQ + q);
+        const int r0 = R == 8 ? 2 * q : 2 * q + 1;
+        if (r0 > 0) tw[nb][r0] = make_float2(t.x, t.y);
+        tw[nb][r0 + 1] = make_float2(t.z, t.w);
+      }
     }
   }
 #pragma unroll
-  for (int nb = 0; nb < NBF; ++nb) {
+  for (int nb = 0; nb < NFULL; ++nb) {
     const int j = lane + WAVE * nb;
     if (j < M) {
 #pragma unroll
@@ -268,9 +299,20 @@ __device__ __forceinline__ void fft_pass_n(float2* const (&bufs)[NSIG], const fl
       }
     }
   }
+  float2* const bm = bufs[JOINT && lane >= WAVE / 2 ? 1 : 0];
+  if constexpr (JOINT) {
+    float2 v[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float2 x = bm[fft_rd<R, NS>(jm, r)];
+      if (NS > 1 && r > 0) x = cmul(x, tw[NTW == 1 ? 0 : NBF - 1][r]);
+      v[r] = x;
+    }
+    butterfly<R>(v, om);
+  }
   rn_sync<NW>();
 #pragma unroll
-  for (int nb = 0; nb < NBF; ++nb) {
+  for (int nb = 0; nb < NFULL; ++nb) {
     const int j = lane + WAVE * nb;
     if (j < M) {
 #pragma unroll
@@ -280,28 +322,32 @@ __device__ __forceinline__ void fft_pass_n(float2* const (&bufs)[NSIG], const fl
       }
     }
   }
+  if constexpr (JOINT) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) bm[fft_wr<R, NS>(jm, r)] = om[r];
+  }
   rn_sync<NW>();
 }
 template <int NW, int R, int NS>
-__device__ __forceinline__ void fft_pass(float2* buf, const float2* __restrict__ w960, int lane) {
+__device__ __forceinline__ void fft_pass(float2* buf, const RnTables* __restrict__ tab, int lane) {
   float2* const bufs[1] = {buf};
-  fft_pass_n<NW, R, NS, 1>(bufs, w960, lane);
+  fft_pass_n<NW, R, NS, 1>(bufs, tab, lane);
 }
 
 // forward DFT of the 480 complex points in buf (unscaled, natural order); caller synchronised
 template <int NW>
-__device__ __forceinline__ void fft480(float2* buf, const float2* __restrict__ w960, int lane) {
-  fft_pass<NW, 4, 1>(buf, w960, lane);
-  fft_pass<NW, 8, 4>(buf, w960, lane);      // 480 = 4 . 8 . 3 . 5: four LDS round trips instead of five (4 . 4 . 2 . 3 . 5)
-  fft_pass<NW, 3, 32>(buf, w960, lane);
-  fft_pass<NW, 5, 96>(buf, w960, lane);
+__device__ __forceinline__ void fft480(float2* buf, const RnTables* __restrict__ tab, int lane) {
+  fft_pass<NW, 4, 1>(buf, tab, lane);
+  fft_pass<NW, 8, 4>(buf, tab, lane);      // 480 = 4 . 8 . 3 . 5: four LDS round trips instead of five (4 . 4 . 2 . 3 . 5)
+  fft_pass<NW, 3, 32>(buf, tab, lane);
+  fft_pass<NW, 5, 96>(buf, tab, lane);
 }
 
 // The same transform with the first pass (radix 4, stride 1) fed by a loader instead of LDS: in(g, j, r) returns point
 // j + 120 r of signal g.  The analysis transforms window their input straight from global memory this way, which saves the
 // separate "window -> LDS -> barrier -> read back" phase.  The buffers must be free (caller synchronised).
 template <int NW, int NSIG, class In>
-__device__ __forceinline__ void fft480_from(float2* const (&bufs)[NSIG], In in, const float2* __restrict__ w960, int lane) {
+__device__ __forceinline__ void fft480_from(float2* const (&bufs)[NSIG], In in, const RnTables* __restrict__ tab, int lane) {
   {
     float2 o[NSIG][2][4];
 #pragma unroll
@@ -330,9 +376,9 @@ __device__ __forceinline__ void fft480_from(float2* const (&bufs)[NSIG], In in, 
     }
     rn_sync<NW>();
   }
-  fft_pass_n<NW, 8, 4, NSIG>(bufs, w960, lane);
-  fft_pass_n<NW, 3, 32, NSIG>(bufs, w960, lane);
-  fft_pass_n<NW, 5, 96, NSIG>(bufs, w960, lane);
+  fft_pass_n<NW, 8, 4, NSIG>(bufs, tab, lane);
+  fft_pass_n<NW, 3, 32, NSIG>(bufs, tab, lane);
+  fft_pass_n<NW, 5, 96, NSIG>(bufs, tab, lane);
 }
 
 // each buf holds Z = FFT480(x[2n] + i x[2n+1]); turn it into X[0..480] = DFT960(x)/960 in place (one set of table values
@@ -444,10 +490,13 @@ __device__ __forceinline__ float band_sum(const float* part_lo, const float* par
 #pragma unroll
   for (int k = 0; k < 6; ++k) s += k < n ? v[k] : 0.f;
   {
-    const float t1 = dpp_mov<0x101>(s);             // row_shl:1 -- the next lane's piece (0 past the row's end)
-    s += (bd >> 11) & 1 ? t1 : 0.f;
-    const float t2 = dpp_mov<0x102>(s);             // row_shl:2
-    s += (bd >> 12) & 1 ? t2 : 0.f;
+    // The GIVING lane masks its value (bits 11 / 12 as lane masks: a bit-field extract and an AND) and the shifted add is
+    // one v_add_f32_dpp.  With the flag in the taking lane -- `s += flag ? dpp_mov<row_shl:1>(s) : 0.f` -- the move could
+    // not fold into the add: a copy of zero, v_mov_b32_dpp, a test, a select and the add per step.  A lane that is given
+    // nothing adds +0 to a sum that is never -0 (it starts from +0): the same bits.
+    const int g1 = (bd << 20) >> 31, g2 = (bd << 19) >> 31;
+    s = dpp_add_of<0x101>(s, __int_as_float(__float_as_int(s) & g1));   // row_shl:1 -- the next lane's piece (0 past the row's end)
+    s = dpp_add_of<0x102>(s, __int_as_float(__float_as_int(s) & g2));   // row_shl:2
   }
   const float rise = __int_as_float(__builtin_amdgcn_ds_bpermute(((bd >> 13) & 63) << 2, __float_as_int(s)));
   const float fall = __int_as_float(__builtin_amdgcn_ds_bpermute(((bd >> 19) & 63) << 2, __float_as_int(s)));
@@ -851,20 +900,25 @@ __device__ __forceinline__ void gru_layer_i(__amdgpu_buffer_rsrc_t rs, int w_off
 //   A   analysis spectrum X / synthesis                (NW = 1 also: pitch-phase scratch -- x4|y4, fine xcorr, yy_lookup)
 //   Bb  pitch spectrum P, RNN vectors, band partials   (NW = 1 also: lp[864], the whitened half-rate buffer)
 //   U   band partial sums while A and Bb both hold spectra | Ly, tmp22, g, r
-// NW = 1 (one wave per stream): one slot + the cepstral ring + the GRU state = 10 192 bytes, 16 streams per CU.
+// NW = 1 (one wave per stream): one slot + the cepstral ring + the GRU state = 10 224 bytes, 16 streams per CU.
 // NW = 3 (stage pipeline, small stream counts): TWO slots (the spectra wave fills one while the synthesis wave empties
-// the other), the pitch wave's own scratch, and the pitch results of two frames in flight: 26.7 KB, 6 streams per CU.
+// the other), the pitch wave's own scratch, and the pitch results of two frames in flight: 27.0 KB, 6 streams per CU.
 // ---------------------------------------------------------------------------------------------
 struct alignas(16) RnSlot {
   float2 A[482];
-  float2 Bb[482];
-  float U[200];
-  float Ex[24], Ep[24], Exp[24];
+  float Ex[24], Ep[24];
   int pitch_index;       // NW = 3: handed from the spectra stage to the synthesis stage with the frame
   float pitch_gain;
   int silence;
-  int pad;
+  int pad[9];
+  // Bb starts a multiple of 256 bytes into the workgroup's LDS: the lag windows of the pitch search (lp = Bb, read 64
+  // floats apart) then pair into ds_read2st64_b32 with the window's distance in the offset fields; 16 bytes off, as it
+  // was behind A alone, every lag pointer took an extra add to reach such a multiple (40 per frame).
+  float2 Bb[482];
+  float U[200];
+  float Exp[24];
 };
+static_assert(offsetof(RnSlot, Bb) % 256 == 0, "lag windows in 256-byte steps");
 template <int NW> struct RnLdsT;
 template <> struct alignas(16) RnLdsT<1> {
   RnSlot s[1];
@@ -874,6 +928,7 @@ template <> struct alignas(16) RnLdsT<1> {
 template <> struct alignas(16) RnLdsT<3> {
   RnSlot s[2];           // by frame parity
   float2 pa[482];        // pitch stage: scratch
+  float pad[52];         // (pb at a multiple of 256 bytes, as Bb in the slot)
   float2 pb[482];        // pitch stage: lp[864]
   float ceps[8 * 22];
   float rnn_state[168];
@@ -882,6 +937,7 @@ template <> struct alignas(16) RnLdsT<3> {
 };
 static_assert(sizeof(RnLdsT<1>) <= 10240, "16 workgroups per CU need <= 10 KB of LDS each");
 static_assert(6 * sizeof(RnLdsT<3>) <= 160 * 1024, "six stage-pipelined streams per CU");
+static_assert(offsetof(RnLdsT<3>, pb) % 256 == 0, "lag windows in 256-byte steps");
 
 // offsets inside U outside band_sums (Ly is dead once the features exist: U[48, 192) is free for the gain network)
 constexpr int U_G = 0, U_R = 24, U_VAD = 46, U_LY = 48;
@@ -1557,16 +1613,20 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
       {
         const float* pp = pb + (768 - pitch_index);
         float2* const xp[2] = {SL.A, SL.Bb};
+        // (indices as 32-bit element offsets next to the scalar bases -- ld_u32 -- and the two window values of a point as
+        // one 8-byte load; `xw + 2 * n` scaled a 64-bit index and every base took a 64-bit vector add per trip)
+        const float2* hw2 = reinterpret_cast<const float2*>(hw);
         fft480_from<NW, 2>(xp, [&](int g, int j, int r) {
-          const int n = j + 120 * r;
-          const float w0 = r < 2 ? hw[2 * n] : hw[959 - 2 * n];
-          const float w1 = r < 2 ? hw[2 * n + 1] : hw[958 - 2 * n];
+          const unsigned n = (unsigned)j + 120u * r;
+          float w0, w1;
+          if (r < 2) { const float2 w = ld_u32(hw2, n); w0 = w.x; w1 = w.y; }            // hw[2n], hw[2n + 1]
+          else { const float2 w = ld_u32(hw2, 479u - n); w0 = w.y; w1 = w.x; }           // hw[959 - 2n], hw[958 - 2n]
           if (g == 0) {
-            const float2 v = *reinterpret_cast<const float2*>(xw + 2 * n);
+            const float2 v = ld_u32(reinterpret_cast<const float2*>(xw), n);
             return make_float2(v.x * w0, v.y * w1);
           }
-          return make_float2(pp[2 * n] * w0, pp[2 * n + 1] * w1);     // (pp is only 4-byte aligned)
-        }, w960, lane);
+          return make_float2(ld_u32(pp, 2u * n) * w0, ld_u32(pp, 2u * n + 1u) * w1);     // (pp is only 4-byte aligned)
+        }, tab, lane);
         real_fwd_post<NW, 2>(xp, w960, lane);
       }
       STAMP(5)
@@ -1876,7 +1936,7 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
       RN_LANE_RANGE(3);
       // ---- 10. frame_synthesis: inverse FFT, window, overlap-add ----
       real_inv_pre<NW>(SL.A, w960, lane);
-      fft480<NW>(SL.A, w960, lane);
+      fft480<NW>(SL.A, tab, lane);
       STAMP(12)
       {
         float* o = a.out + (long)t * a.stride_t + (long)b * a.stride_b;

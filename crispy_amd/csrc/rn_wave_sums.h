@@ -18,6 +18,23 @@ __device__ __forceinline__ float ws_dpp(float v) {
   const int iv = __float_as_int(v);
   return __int_as_float(__builtin_amdgcn_update_dpp(0, iv, CTRL, ROW_MASK, 0xf, false));
 }
+// The two steps that join the 16-lane rows: v += lane 15 of the row before (rows 1 and 3), then v += lane 31 (rows 2 and
+// 3); the rows a step does not name keep v.  Written as `v += ws_dpp<0x142, 0xa>(v)` a step was three instructions -- a
+// copy of zero for the rows that are masked off, v_mov_b32_dpp, v_add_f32: the DPP combiner folds a move with disabled
+// rows into its user only for integer operations.  v_add_f32_dpp with the destination as its own `old` is the same
+// sum in the rows that count (what leaves the reduction is read from lanes 31 and 63) in one instruction.  Inline
+// assembly stands outside the compiler's hazard bookkeeping, so the wait states are spelled out: five in front (a VALU
+// write of EXEC before a DPP instruction; a VALU write of the register itself needs two), one before the v_readlane
+// that follows.
+__device__ __forceinline__ float ws_join_rows(float v) {
+  asm("s_nop 4\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\ts_nop 0" : "+v"(v));
+  return v;
+}
+__device__ __forceinline__ float ws_join_row_pairs(float v) {      // rows 0 + 1 in lane 31, rows 2 + 3 in lane 63
+  asm("s_nop 4\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\ts_nop 0" : "+v"(v));
+  return v;
+}
 // first := [first.lanes 0-31 | second.lanes 0-31], second := [first.lanes 32-63 | second.lanes 32-63]
 __device__ __forceinline__ void ws_swap32(float& a, float& b) {
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
@@ -54,16 +71,12 @@ __device__ __forceinline__ void wave_sum4(float& a, float& b, float& c, float& d
 }
 __device__ __forceinline__ void wave_sum2(float& a, float& b) {
   ws_swap32(a, b);
-  float q = ws_rows(a + b);             // rows 0, 1: a; rows 2, 3: b
-  q += ws_dpp<0x142, 0xa>(q);           // row_bcast:15 into rows 1 and 3
+  const float q = ws_join_row_pairs(ws_rows(a + b));      // rows 0, 1: a; rows 2, 3: b
   a = ws_lane(q, 31);
   b = ws_lane(q, 63);
 }
 __device__ __forceinline__ float wave_sum1(float v) {
-  v = ws_rows(v);
-  v += ws_dpp<0x142, 0xa>(v);           // row_bcast:15 into rows 1 and 3
-  v += ws_dpp<0x143, 0xc>(v);           // row_bcast:31 into rows 2 and 3
-  return ws_lane(v, 63);
+  return ws_lane(ws_join_rows(ws_rows(v)), 63);
 }
 // v[i] := sum over the 64 lanes of v[i], wave-uniform, for all i < N
 template <int N>
