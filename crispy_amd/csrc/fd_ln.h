@@ -3,6 +3,7 @@
 // (whisper_dec_f16.hip): whichever kernel normalises a row, it runs these instructions, so the row's bits do not depend on it.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "wave_ops.h"
 
 namespace crispy {
 
@@ -26,14 +27,12 @@ __device__ __forceinline__ void fd_layernorm_wave(const float* xr, const float* 
   float e[PER], s = 0.f;
 #pragma unroll
   for (int q = 0; q < PER; ++q) { e[q] = xr[lane + 64 * q]; s += e[q]; }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = shfl_sum(s);
   const float mean = s / (float)D;
   float s2 = 0.f;
 #pragma unroll
   for (int q = 0; q < PER; ++q) { const float d = e[q] - mean; s2 = fmaf(d, d, s2); }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s2 += __shfl_xor(s2, off, 64);
+  s2 = shfl_sum(s2);
   const float rstd = 1.f / sqrtf(s2 / (float)D + 1e-5f);
 #pragma unroll
   for (int q = 0; q < PER; ++q) out[lane + 64 * q] = (_Float16)((e[q] - mean) * rstd * gb[lane + 64 * q] + gb[D + lane + 64 * q]);

@@ -3,10 +3,14 @@
 // workgroup-of-one-wave (or the caller's wave-local barrier) synchronises, every lane writes.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "wave_ops.h"
 
 namespace crispy {
 namespace fftx {
 
+// (A hand-scheduled two-instruction form -- v_pk_mul_f32 + v_pk_fma_f32 with op_sel / neg_lo -- removes 230 VALU
+// instructions per frame of the RNNoise frame kernel and measured 4 % SLOWER, round 2: that kernel is bound by dependent
+// chains, and a packed result has to be waited for before its first reader.)
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
   return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
@@ -22,13 +26,23 @@ __device__ __forceinline__ void butterfly<2>(const float2 (&v)[2], float2 (&o)[2
   o[1] = csub(v[0], v[1]);
 }
 template <>
+__device__ __forceinline__ void butterfly<3>(const float2 (&v)[3], float2 (&o)[3]) {
+  const float2 t = cadd(v[1], v[2]), d = csub(v[1], v[2]);
+  o[0] = cadd(v[0], t);
+  const float2 a = make_float2(v[0].x - 0.5f * t.x, v[0].y - 0.5f * t.y);
+  const float s = 0.86602540378443864676f;
+  const float2 b = make_float2(s * d.x, s * d.y);
+  o[1] = make_float2(a.x + b.y, a.y - b.x);  // a - i b
+  o[2] = make_float2(a.x - b.y, a.y + b.x);  // a + i b
+}
+template <>
 __device__ __forceinline__ void butterfly<4>(const float2 (&v)[4], float2 (&o)[4]) {
   const float2 s0 = cadd(v[0], v[2]), d0 = csub(v[0], v[2]);
   const float2 s1 = cadd(v[1], v[3]), d1 = csub(v[1], v[3]);
   o[0] = cadd(s0, s1);
   o[2] = csub(s0, s1);
-  o[1] = make_float2(d0.x + d1.y, d0.y - d1.x);
-  o[3] = make_float2(d0.x - d1.y, d0.y + d1.x);
+  o[1] = make_float2(d0.x + d1.y, d0.y - d1.x);  // d0 - i d1
+  o[3] = make_float2(d0.x - d1.y, d0.y + d1.x);  // d0 + i d1
 }
 template <>
 __device__ __forceinline__ void butterfly<5>(const float2 (&v)[5], float2 (&o)[5]) {
@@ -47,14 +61,22 @@ __device__ __forceinline__ void butterfly<5>(const float2 (&v)[5], float2 (&o)[5
   o[3] = make_float2(a2.x - b2.y, a2.y + b2.x);
 }
 
-// Wave-local barrier for LDS traffic of ONE wave inside a multi-wave workgroup: the wave runs in
-// lockstep and its LDS operations complete in order; the fence keeps the compiler from moving
-// LDS accesses across the point.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+template <>
+__device__ __forceinline__ void butterfly<8>(const float2 (&v)[8], float2 (&o)[8]) {
+  // two radix-4 transforms of the even / odd inputs, then the w8^k twiddles (1, (1-i)/sqrt2, -i, (-1-i)/sqrt2)
+  const float2 ev[4] = {v[0], v[2], v[4], v[6]}, od[4] = {v[1], v[3], v[5], v[7]};
+  float2 e[4], d[4];
+  butterfly<4>(ev, e);
+  butterfly<4>(od, d);
+  const float h = 0.70710678118654752f;
+  const float2 t0 = d[0];
+  const float2 t1 = make_float2((d[1].x + d[1].y) * h, (d[1].y - d[1].x) * h);
+  const float2 t2 = make_float2(d[2].y, -d[2].x);
+  const float2 t3 = make_float2((d[3].y - d[3].x) * h, -(d[3].x + d[3].y) * h);
+  o[0] = cadd(e[0], t0); o[4] = csub(e[0], t0);
+  o[1] = cadd(e[1], t1); o[5] = csub(e[1], t1);
+  o[2] = cadd(e[2], t2); o[6] = csub(e[2], t2);
+  o[3] = cadd(e[3], t3); o[7] = csub(e[3], t3);
 }
 
 // One Stockham pass of an N-point FFT: radix R, NS = product of the earlier radices.

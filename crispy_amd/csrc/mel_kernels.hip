@@ -179,8 +179,7 @@ __global__ __launch_bounds__(256) void mel_frames_kernel(MelArgs a) {
     }
     wave_lds_sync();
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, off, 64));
+  wmax = shfl_max(wmax);
   if (lane == 0) atomicMax(a.clip_max + b, float_order_key(wmax));
 }
 

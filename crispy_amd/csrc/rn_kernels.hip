@@ -17,7 +17,7 @@
 //
 // The analysis window [x_prev, x_cur] and the 1728-sample pitch buffer of the reference are both
 // windows of the same high-passed signal, so neither is stored as state: they are views of xhp.
-#include <type_traits>
+#include "fft_lds.h"
 #include "rn_common.h"
 #include "rn_prio.h"
 #include "rn_scale.h"
@@ -66,41 +66,12 @@ __device__ __forceinline__ void rn_prof_mark(float* p, int k) {
 
 __device__ __constant__ int c_second_check[16] = {0, 0, 3, 2, 3, 2, 5, 2, 3, 2, 3, 2, 5, 2, 3, 2};
 
-// (A hand-scheduled two-instruction form -- v_pk_mul_f32 + v_pk_fma_f32 with op_sel / neg_lo -- removes 230 VALU
-// instructions per frame and measured 4 % SLOWER, round 2: the frame kernel is bound by dependent chains, and a packed
-// result has to be waited for before its first reader.)
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-  return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y); }
+using fftx::butterfly;
+using fftx::cadd;
+using fftx::cconj;
+using fftx::cmul;
+using fftx::csub;
 
-// DPP lane permutations (gfx9 family): no LDS crossbar round trip, one VALU op per step.
-// (`old` = 0: passing the value itself -- legal for the quad / mirror permutations, whose every lane has a valid source --
-// ties the destination to the source register and cost 83 more copies than the zero-initialising moves it removed.)
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ float dpp_mov(float v) {
-  const int iv = __float_as_int(v);
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, iv, CTRL, ROW_MASK, 0xf, false));
-}
-// v + (v of the permuted lane) as ONE v_add_f32_dpp: the DPP combiner only folds a v_mov_b32_dpp into its user inside one
-// basic block, and the compiler likes to sink the add into a following `if (lane ...) store` -- then the move, its
-// zero-initialised destination and the add are three instructions.  Pinning the sum (an empty asm that "uses" it) keeps
-// the add where the move is.
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-  float r = v + dpp_mov<CTRL>(v);
-  asm volatile("" : "+v"(r));
-  return r;
-}
-// v + (u of the permuted lane; 0 where the pattern has no source lane), pinned like dpp_add
-template <int CTRL>
-__device__ __forceinline__ float dpp_add_of(float v, float u) {
-  float r = v + dpp_mov<CTRL>(u);
-  asm volatile("" : "+v"(r));
-  return r;
-}
 // v's lane `l` (a constant) := the wave-uniform s; the other lanes keep their value.  One v_writelane_b32 (the compiler has no
 // builtin for it); s comes from an SGPR -- a v_readlane result or scalar arithmetic -- and the lane select is an immediate.
 template <class V>
@@ -113,15 +84,6 @@ __device__ __forceinline__ void lane_put(V& v, V s, int l) {
 template <class T>
 __device__ __forceinline__ T ld_u32(const T* __restrict__ base, unsigned idx) {
   return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + idx * (unsigned)sizeof(T));
-}
-// sum over the 64 lanes, result uniform (read from lane 63 into an SGPR)
-__device__ __forceinline__ float wave_sum(float v) {
-  v += dpp_mov<0xB1>(v);        // quad_perm [1,0,3,2]
-  v += dpp_mov<0x4E>(v);        // quad_perm [2,3,0,1]
-  v += dpp_mov<0x141>(v);       // row_half_mirror
-  v += dpp_mov<0x140>(v);       // row_mirror: every lane of a 16-lane row holds the row sum
-  v = ws_join_rows(v);          // row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3 (rn_wave_sums.h)
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -137,68 +99,8 @@ __device__ __forceinline__ void rn_sync() {
   if constexpr (NW == 1) {
     __syncthreads();
   } else {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0)
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
   }
-}
-
-template <int R>
-__device__ __forceinline__ void butterfly(const float2 (&v)[R], float2 (&o)[R]);
-
-template <>
-__device__ __forceinline__ void butterfly<4>(const float2 (&v)[4], float2 (&o)[4]) {
-  const float2 s0 = cadd(v[0], v[2]), d0 = csub(v[0], v[2]);
-  const float2 s1 = cadd(v[1], v[3]), d1 = csub(v[1], v[3]);
-  o[0] = cadd(s0, s1);
-  o[2] = csub(s0, s1);
-  o[1] = make_float2(d0.x + d1.y, d0.y - d1.x);  // d0 - i d1
-  o[3] = make_float2(d0.x - d1.y, d0.y + d1.x);  // d0 + i d1
-}
-template <>
-__device__ __forceinline__ void butterfly<3>(const float2 (&v)[3], float2 (&o)[3]) {
-  const float2 t = cadd(v[1], v[2]), d = csub(v[1], v[2]);
-  o[0] = cadd(v[0], t);
-  const float2 a = make_float2(v[0].x - 0.5f * t.x, v[0].y - 0.5f * t.y);
-  const float s = 0.86602540378443864676f;
-  const float2 b = make_float2(s * d.x, s * d.y);
-  o[1] = make_float2(a.x + b.y, a.y - b.x);  // a - i b
-  o[2] = make_float2(a.x - b.y, a.y + b.x);  // a + i b
-}
-template <>
-__device__ __forceinline__ void butterfly<5>(const float2 (&v)[5], float2 (&o)[5]) {
-  const float c1 = 0.30901699437494742410f, s1 = 0.95105651629515357212f;
-  const float c2 = -0.80901699437494742410f, s2 = 0.58778525229247312917f;
-  const float2 t1 = cadd(v[1], v[4]), t2 = cadd(v[2], v[3]);
-  const float2 t3 = csub(v[1], v[4]), t4 = csub(v[2], v[3]);
-  o[0] = make_float2(v[0].x + t1.x + t2.x, v[0].y + t1.y + t2.y);
-  const float2 a1 = make_float2(v[0].x + c1 * t1.x + c2 * t2.x, v[0].y + c1 * t1.y + c2 * t2.y);
-  const float2 a2 = make_float2(v[0].x + c2 * t1.x + c1 * t2.x, v[0].y + c2 * t1.y + c1 * t2.y);
-  const float2 b1 = make_float2(s1 * t3.x + s2 * t4.x, s1 * t3.y + s2 * t4.y);
-  const float2 b2 = make_float2(s2 * t3.x - s1 * t4.x, s2 * t3.y - s1 * t4.y);
-  o[1] = make_float2(a1.x + b1.y, a1.y - b1.x);
-  o[4] = make_float2(a1.x - b1.y, a1.y + b1.x);
-  o[2] = make_float2(a2.x + b2.y, a2.y - b2.x);
-  o[3] = make_float2(a2.x - b2.y, a2.y + b2.x);
-}
-
-template <>
-__device__ __forceinline__ void butterfly<8>(const float2 (&v)[8], float2 (&o)[8]) {
-  // two radix-4 transforms of the even / odd inputs, then the w8^k twiddles (1, (1-i)/sqrt2, -i, (-1-i)/sqrt2)
-  const float2 ev[4] = {v[0], v[2], v[4], v[6]}, od[4] = {v[1], v[3], v[5], v[7]};
-  float2 e[4], d[4];
-  butterfly<4>(ev, e);
-  butterfly<4>(od, d);
-  const float h = 0.70710678118654752f;
-  const float2 t0 = d[0];
-  const float2 t1 = make_float2((d[1].x + d[1].y) * h, (d[1].y - d[1].x) * h);
-  const float2 t2 = make_float2(d[2].y, -d[2].x);
-  const float2 t3 = make_float2((d[3].y - d[3].x) * h, -(d[3].x + d[3].y) * h);
-  o[0] = cadd(e[0], t0); o[4] = csub(e[0], t0);
-  o[1] = cadd(e[1], t1); o[5] = csub(e[1], t1);
-  o[2] = cadd(e[2], t2); o[6] = csub(e[2], t2);
-  o[3] = cadd(e[3], t3); o[7] = csub(e[3], t3);
 }
 
 // Where element i of the Stockham sequence lives between two passes.  In natural order the stores of the first two
@@ -495,8 +397,8 @@ __device__ __forceinline__ float band_sum(const float* part_lo, const float* par
     // not fold into the add: a copy of zero, v_mov_b32_dpp, a test, a select and the add per step.  A lane that is given
     // nothing adds +0 to a sum that is never -0 (it starts from +0): the same bits.
     const int g1 = (bd << 20) >> 31, g2 = (bd << 19) >> 31;
-    s = dpp_add_of<0x101>(s, __int_as_float(__float_as_int(s) & g1));   // row_shl:1 -- the next lane's piece (0 past the row's end)
-    s = dpp_add_of<0x102>(s, __int_as_float(__float_as_int(s) & g2));   // row_shl:2
+    s = dpp_add_of_pinned<0x101>(s, __int_as_float(__float_as_int(s) & g1));   // row_shl:1 -- the next lane's piece (0 past the row's end)
+    s = dpp_add_of_pinned<0x102>(s, __int_as_float(__float_as_int(s) & g2));   // row_shl:2
   }
   const float rise = __int_as_float(__builtin_amdgcn_ds_bpermute(((bd >> 13) & 63) << 2, __float_as_int(s)));
   const float fall = __int_as_float(__builtin_amdgcn_ds_bpermute(((bd >> 19) & 63) << 2, __float_as_int(s)));
@@ -538,8 +440,8 @@ __device__ __forceinline__ void band_pairs(const float2* S, const float2* Xc, fl
       float e1 = sv.z * sv.z; e1 += sv.w * sv.w;
       float lo = (1.f - f.x) * e0 + (1.f - f.y) * e1;
       float hi = f.x * e0 + f.y * e1;
-      lo = dpp_add<0xB1>(lo);
-      hi = dpp_add<0xB1>(hi);
+      lo = dpp_add_pinned<0xB1>(lo);
+      hi = dpp_add_pinned<0xB1>(hi);
       if ((lane & 1) == 0) { part[pidx >> 1] = lo; part[100 + (pidx >> 1)] = hi; }
       if (CORR) {
         const float4 xv = *reinterpret_cast<const float4*>(Xc + 2 * pidx);
@@ -547,8 +449,8 @@ __device__ __forceinline__ void band_pairs(const float2* S, const float2* Xc, fl
         float c1 = xv.z * sv.z; c1 += xv.w * sv.w;
         float l2 = (1.f - f.x) * c0 + (1.f - f.y) * c1;
         float h2 = f.x * c0 + f.y * c1;
-        clo[m] = dpp_add<0xB1>(l2);
-        chi[m] = dpp_add<0xB1>(h2);
+        clo[m] = dpp_add_pinned<0xB1>(l2);
+        chi[m] = dpp_add_pinned<0xB1>(h2);
         if (XE) {
           // Every sum of two products here is one rounded product and one fused multiply-add; WHICH of the two is fused
           // is the compiler's choice under fp-contract, and it decides the last bit of Ex.  When X had a sweep of its
@@ -567,8 +469,8 @@ __device__ __forceinline__ void band_pairs(const float2* S, const float2* Xc, fl
             l3 = fmaf(1.f - f.x, x0, (1.f - f.y) * x1);
             h3 = fmaf(f.x, x0, f.y * x1);
           }
-          xlo[m] = dpp_add<0xB1>(l3);
-          xhi[m] = dpp_add<0xB1>(h3);
+          xlo[m] = dpp_add_pinned<0xB1>(l3);
+          xhi[m] = dpp_add_pinned<0xB1>(h3);
         }
         if (park) *reinterpret_cast<float4*>(park + 2 * pidx) = sv;
       }
@@ -647,7 +549,6 @@ __device__ __forceinline__ float sigmoid_approx(float x, const TansigTab& table)
   return .5f + .5f * tansig_approx(.5f * x, table);
 }
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 // After the lane id has been laundered its range is unknown, every `table[lane + 64 k]` index is sign-extended and
 // the load takes a 64-bit VGPR address (ashr + 64-bit shift-add per load).  Stating the range lets the sign extension
 // fold away: SGPR base + 32-bit lane offset + immediate.
@@ -664,7 +565,7 @@ __device__ __forceinline__ float dot_vad(__amdgpu_buffer_rsrc_t rs, int w_off, c
   float acc = acc0, acc1 = 0.f;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const h8 w = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(rs, 0, (w_off + k) * 16, 0));
+    const half8 w = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rs, 0, (w_off + k) * 16, 0));
 #pragma unroll
     for (int e = 0; e < 8; e += 2) {
       acc = fmaf((float)w[e], x[8 * k + e], acc);
@@ -692,15 +593,11 @@ constexpr int RN_IMG8_LD = 144;   // bytes per digit image (K <= 128), +16: the 
 // bit patterns simply compare as large numbers (scale_of clamps the exponent).
 __device__ __forceinline__ float wave_max(float v) {
   unsigned u = __float_as_uint(v);
-  auto dm = [](unsigned x, auto ctrl) {
-    // old = 0 with all rows and banks enabled: the combiner folds move + maximum into one v_max_u32_dpp (with old = x
-    // it cannot -- x is not the identity of the operation -- and each step was a copy, a DPP move and the maximum)
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, decltype(ctrl)::value, 0xf, 0xf, false);
-  };
-  u = max(u, dm(u, std::integral_constant<int, 0xB1>{}));
-  u = max(u, dm(u, std::integral_constant<int, 0x4E>{}));
-  u = max(u, dm(u, std::integral_constant<int, 0x141>{}));
-  u = max(u, dm(u, std::integral_constant<int, 0x140>{}));      // every lane of a 16-lane row holds the row maximum
+  // dpp_mov's old = 0 lets the combiner fold move + maximum into one v_max_u32_dpp (wave_ops.h)
+  u = max(u, (unsigned)dpp_mov<0xB1>((int)u));
+  u = max(u, (unsigned)dpp_mov<0x4E>((int)u));
+  u = max(u, (unsigned)dpp_mov<0x141>((int)u));
+  u = max(u, (unsigned)dpp_mov<0x140>((int)u));      // every lane of a 16-lane row holds the row maximum
   unsigned m = (unsigned)__builtin_amdgcn_readlane((int)u, 0);
   // scalar maxima (s_max_u32), kept apart: two nested ones are combined into a v_max3_u32, which has no scalar form
   m = max(m, (unsigned)__builtin_amdgcn_readlane((int)u, 16));
@@ -1385,7 +1282,7 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
           c1 = cand_pick(b0, c0, cand_pick(b1, c, c1));
           c0 = cand_pick(b0, c, c0);
         }
-        const int total_valid = __popcll(__ballot(nvalid > 0)) == 0 ? 0 : (int)wave_sum((float)nvalid);
+        const int total_valid = __popcll(__ballot(nvalid > 0)) == 0 ? 0 : (int)wave_sum1((float)nvalid);
         const int half_addr = (lane ^ 32) << 2;
         const Cand w0 = wave_best(c0, half_addr);
         const Cand mine = (c0.idx == w0.idx) ? c1 : c0;   // the winner's lane offers its runner-up
@@ -1738,7 +1635,7 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
           md = fminf(md, dpp_mov<0xB1>(md));     // quad_perm [1,0,3,2]
           md = fminf(md, dpp_mov<0x4E>(md));     // quad_perm [2,3,0,1]
           md = fminf(md, dpp_mov<0x141>(md));    // row_half_mirror: the other quad of the group of 8
-          const float sv = wave_sum(md) * .125f;
+          const float sv = wave_sum1(md) * .125f;
           if (lane == 0) Rb[KB_FEAT + 41] = sv / 8.f - 2.1f;
         }
         rn_sync<NW>();
@@ -1862,8 +1759,8 @@ __device__ __forceinline__ void rn_frame_body(const RnArgs& a) {
               float e1 = x.z * x.z; e1 += x.w * x.w;
               float lo = (1.f - fq[m].x) * e0 + (1.f - fq[m].y) * e1;
               float hi = fq[m].x * e0 + fq[m].y * e1;
-              lo = dpp_add<0xB1>(lo);        // the other pair of this 4-bin chunk sits in the neighbouring lane
-              hi = dpp_add<0xB1>(hi);
+              lo = dpp_add_pinned<0xB1>(lo);        // the other pair of this 4-bin chunk sits in the neighbouring lane
+              hi = dpp_add_pinned<0xB1>(hi);
               if ((lane & 1) == 0) { part[pidx >> 1] = lo; part_hi[pidx >> 1] = hi; }
             }
           }

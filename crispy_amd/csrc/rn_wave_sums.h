@@ -1,25 +1,21 @@
 // rn_wave_sums.h -- several wave-wide sums for the price of one (gfx950, wave64).
 //
-// A lone wave sum is six dependent cross-lane steps (rn_kernels.hip: wave_sum) and the frame kernel takes ~62 of them per
+// A lone wave sum is six dependent cross-lane steps (wave_sum1 below) and the frame kernel takes ~62 of them per
 // frame (the lag inner products of the pitch search, the LPC autocorrelation): ~560 VALU instructions, 7 % of the frame.
 // Here N values are reduced TOGETHER: v_permlane32_swap puts the lower halves of two values into one register and their
 // upper halves into another -- one add folds both values to 32 lanes --, v_permlane16_swap does the same with the odd /
-// even 16-lane rows of two such registers, and four DPP steps finish the four rows at once.  Four sums: 3 swaps + 3 adds +
+// even 16-lane rows of two such registers, and four DPP steps (row_sum16, wave_ops.h) finish the four rows at once.  Four sums: 3 swaps + 3 adds +
 // 4 DPP adds + 4 v_readlane instead of 4 x (6 steps + v_readlane).  The association of the additions differs from the
 // single form (lanes l and l + 32 first); both are trees, neither is the reference's sequential order.
 // Lane semantics checked on the hardware by tools/micro/wave_sum4_test.hip.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "wave_ops.h"
 
 namespace crispy {
 
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ float ws_dpp(float v) {
-  const int iv = __float_as_int(v);
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, iv, CTRL, ROW_MASK, 0xf, false));
-}
 // The two steps that join the 16-lane rows: v += lane 15 of the row before (rows 1 and 3), then v += lane 31 (rows 2 and
-// 3); the rows a step does not name keep v.  Written as `v += ws_dpp<0x142, 0xa>(v)` a step was three instructions -- a
+// 3); the rows a step does not name keep v.  Written as `v += dpp_mov<0x142, 0xa>(v)` a step was three instructions -- a
 // copy of zero for the rows that are masked off, v_mov_b32_dpp, v_add_f32: the DPP combiner folds a move with disabled
 // rows into its user only for integer operations.  v_add_f32_dpp with the destination as its own `old` is the same
 // sum in the rows that count (what leaves the reduction is read from lanes 31 and 63) in one instruction.  Inline
@@ -47,13 +43,6 @@ __device__ __forceinline__ void ws_swap16(float& a, float& b) {
   a = __uint_as_float(r[0]);
   b = __uint_as_float(r[1]);
 }
-__device__ __forceinline__ float ws_rows(float q) {     // every lane of a 16-lane row ends up with the row's sum
-  q += ws_dpp<0xB1>(q);         // quad_perm [1,0,3,2]
-  q += ws_dpp<0x4E>(q);         // quad_perm [2,3,0,1]
-  q += ws_dpp<0x141>(q);        // row_half_mirror
-  q += ws_dpp<0x140>(q);        // row_mirror
-  return q;
-}
 __device__ __forceinline__ float ws_lane(float v, int l) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
@@ -63,7 +52,7 @@ __device__ __forceinline__ void wave_sum4(float& a, float& b, float& c, float& d
   ws_swap32(c, d);
   float cd = c + d;
   ws_swap16(ab, cd);
-  const float q = ws_rows(ab + cd);     // row 0: a, row 1: c, row 2: b, row 3: d
+  const float q = row_sum16(ab + cd);     // row 0: a, row 1: c, row 2: b, row 3: d
   a = ws_lane(q, 0);
   c = ws_lane(q, 16);
   b = ws_lane(q, 32);
@@ -71,12 +60,12 @@ __device__ __forceinline__ void wave_sum4(float& a, float& b, float& c, float& d
 }
 __device__ __forceinline__ void wave_sum2(float& a, float& b) {
   ws_swap32(a, b);
-  const float q = ws_join_row_pairs(ws_rows(a + b));      // rows 0, 1: a; rows 2, 3: b
+  const float q = ws_join_row_pairs(row_sum16(a + b));      // rows 0, 1: a; rows 2, 3: b
   a = ws_lane(q, 31);
   b = ws_lane(q, 63);
 }
 __device__ __forceinline__ float wave_sum1(float v) {
-  return ws_lane(ws_join_rows(ws_rows(v)), 63);
+  return ws_lane(ws_join_rows(row_sum16(v)), 63);
 }
 // v[i] := sum over the 64 lanes of v[i], wave-uniform, for all i < N
 template <int N>

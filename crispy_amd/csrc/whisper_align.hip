@@ -18,6 +18,7 @@
 //      lane walks the backtrace and records where the path enters every row.
 // Nothing reduces across clips: a clip's alignment is its own whatever the batch.
 #include "whisper_internal.h"
+#include "wave_ops.h"
 
 namespace crispy {
 namespace asr {
@@ -59,12 +60,6 @@ struct AlignArgs {
   float* probs;             // nullable [batch][n_heads][ld_rows][ld_f]
   int ld_rows, ld_f;
 };
-
-__device__ __forceinline__ void lds_bar() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 // one cross-attention score: q . k / 8, the products in dimension order (the row statistics and the matrix kernel call
 // the same function, so a score has the same bits in both)
@@ -126,9 +121,9 @@ __global__ __launch_bounds__(256) void align_rowstats_kernel(AlignArgs a) {
     float m = -INFINITY, l = 0.f;
     for (int k0 = 0; k0 < c.n_keys; k0 += 64) {
       const int nk = min(64, c.n_keys - k0);
-      lds_bar();
+      lds_barrier();
       for (int e = threadIdx.x; e < nk * 16; e += 256) stage_k(a, b, hh, k0 + e / 16, e % 16, ks + (e / 16) * kHd);
-      lds_bar();
+      lds_barrier();
       if (live) {
         for (int k = 0; k < nk; ++k) {
           const float s = score(q, ks + k * kHd);
@@ -170,7 +165,7 @@ __global__ __launch_bounds__(256) void align_matrix_kernel(AlignArgs a) {
   float* mu = acc + (size_t)R * kTile;              // [kSpan]
   float* sd = mu + kSpan;                           // [kSpan]
   for (int hh = 0; hh < a.n_heads; ++hh) {
-    lds_bar();                                      // the previous head's readers are done with ks / P / mu / sd
+    lds_barrier();                                  // the previous head's readers are done with ks / P / mu / sd
     for (int e = threadIdx.x; e < kSpan * 16; e += 256) {
       int g = f0 - kHalo + e / 16;                  // reflect padding of the cropped range (torch's mode="reflect")
       if (g < 0) g = -g;
@@ -180,7 +175,7 @@ __global__ __launch_bounds__(256) void align_matrix_kernel(AlignArgs a) {
       g = min(max(g, 0), F - 1);
       stage_k(a, b, hh, g, e % 16, ks + (e / 16) * kHd);
     }
-    lds_bar();
+    lds_barrier();
     for (int r = threadIdx.x; r < R; r += 256) {
       float q[kHd];
       load_q(a, b, hh, r, q);
@@ -193,7 +188,7 @@ __global__ __launch_bounds__(256) void align_matrix_kernel(AlignArgs a) {
         if (prow && t >= kHalo && t < kHalo + kTile && f < F) prow[f] = p;
       }
     }
-    lds_bar();
+    lds_barrier();
     if (threadIdx.x < kSpan) {                      // standardise every frame over the token rows
       const int t = threadIdx.x;
       float s = 0.f;
@@ -204,7 +199,7 @@ __global__ __launch_bounds__(256) void align_matrix_kernel(AlignArgs a) {
       mu[t] = mean;
       sd[t] = sqrtf(v / (float)R);
     }
-    lds_bar();
+    lds_barrier();
     for (int e = threadIdx.x; e < R * kTile; e += 256) {
       const int r = e / kTile, u = e % kTile;
       const float* pr = P + r * kSpan + u;
@@ -215,7 +210,7 @@ __global__ __launch_bounds__(256) void align_matrix_kernel(AlignArgs a) {
       acc[e] = hh == 0 ? med : acc[e] + med;
     }
   }
-  lds_bar();
+  lds_barrier();
   for (int e = threadIdx.x; e < R * kTile; e += 256) {
     const int r = e / kTile, u = e % kTile, f = f0 + u;
     if (f < F) a.matrix[((long)b * a.ld_rows + r) * a.ld_f + f] = acc[e] / (float)a.n_heads;
@@ -285,7 +280,7 @@ __global__ __launch_bounds__(kDtwMaxRows) void align_dtw_kernel(DtwArgs a) {
         tw |= t << (2 * ((j - 1) & 15));
         if (((j - 1) & 15) == 15 || j == M) { trace[(size_t)(i - 1) * W + (j - 1) / 16] = tw; tw = 0; }
       }
-      lds_bar();
+      lds_barrier();
     }
   }
   __shared__ int n_jb;
@@ -312,7 +307,7 @@ __global__ __launch_bounds__(kDtwMaxRows) void align_dtw_kernel(DtwArgs a) {
     n_jb = nj;
     if (a.n_path) a.n_path[b] = n;
   }
-  lds_bar();
+  lds_barrier();
   const int nj = n_jb;
   for (int k = threadIdx.x; k < N && k < nj; k += blockDim.x) a.jumps[b * a.ld_jumps + k] = jb[nj - 1 - k];
 }

@@ -15,6 +15,7 @@
 // on which of them the launcher picks.  (The fused and matrix-vector decode paths have attention kernels of their own:
 // whisper_dec_fused.hip, whisper_dec_gemv.hip.)
 #include "asr_common.h"
+#include "wave_ops.h"
 
 namespace crispy {
 namespace {
@@ -126,10 +127,7 @@ __global__ __launch_bounds__(256) void attn_enc_kernel(const float* __restrict__
     st[li * 65 + d] = o0[r] * inv;
     st[li * 65 + 32 + d] = o1[r] * inv;
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   for (int idx = lane; idx < 32 * 64; idx += 64) {
     const int q = idx >> 6, d = idx & 63;
     if (q0 + q < T) out[((long)b * T + q0 + q) * D + h * 64 + d] = st[q * 65 + d];
@@ -156,12 +154,10 @@ template <> __device__ __forceinline__ float4 ld4<float, true>(const float* p) {
   return make_float4(v[0], v[1], v[2], v[3]);
 }
 template <> __device__ __forceinline__ float4 ld4<_Float16, false>(const _Float16* p) {
-  typedef _Float16 half4 __attribute__((ext_vector_type(4)));
   const half4 h = *reinterpret_cast<const half4*>(p);
   return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
 }
 template <> __device__ __forceinline__ float4 ld4<_Float16, true>(const _Float16* p) {
-  typedef _Float16 half4 __attribute__((ext_vector_type(4)));
   const half4 h = __builtin_nontemporal_load(reinterpret_cast<const half4*>(p));
   return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
 }
@@ -219,10 +215,7 @@ __global__ __launch_bounds__(64 * AD_WAVES) void attn_dec_kernel(const float* __
 #pragma unroll
       for (int u = 0; u < SU; ++u) {
         float v = sacc[u];
-        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false));
-        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, false));
-        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false));
-        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, false));
+        v = row_sum16(v);
         const int k = kb + 4 * u + sub;
         if (k < k_hi) {
           if (c == 0) p_s[k] = v;
@@ -231,10 +224,7 @@ __global__ __launch_bounds__(64 * AD_WAVES) void attn_dec_kernel(const float* __
       }
     }
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) mloc = fmaxf(mloc, __shfl_xor(mloc, off, 64));
   float lsum = 0.f;
@@ -245,10 +235,7 @@ __global__ __launch_bounds__(64 * AD_WAVES) void attn_dec_kernel(const float* __
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) lsum += __shfl_xor(lsum, off, 64);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   // P.V with the same access shape as the scores: 16 lanes share one 256-byte V row (4 dims each), 4 rows per wave
   // instruction, SU instructions (8 KB) in flight per wave -- the one-float-per-lane version kept 2 KB in flight and
   // spent most of the kernel waiting on it.  The four key residues are summed across the DPP rows at the end.
@@ -326,7 +313,6 @@ __global__ __launch_bounds__(64 * AD_WAVES) void attn_dec_x16_kernel(const float
   const int clip = b / rows.group;
   const int k_off = rows.key_off ? rows.key_off[clip] : 0;       // see attn_dec_kernel
   const int n_keys = n_keys_base + (pos_dev ? *pos_dev : 0) + rows.key_step * (b % rows.group) - k_off;
-  typedef _Float16 half8 __attribute__((ext_vector_type(8)));
   __shared__ __attribute__((aligned(16))) float part_o[AD_WAVES][64];
   __shared__ float part_m[AD_WAVES], part_l[AD_WAVES];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -379,15 +365,12 @@ __global__ __launch_bounds__(64 * AD_WAVES) void attn_dec_x16_kernel(const float
     float v = (float)kr[i][0] * qv[0];
 #pragma unroll
     for (int e = 1; e < 8; ++e) v = fmaf((float)kr[i][e], qv[e], v);
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false));    // lanes ^ 1
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, false));    // lanes ^ 2
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false));   // the other quad of the 8
+    v = row_sum8(v);       // the 8 lanes of a key row
     const bool valid = k_lo + 8 * i + r < k_hi;
     sc[i] = valid ? v : -1e30f;
     mloc = fmaxf(mloc, sc[i]);
   }
-#pragma unroll
-  for (int off = 8; off <= 32; off <<= 1) mloc = fmaxf(mloc, __shfl_xor(mloc, off, 64));
+  mloc = shfl_max<8, 32>(mloc);
   float lsum = 0.f;
   float acc[8];
 #pragma unroll
@@ -464,7 +447,6 @@ __global__ __launch_bounds__(64 * AD_WAVES) void attn_dec_x16g_kernel(const floa
                                                                       long kv_batch_stride, long ldkv, long head_stride, long koff, long voff,
                                                                       int n_keys, float* __restrict__ out, long ldo, AttnRows rows) {
   constexpr int SL = 12;
-  typedef _Float16 half8 __attribute__((ext_vector_type(8)));
   __shared__ __attribute__((aligned(16))) float part_o[ADG_ROWS][AD_WAVES][64];
   __shared__ float part_m[ADG_ROWS][AD_WAVES], part_l[ADG_ROWS][AD_WAVES];
   __shared__ float wave_m[ADG_ROWS][AD_WAVES], wave_l[ADG_ROWS][AD_WAVES];
@@ -507,15 +489,12 @@ __global__ __launch_bounds__(64 * AD_WAVES) void attn_dec_x16g_kernel(const floa
       float v = (float)kr[i][0] * qv[0];
 #pragma unroll
       for (int e = 1; e < 8; ++e) v = fmaf((float)kr[i][e], qv[e], v);
-      v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false));
-      v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, false));
-      v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, false));
+      v = row_sum8(v);       // the 8 lanes of a key row
       const float sc = k_lo + 8 * i + r < k_hi ? v : -1e30f;
       if (c == 0) sc_s[j][wave][i][r] = sc;
       mloc = fmaxf(mloc, sc);
     }
-#pragma unroll
-    for (int off = 8; off <= 32; off <<= 1) mloc = fmaxf(mloc, __shfl_xor(mloc, off, 64));
+    mloc = shfl_max<8, 32>(mloc);
     if (lane == 0) wave_m[j][wave] = mloc;
   }
   // the values, into the registers the keys leave

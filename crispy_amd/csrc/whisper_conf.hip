@@ -10,22 +10,12 @@
 // a row's result depends on the row alone, never on the rows launched with it.
 // decode_steps.cpp reaches the two launchers through a table this file installs at static initialisation (g_conf_kernels).
 #include "whisper_internal.h"
+#include "wave_ops.h"
 
 namespace crispy {
 namespace {
 
 constexpr int kLpThreads = 1024, kLpWaves = kLpThreads / 64;
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // grid (rows), 1024 threads.  Row r of the launch is position pos + r % P of clip r / P (the rows of a multi-position prompt
 // step); its target and its result live at [clip][ld_t] + position.  target < 0: the row has nothing to predict (left padding,
@@ -48,7 +38,7 @@ __global__ __launch_bounds__(kLpThreads) void tok_logprob_kernel(const float* __
     m = fmaxf(fmaxf(m, fmaxf(x.x, x.y)), fmaxf(x.z, x.w));
   }
   if (tid < n_cols - 4 * n4) m = fmaxf(m, lg[4 * n4 + tid]);
-  m = wave_max(m);
+  m = shfl_max(m);
   if ((tid & 63) == 0) s_r[tid >> 6] = m;
   __syncthreads();
   m = s_r[0];
@@ -61,7 +51,7 @@ __global__ __launch_bounds__(kLpThreads) void tok_logprob_kernel(const float* __
     sum += (expf(x.x - m) + expf(x.y - m)) + (expf(x.z - m) + expf(x.w - m));
   }
   if (tid < n_cols - 4 * n4) sum += expf(lg[4 * n4 + tid] - m);
-  sum = wave_sum(sum);
+  sum = shfl_sum(sum);
   if ((tid & 63) == 0) s_r[tid >> 6] = sum;
   __syncthreads();
   if (tid == 0) {
@@ -81,10 +71,10 @@ __global__ __launch_bounds__(256) void lang_probs_kernel(const float* __restrict
   const float* lg = logits + (long)r * ld + lang0;
   const float a = lane < n_lang ? lg[lane] : -INFINITY;
   const float b = lane + 64 < n_lang ? lg[lane + 64] : -INFINITY;
-  const float m = wave_max(fmaxf(a, b));
+  const float m = shfl_max(fmaxf(a, b));
   const float ea = lane < n_lang ? expf(a - m) : 0.f;
   const float eb = lane + 64 < n_lang ? expf(b - m) : 0.f;
-  const float tot = wave_sum(ea + eb);
+  const float tot = shfl_sum(ea + eb);
   if (lane < n_lang) probs[(long)r * n_lang + lane] = ea / tot;
   if (lane + 64 < n_lang) probs[(long)r * n_lang + lane + 64] = eb / tot;
 }

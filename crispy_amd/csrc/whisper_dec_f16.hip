@@ -15,14 +15,12 @@
 // per tile.
 #include "asr_common.h"
 #include "fd_ln.h"
+#include "wave_ops.h"
 
 namespace crispy {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // dst[((t * KC + kc) * 64 + lane) * 8 + e] = f16(E[32 t + (lane & 31)][16 kc + 8 (lane >> 5) + e]), rows >= V zero
 __global__ __launch_bounds__(256) void pack_vocab_kernel(const float* __restrict__ E, _Float16* __restrict__ dst, int V, int K,

@@ -40,12 +40,11 @@
 // hidden units rounded to f16 against f16 weights.  Oracle: oracle/whisper_oracle.py DecoderCache(f16=True, ln16=True).
 #include "asr_common.h"
 #include "fd_ln.h"
+#include "wave_ops.h"
 
 namespace crispy {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -59,22 +58,6 @@ __device__ __forceinline__ float dot8(const half8 a, const half8 b, float acc) {
   for (int i = 0; i < 4; ++i)
     acc = __builtin_amdgcn_fdot2(half2v{a[2 * i], a[2 * i + 1]}, half2v{b[2 * i], b[2 * i + 1]}, acc, false);
   return acc;
-}
-template <int CTRL> __device__ __forceinline__ float dpp_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-// sum over the 8 / 16 lanes that share a row (every one of them ends up with the total)
-__device__ __forceinline__ float sum8(float v) { return dpp_add<0x141>(dpp_add<0x4E>(dpp_add<0xB1>(v))); }
-__device__ __forceinline__ float sum16(float v) { return dpp_add<0x140>(sum8(v)); }
-
-// Workgroup barrier for LDS traffic ONLY: __syncthreads() waits for every outstanding vector-memory operation first
-// (s_waitcnt vmcnt(0)), i.e. the first barrier of a kernel would wait for all the weights and keys requested at its top
-// and serialise exactly the overlap these kernels are built on (measured: a row's pass through the MLP block cost ~3 us
-// with the next row's residual stream "in flight").  Nothing in these kernels hands GLOBAL data from wave to wave.
-__device__ __forceinline__ void fd_bar() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
 // a load from a workgroup-uniform base (scalar registers) + a 32-bit byte offset per lane: one address register instead of
@@ -139,10 +122,10 @@ struct FdInput {
         if (writer && row0 + r < rows) in.x_out[(long)(row0 + r) * D + col] = x;
       }
     }
-    fd_bar();
+    lds_barrier();
     const int wave = tid >> 6, lane = tid & 63;
     if (wave < RB) fd_layernorm_wave<D>(xs + wave * D, gb, xn + wave * XLD, lane);
-    fd_bar();
+    lds_barrier();
   }
 };
 
@@ -163,7 +146,7 @@ struct HeadOut {
     const half8 a = *reinterpret_cast<const half8*>(att_h + 8 * (lane & 7));
 #pragma unroll
     for (int p = 0; p < NPASS; ++p) {
-      const float v = sum8(dot8(w[p], a, 0.f));
+      const float v = row_sum8(dot8(w[p], a, 0.f));
       if ((lane & 7) == 0) po[128 * p + 8 * wave + (lane >> 3)] = v;
     }
   }
@@ -220,14 +203,13 @@ __device__ __forceinline__ void fd_attend(const half8 (&kr)[SLOTS], half8 (&vr)[
     float v = (float)kr[i][0] * qv[0];
 #pragma unroll
     for (int e = 1; e < 8; ++e) v = fmaf((float)kr[i][e], qv[e], v);
-    v = sum8(v);
+    v = row_sum8(v);
     const bool valid = k_lo + 8 * i + r < k_hi;
     sc[i] = valid ? v : -1e30f;
     mloc = fmaxf(mloc, sc[i]);
   }
   after_scores();
-#pragma unroll
-  for (int off = 8; off <= 32; off <<= 1) mloc = fmaxf(mloc, __shfl_xor(mloc, off, 64));
+  mloc = shfl_max<8, 32>(mloc);
   float lsum = 0.f;
   float acc[8];
 #pragma unroll
@@ -235,7 +217,7 @@ __device__ __forceinline__ void fd_attend(const half8 (&kr)[SLOTS], half8 (&vr)[
   float inv16 = 0.f;
   if (attn16) {                 // the soft-max in full, normalised, THEN rounded (ggml's P.V operand): needs the row's maximum and sum first
     if (lane == 0) part_m[wave] = mloc;
-    fd_bar();
+    lds_barrier();
     float m = part_m[0];
 #pragma unroll
     for (int w = 1; w < FD_WAVES; ++w) m = fmaxf(m, part_m[w]);
@@ -246,12 +228,12 @@ __device__ __forceinline__ void fd_attend(const half8 (&kr)[SLOTS], half8 (&vr)[
 #pragma unroll
     for (int off = 8; off <= 32; off <<= 1) ls += __shfl_xor(ls, off, 64);
     if (lane == 0) part_l[wave] = ls;
-    fd_bar();
+    lds_barrier();
     float l = 0.f;
 #pragma unroll
     for (int w = 0; w < FD_WAVES; ++w) l += part_l[w];
     inv16 = 1.f / l;
-    fd_bar();
+    lds_barrier();
   }
 #pragma unroll
   for (int i = 0; i < SLOTS; ++i) {
@@ -274,9 +256,9 @@ __device__ __forceinline__ void fd_attend(const half8 (&kr)[SLOTS], half8 (&vr)[
   }
   if (lane == 0) { part_m[wave] = mloc; part_l[wave] = lsum; }
   if (MERGE) {
-    fd_bar();
+    lds_barrier();
     if (wave == 0) fd_merge(part_o, part_m, part_l, attn16, att_h);
-    fd_bar();
+    lds_barrier();
   }
 }
 
@@ -382,11 +364,11 @@ __global__ __launch_bounds__(FD_THREADS) void fused_self_kernel(FusedSelfArgs a)
       *reinterpret_cast<f32x4*>(&q_s[n16][j0]) = acc + bias4;
     } else {
       const f32x4 v = acc + bias4;
-      *reinterpret_cast<half4v*>(&kv_new[n16][64 * (p - 1) + j0]) = half4v{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+      *reinterpret_cast<half4*>(&kv_new[n16][64 * (p - 1) + j0]) = half4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
     }
   }
   if (LATE) { __builtin_amdgcn_sched_barrier(0); request_kv(); }
-  fd_bar();
+  lds_barrier();
   // the cache rows of this position: 8 + 8 sixteen-byte pieces per row
   if (tid < 16 * RB) {
     const int rb = tid >> 4, t = tid & 15;
@@ -407,9 +389,9 @@ __global__ __launch_bounds__(FD_THREADS) void fused_self_kernel(FusedSelfArgs a)
     }
     fd_attend<SLOTS, false>(kr[rb], vr[rb], q_s[rb], k_lo[rb], k_hi[rb], a.attn16, part_o[rb], part_m[rb], part_l[rb], att_h[rb], [] {}, [] {});
   }
-  fd_bar();                                                            // the partials of every row: one barrier, then row r's merge on wave r
+  lds_barrier();                                                            // the partials of every row: one barrier, then row r's merge on wave r
   if (wave < RB) fd_merge(part_o[wave], part_m[wave], part_l[wave], a.attn16, att_h[wave]);
-  fd_bar();
+  lds_barrier();
   // (5) this head's share of the output projection, every row: waves 12 - 15
   if (wave >= 12) {
     if (LATE_WO) request_wo();
@@ -422,7 +404,7 @@ __global__ __launch_bounds__(FD_THREADS) void fused_self_kernel(FusedSelfArgs a)
       if (n16 < RB) *reinterpret_cast<f32x4*>(po + n16 * D + 16 * (OT * (wave - 12) + j) + 4 * kq) = acc;
     }
   }
-  fd_bar();
+  lds_barrier();
   fd_store_partial<D, RB>(po, a.part_out, a.rows, row0, h);
 }
 
@@ -489,10 +471,10 @@ __global__ __launch_bounds__(FD_THREADS) void fused_cross_kernel(FusedCrossArgs 
     float v = 0.f;
 #pragma unroll
     for (int j = 0; j < PPL; ++j) v = dot8(wq[j], *reinterpret_cast<const half8*>(xn + 8 * c + 128 * j), v);
-    v = sum16(v) + bq;
+    v = row_sum16(v) + bq;
     if (c == 0) q_s[jrow] = v;
   }
-  fd_bar();
+  lds_barrier();
   HeadOut<D> ho;
   fd_attend<FX_SLOTS>(kr, vr, q_s, k_lo, k_hi, a.attn16, part_o, part_m, part_l, att_h,
                       [&] {
@@ -506,7 +488,7 @@ __global__ __launch_bounds__(FD_THREADS) void fused_cross_kernel(FusedCrossArgs 
                       },
                       [&] { ho.request(a.wo, h * 64); });
   ho.finish(att_h, po);
-  fd_bar();
+  lds_barrier();
   fd_store_partial<D, 1>(po, a.part_out, a.rows, row, h);
 }
 
@@ -553,10 +535,10 @@ __global__ __launch_bounds__(FD_THREADS) void fused_mlp_kernel(FusedMlpArgs a) {
     for (int s2 = 0; s2 < KS; ++s2)
       acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[s2], *reinterpret_cast<const half8*>(xn + n16 * XLD + 32 * s2 + 8 * kq), acc, 0, 0, 0);
     const f32x4 v = acc + bias4;
-    *reinterpret_cast<half4v*>(&hh[n16][16 * wave + 4 * kq]) =
-        half4v{(_Float16)gelu_ggml(v[0]), (_Float16)gelu_ggml(v[1]), (_Float16)gelu_ggml(v[2]), (_Float16)gelu_ggml(v[3])};
+    *reinterpret_cast<half4*>(&hh[n16][16 * wave + 4 * kq]) =
+        half4{(_Float16)gelu_ggml(v[0]), (_Float16)gelu_ggml(v[1]), (_Float16)gelu_ggml(v[2]), (_Float16)gelu_ggml(v[3])};
   }
-  fd_bar();
+  lds_barrier();
   if (wave >= 8) {
 #pragma unroll
     for (int j = 0; j < T2; ++j) {
@@ -567,7 +549,7 @@ __global__ __launch_bounds__(FD_THREADS) void fused_mlp_kernel(FusedMlpArgs a) {
       if (n16 < RB) *reinterpret_cast<f32x4*>(po + n16 * D + 16 * (T2 * (wave - 8) + j) + 4 * kq) = acc;
     }
   }
-  fd_bar();
+  lds_barrier();
   fd_store_partial<D, RB>(po, a.part_out, a.rows, row0, ch);
 }
 

@@ -23,11 +23,11 @@
 // pairs per block, blocks of a lane in K order, then a fixed shuffle tree over the 32 lanes of the row).
 #include "asr_common.h"
 #include "asr_quant.h"
+#include "wave_ops.h"
 
 namespace crispy {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 
 constexpr int GV_THREADS = 256;
@@ -138,14 +138,12 @@ __device__ __forceinline__ void gv_layernorm_wave(const float* __restrict__ x, c
   }
 #pragma unroll
   for (int q = 0; q < PER; ++q) s += e[q];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = shfl_sum(s);
   const float mean = s / (float)D;
   float s2 = 0.f;
 #pragma unroll
   for (int q = 0; q < PER; ++q) { const float d = e[q] - mean; s2 = fmaf(d, d, s2); }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s2 += __shfl_xor(s2, off, 64);
+  s2 = shfl_sum(s2);
   const float rstd = 1.f / sqrtf(s2 / (float)D + 1e-5f);
 #pragma unroll
   for (int q = 0; q < PER; ++q) {
@@ -363,8 +361,7 @@ __global__ __launch_bounds__(XA_THREADS) void gv_xattn_kernel(XattnArgs a) {
     sc[i] = k_lo + 8 * i + r8 < k_hi ? v : -1e30f;
     mloc = fmaxf(mloc, sc[i]);
   }
-#pragma unroll
-  for (int off = 8; off <= 32; off <<= 1) mloc = fmaxf(mloc, __shfl_xor(mloc, off, 64));
+  mloc = shfl_max<8, 32>(mloc);
   float lsum = 0.f, acc[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;

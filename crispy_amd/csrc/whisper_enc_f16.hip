@@ -20,6 +20,7 @@
 #include "api_util.h"
 #include <type_traits>
 #include "asr_common.h"
+#include "wave_ops.h"
 
 #include <cstdlib>
 
@@ -27,8 +28,6 @@ namespace crispy {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 typedef float float2v __attribute__((ext_vector_type(2)));
 
@@ -37,8 +36,6 @@ constexpr int HH_M = 128, HH_N = 128, HH_K = 32, HH_LD = 40;
 // GELU: ggml's form (asr_common.h: gelu_ggml).  (Rounds 1 - 2 used the exact erf form here -- Abramowitz & Stegun 7.1.26,
 // on packed f32 instructions: 97 cycles per value and lane, 12.4 k of the 23.4 k cycles of an fc1 epilogue.)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-// row index of accumulator register r for this lane (32 x 32 MFMA C / D layout)
-__device__ __forceinline__ int acc_row_e(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 __device__ __forceinline__ half4 to_half4(float a, float b, float c, float d) {
   const half2v lo = __builtin_convertvector(float2v{a, b}, half2v), hi = __builtin_convertvector(float2v{c, d}, half2v);
   return half4{lo[0], lo[1], hi[0], hi[1]};
@@ -71,14 +68,12 @@ __global__ __launch_bounds__(256) void layernorm_h_kernel(const float* __restric
   for (int q = 0; q < PER; ++q) { gm[q] = gamma[lane + 64 * q]; bt[q] = beta[lane + 64 * q]; }
 #pragma unroll
   for (int q = 0; q < PER; ++q) s += v[q];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = shfl_sum(s);
   const float mean = s / (float)D;
   float s2 = 0.f;
 #pragma unroll
   for (int q = 0; q < PER; ++q) { const float d = v[q] - mean; s2 = fmaf(d, d, s2); }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s2 += __shfl_xor(s2, off, 64);
+  s2 = shfl_sum(s2);
   const float rstd = 1.f / sqrtf(s2 / (float)D + 1e-5f);
   _Float16* yr = y + row * D;
 #pragma unroll
@@ -158,10 +153,10 @@ __device__ __forceinline__ void hh_epilogue(const HGemmArgs& g, f32x16 (&acc)[2]
           float extra[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r)     // residual operands of four rows requested together (clamped rows)
-            extra[r] = Rt[min(32 * i + acc_row_e(r0 + r, lane), mrem - 1) * ldr + (nok ? nl : 0)];
+            extra[r] = Rt[min(32 * i + acc_row(r0 + r, lane), mrem - 1) * ldr + (nok ? nl : 0)];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int ml = 32 * i + acc_row_e(r0 + r, lane);
+            const int ml = 32 * i + acc_row(r0 + r, lane);
             if (ml < mrem && nok) Ct[ml * ldc + nl] = acc[i][j][r0 + r] + bias + extra[r];
           }
         }
@@ -184,12 +179,12 @@ __device__ __forceinline__ void hh_epilogue(const HGemmArgs& g, f32x16 (&acc)[2]
           float extra[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int mg = min(m0 + wm + 32 * i + acc_row_e(r0 + r, lane), g.M - 1) % g.rowtab_period;
+            const int mg = min(m0 + wm + 32 * i + acc_row(r0 + r, lane), g.M - 1) % g.rowtab_period;
             extra[r] = Tt[mg * g.N + (nok ? nl : 0)];
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int ml = 32 * i + acc_row_e(r0 + r, lane);
+            const int ml = 32 * i + acc_row(r0 + r, lane);
             if (ml < mrem && nok) Ct[ml * ldc + nl] = gelu_ggml(acc[i][j][r0 + r] + bias) + extra[r];
           }
         }
@@ -306,12 +301,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void g
 // ---------------------------------------------------------------------------------------------
 constexpr int EP_LD = 68, EP_VLD = 36;
 constexpr int EP_IMAGE_BYTES = 64 * EP_VLD * 4;      // 9216: the larger of the two image shapes (32 x 68 and 64 x 36 floats)
-__device__ __forceinline__ void ep_wave_sync() {     // this wave's LDS traffic has landed (single-wave hand-off)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_s_waitcnt(0xc07f);                // lgkmcnt(0)
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // The three pieces of one 32-row pass.  rb = first row of the pass inside the wave's rows (m0 + wm is the wave's origin).
 // bias[j]: this lane's column 32 j + li of the wave's 64, requested by the caller above the k loop.
 //   ep_write     registers -> image: lane = column 32 j + li, register r = row 8 (r >> 2) + 4 lh + (r & 3)
@@ -332,8 +321,8 @@ __device__ __forceinline__ void ep_write(const HGemmArgs& g, const f32x16 (&acc)
       for (int r = 0; r < 16; r += 2) {
         f32x2 v = {acc[j][r] + bias[j], acc[j][r + 1] + bias[j]};
         if ((EPI == EPI_F16 && g.gelu) || EPI == EPI_TAB) v = f32x2{gelu_ggml(v.x), gelu_ggml(v.y)};
-        T[acc_row_e(r, lane) * EP_LD + 32 * j + li] = v.x;
-        T[acc_row_e(r + 1, lane) * EP_LD + 32 * j + li] = v.y;
+        T[acc_row(r, lane) * EP_LD + 32 * j + li] = v.x;
+        T[acc_row(r + 1, lane) * EP_LD + 32 * j + li] = v.y;
       }
   }
 }
@@ -440,10 +429,10 @@ __device__ __forceinline__ void hd_epilogue(const HGemmArgs& g, f32x16 (&acc)[2]
   for (int i = 0; i < 2; ++i) {
     float4 ex[8];
     ep_write<EPI>(g, acc[i], T, lane, bias);
-    ep_wave_sync();
+    wave_lds_sync();
     ep_prefetch<EPI>(g, ex, m0, n0, wm, wn, 32 * i, lane, bz);       // (ahead of the image write it costs 12 - 18 registers: 128 is the budget here)
     ep_store<EPI>(g, T, ex, m0, n0, wm, wn, 32 * i, lane, bz);
-    ep_wave_sync();                                  // the image is read before the second half overwrites it
+    wave_lds_sync();                                 // the image is read before the second half overwrites it
   }
 }
 // 128 x 64 wave tile, two images: the image of pass p + 1 is written BEFORE the hand-off of pass p, so a pass is one
@@ -462,7 +451,7 @@ __device__ __forceinline__ void hd2_epilogue(const HGemmArgs& g, f32x16 (&acc)[M
       ep_prefetch<EPI>(g, ex[(p + 1) & 1], m0, n0, wm, wn, 32 * (p + 1), lane, bz);
       ep_write<EPI>(g, acc[p + 1], (p & 1) ? T0 : T1, lane, bias);     // its previous reader (pass p - 1) has issued its stores
     }
-    ep_wave_sync();
+    wave_lds_sync();
     ep_store<EPI>(g, (p & 1) ? T1 : T0, ex[p & 1], m0, n0, wm, wn, 32 * p, lane, bz);
   }
 }
@@ -675,7 +664,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void a
       if (k0 + 32 > T) {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (k0 + acc_row_e(r, lane) >= T) s[r] = -3e38f;
+          if (k0 + acc_row(r, lane) >= T) s[r] = -3e38f;
       }
       float mloc = fmaxf(fmaxf(s[0], s[1]), s[2]);
 #pragma unroll
@@ -749,7 +738,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void a
     if (tail) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        if (k0 + acc_row_e(r, lane) >= T) s[r] = -3e38f;
+        if (k0 + acc_row(r, lane) >= T) s[r] = -3e38f;
     }
     float mloc = nlarge;
 #pragma unroll
@@ -839,10 +828,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void a
     *reinterpret_cast<half4*>(Timg + li * AT_KLD + d) = to_half4(o0[4 * g4] * inv, o0[4 * g4 + 1] * inv, o0[4 * g4 + 2] * inv, o0[4 * g4 + 3] * inv);
     *reinterpret_cast<half4*>(Timg + li * AT_KLD + 32 + d) = to_half4(o1[4 * g4] * inv, o1[4 * g4 + 1] * inv, o1[4 * g4 + 2] * inv, o1[4 * g4 + 3] * inv);
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
     const int row = (lane >> 3) + 8 * p, c8 = (lane & 7) * 8;

@@ -21,6 +21,7 @@
 #include <atomic>
 #include "asr_common.h"
 #include "asr_quant.h"
+#include "wave_ops.h"
 
 namespace crispy {
 namespace {
@@ -162,14 +163,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
 // (24 for N = 384).  W is re-read per row block from L2.
 // ---------------------------------------------------------------------------------------------
 constexpr int SK_PF = 3;                       // K chunks (32 wide) in flight per wave
-typedef _Float16 sk_half8 __attribute__((ext_vector_type(8)));
 constexpr int SK_WAVE_LDS = 2048;              // floats of LDS per wave (two 4 KB operand chunks; later the 32 x 33 partial tile)
-__device__ __forceinline__ void sk_wave_sync() {     // LDS traffic of one wave: in order, so a fence for the compiler and a wait
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0)
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // LN / GELU / RES are compile-time so that the epilogue operands (ln_s, ln_c or bias, residual) can be requested
 // up front, next to the first K chunks, from clamped (always valid) addresses: with run-time flags every one of them
 // sat behind its own branch in the epilogue and cost a serialized L2 round trip after the barrier.
@@ -277,7 +271,7 @@ __device__ __forceinline__ void sk_wave_sync() {     // LDS traffic of one wave:
 // f16 on the way in, against the eight halves WV.
 #define SK_MFMA_F16(ST, WV)                                                                                        \
   {                                                                                                                \
-    const sk_half8 av = {(_Float16)ca[2 * (ST)].x, (_Float16)ca[2 * (ST)].y, (_Float16)ca[2 * (ST)].z, (_Float16)ca[2 * (ST)].w, \
+    const half8 av = {(_Float16)ca[2 * (ST)].x, (_Float16)ca[2 * (ST)].y, (_Float16)ca[2 * (ST)].z, (_Float16)ca[2 * (ST)].w,    \
                          (_Float16)ca[2 * (ST) + 1].x, (_Float16)ca[2 * (ST) + 1].y, (_Float16)ca[2 * (ST) + 1].z, (_Float16)ca[2 * (ST) + 1].w}; \
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, WV, acc, 0, 0, 0);                                            \
   }
@@ -340,13 +334,13 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_f32_kernel(GemmArgs g) {
   {                                                                                                 \
     _Pragma("unroll") for (int j = 0; j < 4; ++j) { if (!WH || j < 2) stw[64 * j + lane] = WR[j]; sta[64 * j + lane] = AR[j]; } \
     if ((KC) + 32 * PF < kper) { SK_REQUEST(WR, AR, (KC) + 32 * PF) }                               \
-    sk_wave_sync();                                                                                 \
+    wave_lds_sync();                                                                                \
     f32x4 cw[4], ca[4];                                                                            \
     _Pragma("unroll") for (int q = 0; q < 4; ++q) { if (!WH) cw[q] = stw[rslot[q]]; ca[q] = sta[rslot[q]]; } \
     if (WH) { cw[0] = stw[li * 4 + ((2 * lh) ^ ((li >> 2) & 3))]; cw[1] = stw[li * 4 + ((2 * lh + 1) ^ ((li >> 2) & 3))]; } \
-    sk_wave_sync();                                                                                 \
+    wave_lds_sync();                                                                                \
     if (WH) {                                                                                       \
-      _Pragma("unroll") for (int st = 0; st < 2; ++st) SK_MFMA_F16(st, __builtin_bit_cast(sk_half8, cw[st]))     \
+      _Pragma("unroll") for (int st = 0; st < 2; ++st) SK_MFMA_F16(st, __builtin_bit_cast(half8, cw[st]))        \
     } else {                                                                                        \
       _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                               \
         const float wv[4] = {cw[q].x, cw[q].y, cw[q].z, cw[q].w};                                   \
@@ -494,13 +488,13 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_q_kernel(GemmArgs g) {
       }                                                                                             \
     }                                                                                               \
     if ((KC) + 32 * PF < kper) SKQ_REQUEST(BR, AR, GR, (KC) + 32 * PF)                              \
-    sk_wave_sync();                                                                                 \
+    wave_lds_sync();                                                                                \
     f32x4 ca[4];                                                                                    \
     _Pragma("unroll") for (int q = 0; q < 4; ++q) ca[q] = sta[rslot[q]];                            \
-    sk_wave_sync();                                                                                 \
+    wave_lds_sync();                                                                                \
     if (WH) {                                                                                       \
       _Pragma("unroll") for (int st = 0; st < 2; ++st)                                              \
-        SK_MFMA_F16(st, (sk_half8{(_Float16)wy[8 * st], (_Float16)wy[8 * st + 1], (_Float16)wy[8 * st + 2], (_Float16)wy[8 * st + 3], \
+        SK_MFMA_F16(st, (half8{(_Float16)wy[8 * st], (_Float16)wy[8 * st + 1], (_Float16)wy[8 * st + 2], (_Float16)wy[8 * st + 3],    \
                                   (_Float16)wy[8 * st + 4], (_Float16)wy[8 * st + 5], (_Float16)wy[8 * st + 6], (_Float16)wy[8 * st + 7]})) \
     } else {                                                                                        \
       _Pragma("unroll") for (int q = 0; q < 4; ++q) SK_MFMA_F32(q, wy[4 * q + e])                   \
@@ -544,14 +538,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   for (int q = 0; q < PER; ++q) { gm[q] = gamma[lane + 64 * q]; bt[q] = beta[lane + 64 * q]; }
 #pragma unroll
   for (int q = 0; q < PER; ++q) s += v[q];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = shfl_sum(s);
   const float mean = s / (float)D;
   float s2 = 0.f;
 #pragma unroll
   for (int q = 0; q < PER; ++q) { const float d = v[q] - mean; s2 = fmaf(d, d, s2); }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s2 += __shfl_xor(s2, off, 64);
+  s2 = shfl_sum(s2);
   const float rstd = 1.f / sqrtf(s2 / (float)D + 1e-5f);
   float* yr = y + row * D;
 #pragma unroll

@@ -16,6 +16,7 @@
 // called from decode_steps.cpp alone, whichever kernels run the layers of the step.
 #include "asr_common.h"
 #include "asr_quant.h"
+#include "wave_ops.h"
 
 namespace crispy {
 namespace {
@@ -741,8 +742,7 @@ __global__ __launch_bounds__(1024) void softmax_prob_kernel(const float* __restr
   const float* lg = logits + (long)b * ld;
   float m = -INFINITY;
   for (int v = tid; v < V; v += 1024) m = fmaxf(m, lg[v]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  m = shfl_max(m);
   if ((tid & 63) == 0) s_r[tid >> 6] = m;
   __syncthreads();
   m = s_r[0];
@@ -751,8 +751,7 @@ __global__ __launch_bounds__(1024) void softmax_prob_kernel(const float* __restr
   __syncthreads();
   float sum = 0.f;
   for (int v = tid; v < V; v += 1024) sum += expf(lg[v] - m);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+  sum = shfl_sum(sum);
   if ((tid & 63) == 0) s_r[tid >> 6] = sum;
   __syncthreads();
   if (tid == 0) {

@@ -1,10 +1,10 @@
 // whisper_quant.hip -- de-quantisation of resident ggml blocks at the point of use (asr_quant.h).
 #include "asr_quant.h"
+#include "wave_ops.h"
 
 namespace crispy {
 namespace {
 
-typedef _Float16 q_half8 __attribute__((ext_vector_type(8)));
 typedef float q_f4 __attribute__((ext_vector_type(4)));
 
 // One thread per block of 32 weights: consecutive threads read consecutive blocks (18 - 34 bytes each, contiguous) and
@@ -23,10 +23,10 @@ __global__ __launch_bounds__(256) void dequant_kernel(const unsigned char* __res
     for (int j = 0; j < 32; ++j) y[j] = y[j] * g[j];
   }
   if (F16OUT) {
-    q_half8* o = reinterpret_cast<q_half8*>(reinterpret_cast<_Float16*>(dst) + i * 32);
+    half8* o = reinterpret_cast<half8*>(reinterpret_cast<_Float16*>(dst) + i * 32);
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
-      q_half8 v;
+      half8 v;
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = (_Float16)y[8 * w + e];
       o[w] = v;

@@ -3,7 +3,8 @@
         --b crispy_amd/csrc/whisper_gemm.hip crispy_amd/csrc/whisper_attn.hip crispy_amd/csrc/whisper_pick.hip
 A side is a git revision (its crispy_amd/csrc and include/ are checked out into a temporary directory) or a directory that
 holds such a tree ("." = the working tree); --a / --b list the .hip files of each side (--b defaults to --a).  Every file
-is cross-compiled to gfx950 assembly with the CXXFLAGS of its own side's Makefile; the kernels of a side's files are pooled
+is cross-compiled to gfx950 assembly with the CXXFLAGS of its own side's Makefile, followed on both sides by what --flags
+gives (one string, e.g. --flags "-DRN_PROFILE -DCRISPY_DEV_KNOBS", for the builds the Makefile makes with other defines); the kernels of a side's files are pooled
 and compared by mangled name:
   * the instruction stream from the kernel's label to its end, without comments and .loc / .file / .cfi lines, with the
     local labels (.LBB<function>_<n>, .Ltmp<n>, .Lfunc_begin / .Lfunc_end<n>) renumbered per kernel;
@@ -37,12 +38,12 @@ def materialise(side: str, tmp: str) -> str:
     return dst
 
 
-def assemble(root: str, rel: str) -> str:
+def assemble(root: str, rel: str, extra: list[str]) -> str:
     csrc = os.path.join(root, "crispy_amd", "csrc")
     text = open(os.path.join(csrc, "Makefile")).read()
     arch = re.search(r"^ARCH \?= (\S+)", text, re.M).group(1)
     flags = re.search(r"^CXXFLAGS \?= (.*)$", text, re.M).group(1).replace("$(ARCH)", arch).split()
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), *flags, "--cuda-device-only", "-S", "-x", "hip",
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), *flags, *extra, "--cuda-device-only", "-S", "-x", "hip",
            os.path.join(root, rel), "-o", "-"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=csrc)
     if r.returncode != 0:
@@ -91,10 +92,10 @@ def kernels(asm: str) -> dict[str, tuple[list[str], list[str]]]:
     return res
 
 
-def pooled(root: str, files: list[str]) -> dict:
+def pooled(root: str, files: list[str], extra: list[str]) -> dict:
     pool = {}
     for f in files:
-        ks = kernels(assemble(root, f))
+        ks = kernels(assemble(root, f, extra))
         dup = set(ks) & set(pool)
         if dup:
             sys.exit(f"{f}: kernels already seen in another file of the same side: {sorted(dup)[:3]}")
@@ -117,12 +118,20 @@ def main():
     ap.add_argument("--a", nargs="+", required=True, metavar="FILE", help=".hip files of side A, relative to the tree's root")
     ap.add_argument("--b", nargs="+", default=None, metavar="FILE", help=".hip files of side B (default: those of A)")
     ap.add_argument("-q", "--quiet", action="store_true", help="only kernels that differ, and the summary")
-    a = ap.parse_args()
+    ap.add_argument("--flags", default="", metavar="FLAGS", help="extra compiler flags appended on both sides, one string")
+    # `--flags -DX=1`: argparse would take a lone value that begins with '-' for an option, so the pair is joined first
+    argv = sys.argv[1:]
+    for i in range(len(argv) - 1):
+        if argv[i] == "--flags":
+            argv[i:i + 2] = ["--flags=" + argv[i + 1]]
+            break
+    a = ap.parse_args(argv)
+    extra = a.flags.split()
     with tempfile.TemporaryDirectory() as tmp:
         print(f"A = {a.side_a}", file=sys.stderr)
-        ka = pooled(materialise(a.side_a, tmp), a.a)
+        ka = pooled(materialise(a.side_a, tmp), a.a, extra)
         print(f"B = {a.side_b}", file=sys.stderr)
-        kb = pooled(materialise(a.side_b, tmp), a.b or a.a)
+        kb = pooled(materialise(a.side_b, tmp), a.b or a.a, extra)
     same = 0
     for n in sorted(set(ka) & set(kb)):
         (ia, da), (ib, db) = ka[n], kb[n]
