@@ -329,6 +329,10 @@ extern "C" {
     pub fn crispy_diar_find_speaker(time: f64, seg_start: *const f64, seg_end: *const f64, seg_speaker: *const c_int, n_segments: c_long) -> c_int;
     pub fn crispy_diar_format_text(t0: *const f64, t1: *const f64, text: *const *const c_char, n_words: c_long, seg_start: *const f64, seg_end: *const f64, seg_speaker: *const c_int, n_segments: c_long, out: *mut c_char, cap: usize, needed: *mut usize) -> c_int;
     pub fn crispy_diar_format_result(r: *const crispy_asr_result, chunk_offset: f64, seg_start: *const f64, seg_end: *const f64, seg_speaker: *const c_int, n_segments: c_long, out: *mut c_char, cap: usize, needed: *mut usize) -> c_int;
+    pub fn crispy_diar_fbank_frames(n_samples: c_long) -> c_long;
+    pub fn crispy_diar_speech_segments(scores: *const c_float, n_windows: c_long, n_frames: c_int, n_classes: c_int, n_samples: c_long, sample_rate: c_int, merge_gap: f64, out_start: *mut f64, out_end: *mut f64, out_first: *mut c_long, out_len: *mut c_long, cap: c_long) -> c_long;
+    pub fn crispy_diar_fbank_device(h: *mut c_void, d_pcm: *const c_void, pcm_format: c_int, first: *const c_long, len: *const c_long, n_chunks: c_int, scale: c_float, d_feats: *mut c_float, d_raw: *mut c_float, frame_offset: *mut c_long, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_diar_fbank(h: *mut c_void, pcm: *const c_void, pcm_format: c_int, first: *const c_long, len: *const c_long, n_chunks: c_int, scale: c_float, feats: *mut c_float, frame_offset: *mut c_long) -> c_int;
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -67,7 +67,10 @@ DIAR_SYMBOLS = ("crispy_diar_create", "crispy_diar_destroy", "crispy_diar_cluste
                 "crispy_diar_decide_device", "crispy_diar_kmeans_device", "crispy_diar_chunk_plan",
                 "crispy_diar_speaker_segments", "crispy_diar_find_speaker",
                 "crispy_diar_format_text", "crispy_diar_format_result")
-ALL_SYMBOLS = RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS + DIAR_SYMBOLS
+DIAR_FRONT_SYMBOLS = ("crispy_diar_fbank_frames", "crispy_diar_speech_segments", "crispy_diar_fbank_device", "crispy_diar_fbank")
+ALL_SYMBOLS = RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS + DIAR_SYMBOLS + DIAR_FRONT_SYMBOLS
+FBANK_BINS, FBANK_WAVE_FRAMES, FBANK_TILE_FRAMES = 80, 8, 32      # crispy_amd/csrc/diar_internal.h
+FBANK_MAX_CHUNKS, FBANK_MAX_CHUNK_SAMPLES = 16384, 4800000
 DIAR_MAX_N, DIAR_MAX_DIM, DIAR_MAX_BATCH, DIAR_LDS_N = 2048, 1024, 64, 192
 
 
@@ -318,6 +321,14 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_diar_format_text.argtypes = [f64p, f64p, C.POINTER(C.c_char_p), C.c_long, f64p, f64p, i32p, C.c_long,
                                           C.c_char_p, C.c_size_t, szp]
     L.crispy_diar_format_result.argtypes = [C.c_void_p, C.c_double, f64p, f64p, i32p, C.c_long, C.c_char_p, C.c_size_t, szp]
+    L.crispy_diar_fbank_frames.argtypes = [C.c_long]
+    L.crispy_diar_fbank_frames.restype = C.c_long
+    L.crispy_diar_speech_segments.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_long, C.c_int, C.c_double,
+                                              f64p, f64p, lp, lp, C.c_long]
+    L.crispy_diar_speech_segments.restype = C.c_long
+    L.crispy_diar_fbank_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, lp, lp, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                           lp, C.c_void_p]
+    L.crispy_diar_fbank.argtypes = [C.c_void_p, C.c_void_p, C.c_int, lp, lp, C.c_int, C.c_float, C.c_void_p, lp]
     return L
 
 

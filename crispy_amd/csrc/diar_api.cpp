@@ -15,18 +15,6 @@ using crispy::DevBuf;
 using crispy::fail;
 using namespace crispy::diar;
 
-struct crispy_diar {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  DevBuf<char> scratch;      // the turn's matrices, grown on demand and kept
-  DevBuf<char> io;           // host-form embeddings and labels
-  DevBuf<char> descs;        // the solver's counter, the non-finite flag (first 256 bytes), EigDesc and ClusterDesc lists
-  DevBuf<char> infos;        // crispy_diar_info of a call's recordings
-  ~crispy_diar() {
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
 namespace {
 
 constexpr size_t kScratchCap = (size_t)2000 << 20;      // per turn, below the 2 GB the header states

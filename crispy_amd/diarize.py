@@ -1,7 +1,10 @@
 """Speaker clustering and diarized text over the C ABI (crispy_diar_*, include/crispy_hip.h): the reference's `nme_sc`, the
 tail of `run_diarization` and `format_diarized_text` (src-tauri/src/managers/diarization.rs:276-724).  Embeddings are the
 caller's; there is no CPU path for the clustering.  The host functions (`chunk_plan`, `speaker_segments`, `find_speaker`,
-`format_diarized_text`) need no device."""
+`format_diarized_text`) need no device.
+
+The front end (crispy_diar_fbank*, crispy_diar_speech_segments): `segmentation_windows`, `speech_segments`, `Diarizer.fbank`
+and `run_diarization`, which is the reference's run_diarization (:276-409) with its two networks as callables."""
 from __future__ import annotations
 
 import ctypes as C
@@ -101,6 +104,119 @@ class Diarizer:
                                                   pts.data_ptr() if pts is not None else None,
                                                   ctr.data_ptr() if ctr is not None else None), self._L)
         return (labels, pts, ctr) if details else labels
+
+    def fbank(self, pcm, chunks, scale: float = 1.0):
+        """The embedding network's features (EmbeddingExtractor::compute, :53-75).  pcm: 16 kHz mono numpy int16 or float32
+        (f32 goes through f32_to_i16 on the device); chunks: (first sample, n samples) pairs -> list of f32 [frames, 80] arrays,
+        one per chunk (no rows for a chunk of fewer than 400 samples)."""
+        pcm = np.ascontiguousarray(pcm)
+        fmt = _pcm_format(pcm.dtype)
+        first, ln, off = _chunk_arrays(chunks)
+        args = (self._h, pcm.ctypes.data if pcm.size else None, fmt, _p(first, C.c_long), _p(ln, C.c_long), len(first), float(scale))
+        N.check(self._L.crispy_diar_fbank(*args, None, _p(off, C.c_long)), self._L)
+        feats = np.zeros((int(off[-1]), N.FBANK_BINS), np.float32)
+        if feats.size:
+            N.check(self._L.crispy_diar_fbank(*args, feats.ctypes.data, _p(off, C.c_long)), self._L)
+        return [feats[off[c]:off[c + 1]] for c in range(len(first))]
+
+    def fbank_device(self, pcm, chunks, scale: float = 1.0, raw: bool = False, stream=None):
+        """The same on a CUDA int16 or float32 tensor -> (f32 CUDA tensor [rows, 80], frame_offset int64 [n_chunks + 1]), with
+        `raw` also the rows before the mean subtraction."""
+        import torch
+        fmt = _pcm_format(pcm.dtype)
+        first, ln, off = _chunk_arrays(chunks)
+        args = (self._h, pcm.data_ptr() if pcm.numel() else None, fmt, _p(first, C.c_long), _p(ln, C.c_long), len(first), float(scale))
+        N.check(self._L.crispy_diar_fbank_device(*args, None, None, _p(off, C.c_long), stream), self._L)
+        feats = torch.empty((int(off[-1]), N.FBANK_BINS), dtype=torch.float32, device=pcm.device)
+        rows = torch.empty_like(feats) if raw else None
+        if feats.numel():
+            if stream is None:      # the handle's stream does not wait for torch's: what produced pcm must have finished
+                torch.cuda.current_stream(pcm.device).synchronize()
+            N.check(self._L.crispy_diar_fbank_device(*args, feats.data_ptr(), rows.data_ptr() if raw else None, _p(off, C.c_long), stream),
+                    self._L)
+        return (feats, rows, off) if raw else (feats, off)
+
+
+def _pcm_format(dtype) -> int:
+    name = str(dtype).replace("torch.", "")
+    if name == "int16":
+        return N.PCM_I16
+    if name == "float32":
+        return N.PCM_F32
+    raise TypeError(f"pcm must be int16 or float32, not {dtype}")
+
+
+def _chunk_arrays(chunks):
+    first = np.ascontiguousarray([c[0] for c in chunks], dtype=np.int64)
+    ln = np.ascontiguousarray([c[1] for c in chunks], dtype=np.int64)
+    return first, ln, np.zeros(len(first) + 1, np.int64)
+
+
+def fbank_frames(n: int) -> int:
+    """Rows of the fbank for n samples (snip_edges: 400 samples at hop 160)."""
+    return int(N.lib().crispy_diar_fbank_frames(int(n)))
+
+
+def f32_to_i16(x) -> np.ndarray:
+    """f32_to_i16 (:649-654): (s.clamp(-1, 1) * 32767.0) as i16 -- truncating, NaN -> 0."""
+    x = np.asarray(x, np.float32)
+    v = np.clip(x, np.float32(-1), np.float32(1)) * np.float32(32767.0)
+    return np.where(np.isnan(v), np.float32(0), v).astype(np.int16)
+
+
+SEG_WINDOW = 160000      # the segmentation network's 10 s window
+
+
+def segmentation_windows(pcm_i16) -> np.ndarray:
+    """The network inputs of pyannote_get_segments_fixed (:103-128): the samples padded with zeros to a multiple of 10 s plus
+    one more window, as i16 / 32768 -> f32 [n_windows, 160000] (no window for no samples)."""
+    x = np.ascontiguousarray(pcm_i16, dtype=np.int16)
+    if x.size == 0:
+        return np.zeros((0, SEG_WINDOW), np.float32)
+    n_win = -(-x.size // SEG_WINDOW) + 1
+    out = np.zeros(n_win * SEG_WINDOW, np.float32)
+    out[:x.size] = x.astype(np.float32) / np.float32(32768.0)
+    return out.reshape(n_win, SEG_WINDOW)
+
+
+def speech_segments(scores, n_samples: int, merge_gap: float, sample_rate: int = 16000):
+    """The post-network half of pyannote_get_segments_fixed (:146-271).  scores: f32 [n_windows, n_frames, n_classes] ->
+    list of (start s, end s, first sample, n samples)."""
+    L = N.lib()
+    sc = np.ascontiguousarray(scores, dtype=np.float32)
+    if sc.ndim != 3:
+        raise ValueError("scores must be [n_windows, n_frames, n_classes]")
+    args = (sc.ctypes.data if sc.size else None, sc.shape[0], sc.shape[1], sc.shape[2], int(n_samples), int(sample_rate), float(merge_gap))
+    cnt = L.crispy_diar_speech_segments(*args, None, None, None, None, 0)
+    if cnt < 0:
+        N.check(int(cnt), L)
+    os_, oe = np.zeros(cnt), np.zeros(cnt)
+    of, ol = np.zeros(cnt, np.int64), np.zeros(cnt, np.int64)
+    if cnt:
+        L.crispy_diar_speech_segments(*args, _p(os_, C.c_double), _p(oe, C.c_double), _p(of, C.c_long), _p(ol, C.c_long), cnt)
+    return [(float(os_[i]), float(oe[i]), int(of[i]), int(ol[i])) for i in range(cnt)]
+
+
+def run_diarization(pcm, seg_fn, emb_fn, max_speakers: int, merge_gap: float, diarizer: "Diarizer"):
+    """run_diarization (:276-409) with the two networks as callables.  pcm: 16 kHz mono, f32 in [-1, 1] (taken through
+    f32_to_i16) or int16; seg_fn(window f32 [160000]) -> [frames, classes]; emb_fn(features f32 [frames, 80]) -> [dim].
+    -> merged [(start, end, speaker number >= 1)]."""
+    pcm = np.asarray(pcm)
+    x = pcm if pcm.dtype == np.int16 else f32_to_i16(pcm)
+    if x.size == 0:
+        return []
+    scores = np.stack([np.asarray(seg_fn(w), np.float32) for w in segmentation_windows(x)])
+    segments = speech_segments(scores, x.size, merge_gap)
+    if not segments:
+        return []
+    plan = chunk_plan([(s, e, n) for s, e, _first, n in segments])
+    feats = diarizer.fbank(x, [(segments[seg][2] + first, n) for _s, _e, seg, first, n in plan])
+    keep = [c for c in range(len(plan)) if len(feats[c])]      # `if let Ok(embedding)`: a chunk without frames is dropped
+    if not keep:
+        return []
+    emb = np.stack([np.asarray(emb_fn(feats[c]), np.float32).reshape(-1) for c in keep])
+    labels = diarizer.cluster([emb], max(int(max_speakers), 1))[0][0]
+    return speaker_segments([plan[c][0] for c in keep], [plan[c][1] for c in keep], labels, merge_gap)
 
 
 def nme_sc(embeddings, max_speakers: int, device: int = 0) -> np.ndarray:

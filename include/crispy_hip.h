@@ -1089,6 +1089,56 @@ int crispy_diar_format_text(const double *t0, const double *t1, const char *cons
 int crispy_diar_format_result(const crispy_asr_result *r, double chunk_offset, const double *seg_start, const double *seg_end,
                               const int *seg_speaker, long n_segments, char *out, size_t cap, size_t *needed);
 
+/* ------------------------------------------------------------------------------------------
+ * Diarization front end: what run_diarization (managers/diarization.rs:276-409) computes between the 16 kHz audio and its
+ * two networks, so that a host supplies the networks alone.  New entry points only: no struct grew, the ABI version is
+ * unchanged.
+ *
+ *   crispy_diar_fbank_frames: rows the fbank gives for n samples: n < 400 ? 0 : 1 + (n - 400) / 160.
+ *
+ *   crispy_diar_speech_segments (host, no device): the post-network half of pyannote_get_segments_fixed (:146-271).
+ *     scores [n_windows][n_frames][n_classes] are the segmentation network's outputs on the zero-padded 10 s windows of
+ *     :103-128 (the samples as i16 / 32768, padded to a multiple of 160000 plus one more window).  Per frame the f32
+ *     soft-max with the maximum subtracted, summed in class order; p_sil = e[0] / sum; speech unless p_sil > 0.5.  The
+ *     11-frame median filter (speech where count_speech > count_total / 2, integer division, the window shortened at a
+ *     window's edges).  A change of state at frame i of window w falls at sample w * 160000 + 721 + 270 i; the state is
+ *     carried from window to window; a start below 1600 snaps to 0; starts and ends are clamped to n_samples and empty
+ *     spans dropped; speech still open at the end closes at n_samples.  Sorted by start (stable), merged while start <=
+ *     last.end + (usize)(sample_rate * merge_gap), kept from (usize)(sample_rate * 1.5) samples on; if none is left, the
+ *     longest merged span (the last of equals).  Outputs as crispy_diar_chunk_plan takes them: start and end in seconds
+ *     (index as f64 / rate), first sample, sample count.  Returns the number of segments; entries beyond `cap` are not
+ *     written.  sample_rate != 16000, a non-finite merge_gap, n_classes < 1, n_frames < 1: INVALID_ARG; n_samples == 0 or
+ *     n_windows == 0: 0.
+ *
+ *   crispy_diar_fbank_device / crispy_diar_fbank: the features the embedding network reads (EmbeddingExtractor::compute,
+ *     :53-75, knf_rs::compute_fbank): an 80-bin Kaldi fbank with per-chunk mean subtraction, every chunk of a call in one
+ *     launch pair on a crispy_diar handle.  d_pcm is one 16 kHz mono buffer of pcm_format CRISPY_PCM_I16 (the reference's
+ *     &[i16]) or CRISPY_PCM_F32; chunk c is its samples first[c] ... first[c] + len[c] (crispy_diar_chunk_plan's arrays,
+ *     the segment's own first sample added; overlapping and out-of-order chunks are fine).  With f32 the kernel applies
+ *     f32_to_i16 itself ((s.clamp(-1, 1) * 32767.0) as i16, truncating, NaN -> 0), so the result is bit for bit that
+ *     of the i16 form.  x = i16 as f32 / 32768 * scale: scale 1 is what knf-rs hands over, 32768 the Kaldi / WeSpeaker
+ *     convention; the mel floor is absolute, so the choice changes results.
+ *     Per frame (snip_edges: 400 samples at hop 160, a chunk of fewer than 400 samples has no rows): frame mean removed,
+ *     pre-emphasis 0.97 from the back (x[0] -= 0.97 x[0]), Povey window (0.5 - 0.5 cos(2 pi i / 399))^0.85, zero padding to
+ *     512, power spectrum (f32; a 256-point complex transform plus the real-input pass), 80 filters triangular in mel
+ *     space (1127 ln(1 + f / 700)) between 20 and 8000 Hz over bins 0 ... 255 (501 taps, f32 sums in tap order),
+ *     log(max(e, 1.1920929e-07)).  Per chunk every column's mean (the f32 sum in frame order / the frame count) is
+ *     subtracted.  d_feats [rows][80]; d_raw (nullable) receives the rows before the subtraction; frame_offset (host,
+ *     [n_chunks + 1]) receives each chunk's first row and the total, from the lengths alone: with d_feats NULL the call
+ *     only fills it (no device is touched), which sizes the buffers.  A chunk's rows are the same bytes alone and in
+ *     any call.  The work is enqueued on hip_stream (NULL: the handle's own) and complete on return.  crispy_diar_fbank
+ *     is the same with pcm and feats on the host.
+ *     Limits, checked before any launch: 1 <= n_chunks <= 16384, 0 <= len[c] <= 4 800 000, first[c] >= 0, rows x 320
+ *     bytes <= 2 GB, scale finite and > 0.  There is no CPU path.
+ * ------------------------------------------------------------------------------------------ */
+long crispy_diar_fbank_frames(long n_samples);
+long crispy_diar_speech_segments(const float *scores, long n_windows, int n_frames, int n_classes, long n_samples, int sample_rate,
+                                 double merge_gap, double *out_start, double *out_end, long *out_first, long *out_len, long cap);
+int crispy_diar_fbank_device(void *h, const void *d_pcm, int pcm_format, const long *first, const long *len, int n_chunks,
+                             float scale, float *d_feats, float *d_raw, long *frame_offset, void *hip_stream);
+int crispy_diar_fbank(void *h, const void *pcm, int pcm_format, const long *first, const long *len, int n_chunks, float scale,
+                      float *feats, long *frame_offset);
+
 #ifdef __cplusplus
 }
 #endif
