@@ -333,6 +333,14 @@ extern "C" {
     pub fn crispy_diar_speech_segments(scores: *const c_float, n_windows: c_long, n_frames: c_int, n_classes: c_int, n_samples: c_long, sample_rate: c_int, merge_gap: f64, out_start: *mut f64, out_end: *mut f64, out_first: *mut c_long, out_len: *mut c_long, cap: c_long) -> c_long;
     pub fn crispy_diar_fbank_device(h: *mut c_void, d_pcm: *const c_void, pcm_format: c_int, first: *const c_long, len: *const c_long, n_chunks: c_int, scale: c_float, d_feats: *mut c_float, d_raw: *mut c_float, frame_offset: *mut c_long, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_diar_fbank(h: *mut c_void, pcm: *const c_void, pcm_format: c_int, first: *const c_long, len: *const c_long, n_chunks: c_int, scale: c_float, feats: *mut c_float, frame_offset: *mut c_long) -> c_int;
+    // the segmentation network (pyannote segmentation-3.0) on a crispy_diar handle: the first session.run of run_diarization
+    pub fn crispy_diar_seg_frames(len: c_long) -> c_long;
+    pub fn crispy_diar_seg_windows(n_samples: c_long) -> c_long;
+    pub fn crispy_diar_seg_load(h: *mut c_void, names: *const *const c_char, data: *const *const c_float, count: *const c_long, n_tensors: c_int) -> c_int;
+    pub fn crispy_diar_seg_loaded(h: *mut c_void) -> c_int;
+    pub fn crispy_diar_seg_forward_device(h: *mut c_void, d_x: *const c_float, n_win: c_int, len: c_long, d_scores: *mut c_float, d_sincnet: *mut c_float, d_lstm: *mut c_float, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_diar_seg_scores_device(h: *mut c_void, d_pcm: *const c_void, pcm_format: c_int, n_samples: c_long, d_scores: *mut c_float, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_diar_seg_scores(h: *mut c_void, pcm: *const c_void, pcm_format: c_int, n_samples: c_long, scores: *mut c_float) -> c_int;
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -68,7 +68,11 @@ DIAR_SYMBOLS = ("crispy_diar_create", "crispy_diar_destroy", "crispy_diar_cluste
                 "crispy_diar_speaker_segments", "crispy_diar_find_speaker",
                 "crispy_diar_format_text", "crispy_diar_format_result")
 DIAR_FRONT_SYMBOLS = ("crispy_diar_fbank_frames", "crispy_diar_speech_segments", "crispy_diar_fbank_device", "crispy_diar_fbank")
-ALL_SYMBOLS = RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS + DIAR_SYMBOLS + DIAR_FRONT_SYMBOLS
+DIAR_SEG_SYMBOLS = ("crispy_diar_seg_frames", "crispy_diar_seg_windows", "crispy_diar_seg_load", "crispy_diar_seg_loaded",
+                    "crispy_diar_seg_forward_device", "crispy_diar_seg_scores_device", "crispy_diar_seg_scores")
+ALL_SYMBOLS = RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS + DIAR_SYMBOLS + DIAR_FRONT_SYMBOLS + DIAR_SEG_SYMBOLS
+SEG_WINDOW, SEG_MIN_LEN, SEG_FRAMES, SEG_CLASSES = 160000, 991, 589, 7      # crispy_amd/csrc/diar_internal.h
+SEG_MAX_SAMPLES, SEG_MAX_WINDOWS = 115200000, 4096
 FBANK_BINS, FBANK_WAVE_FRAMES, FBANK_TILE_FRAMES = 80, 8, 32      # crispy_amd/csrc/diar_internal.h
 FBANK_MAX_CHUNKS, FBANK_MAX_CHUNK_SAMPLES = 16384, 4800000
 DIAR_MAX_N, DIAR_MAX_DIM, DIAR_MAX_BATCH, DIAR_LDS_N = 2048, 1024, 64, 192
@@ -329,6 +333,15 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_diar_fbank_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, lp, lp, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                            lp, C.c_void_p]
     L.crispy_diar_fbank.argtypes = [C.c_void_p, C.c_void_p, C.c_int, lp, lp, C.c_int, C.c_float, C.c_void_p, lp]
+    L.crispy_diar_seg_frames.argtypes = [C.c_long]
+    L.crispy_diar_seg_frames.restype = C.c_long
+    L.crispy_diar_seg_windows.argtypes = [C.c_long]
+    L.crispy_diar_seg_windows.restype = C.c_long
+    L.crispy_diar_seg_load.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), lp, C.c_int]
+    L.crispy_diar_seg_loaded.argtypes = [C.c_void_p]
+    L.crispy_diar_seg_forward_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.crispy_diar_seg_scores_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_void_p]
+    L.crispy_diar_seg_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_void_p]
     return L
 
 

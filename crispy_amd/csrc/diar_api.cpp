@@ -17,18 +17,6 @@ using namespace crispy::diar;
 
 namespace {
 
-constexpr size_t kScratchCap = (size_t)2000 << 20;      // per turn, below the 2 GB the header states
-
-struct Carve {
-  char* p = nullptr;
-  size_t used = 0;
-  template <class T> T* take(size_t n) {
-    T* r = p ? reinterpret_cast<T*>(p + used) : nullptr;
-    used += (n * sizeof(T) + 255) & ~(size_t)255;
-    return r;
-  }
-};
-
 int p_max_of(int n) { return std::min(n - 1, std::max((int)std::sqrt((double)n), 2) * 2); }
 
 // Solves every matrix of `descs` (host copies; pointers are device memory) on `st`: the LDS form for n <= kLdsN, the

@@ -1,6 +1,6 @@
-// diar_internal.h -- what the host side (diar_api.cpp, diar_front.cpp) and the device side (diar_kernels.hip,
-// diar_fbank.hip) of the speaker clustering and its front end share: the handle, the descriptors the kernels read from
-// device memory and the launch functions.
+// diar_internal.h -- what the host side (diar_api.cpp, diar_front.cpp, diar_seg_api.cpp) and the device side (diar_kernels.hip,
+// diar_fbank.hip, diar_seg.hip) of the speaker clustering, its front end and the segmentation network share: the handle,
+// the descriptors the kernels read from device memory and the launch functions.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -20,6 +20,7 @@ struct crispy_diar {
   crispy::DevBuf<char> infos;        // crispy_diar_info of a call's recordings
   crispy::DevBuf<char> fbank_tab;    // FbankTables, built with the first fbank call
   crispy::DevBuf<char> fbank_descs;  // FbankChunk and FbankTile lists of a call
+  crispy::DevBuf<float> seg_weights; // the segmentation network as crispy_diar_seg_load laid it out (SegModel); empty until a load
   ~crispy_diar() {
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -27,6 +28,19 @@ struct crispy_diar {
 
 namespace crispy {
 namespace diar {
+
+constexpr size_t kScratchCap = (size_t)2000 << 20;      // a turn's scratch, below the 2 GB the header states
+
+// Pieces of the handle's scratch, each on a 256-byte boundary; with p == NULL it only adds up the size.
+struct Carve {
+  char* p = nullptr;
+  size_t used = 0;
+  template <class T> T* take(size_t n) {
+    T* r = p ? reinterpret_cast<T*>(p + used) : nullptr;
+    used += (n * sizeof(T) + 255) & ~(size_t)255;
+    return r;
+  }
+};
 
 // One matrix of a solve.  A [n][n] is worked on in place (its diagonal ends up holding the eigenvalues, unsorted);
 // V [n][n] accumulates the rotations (NULL: values only); cs [3 * rr_pairs(n)] is the global form's rotation list (c, s, t);
@@ -100,6 +114,56 @@ hipError_t launch_fbank_frames(const FbankTables* d_tab, const void* d_pcm, int 
                                const FbankTile* d_tiles, int n_tiles, float* d_raw, hipStream_t st);
 // feats = raw - column mean over the chunk's frames (in place where d_feats == d_raw)
 hipError_t launch_fbank_means(const FbankChunk* d_chunks, int n_chunks, const float* d_raw, float* d_feats, hipStream_t st);
+
+// ---- segmentation network (diar_seg.hip) ----------------------------------------------------------------------------
+constexpr int kSegWindow = 160000, kSegMinLen = 991, kSegClasses = 7;
+constexpr int kSegTaps0 = 251, kSegStride0 = 10, kSegC0 = 80, kSegC1 = 60, kSegTaps = 5;
+constexpr int kSegHidden = 128, kSegLayers = 4, kSegGates = 4 * kSegHidden;
+
+// Positions after each stage for a window of len samples (integer division throughout); frames is p2.
+struct SegShape {
+  int c0, p0, c1, p1, c2, frames;
+};
+inline SegShape seg_shape(long len) {
+  SegShape s{0, 0, 0, 0, 0, 0};
+  if (len < kSegMinLen) return s;
+  s.c0 = (int)((len - kSegTaps0) / kSegStride0 + 1);
+  s.p0 = s.c0 / 3;
+  s.c1 = s.p0 - (kSegTaps - 1);
+  s.p1 = s.c1 / 3;
+  s.c2 = s.p1 - (kSegTaps - 1);
+  s.frames = s.c2 / 3;
+  return s;
+}
+
+// Where each tensor sits in the handle's device copy, as the kernels read it (offsets in floats from the base).
+// Convolution weights are [(ci * taps + k)][co] (the output channel contiguous), the LSTM's input weights of a layer are the
+// forward rows then the reverse rows [1024][in] with bias_ih + bias_hh [1024] behind them, weight_hh is [2][512][128], the
+// two hidden linear layers are [in][out].
+struct SegModel {
+  const float *wav_g, *wav_b;                      // [1]
+  const float *f0, *w1, *b1, *w2, *b2;             // [251][80]; [400][60], [60]; [300][60], [60]
+  const float *n_g[3], *n_b[3];                    // [80], [60], [60]
+  const float *w_ih[kSegLayers], *b[kSegLayers], *w_hh[kSegLayers];
+  const float *l0, *l0_b, *l1, *l1_b, *cls, *cls_b;      // [256][128], [128]; [128][128], [128]; [7][128], [7]
+};
+
+// float windows [n_win][kSegWindow] from window w0 on of a recording of n samples: i16 (f32: through f32_to_i16) / 32768, zeros behind the end
+hipError_t launch_seg_windows(const void* d_pcm, int pcm_format, long n, long w0, int n_win, float* d_x, hipStream_t st);
+// mean and 1 / sqrt(biased variance + 1e-5) of every channel of x [n_win][P][C] over P -> stats [n_win][C]; C <= 1024
+hipError_t launch_seg_stats(const float* d_x, int n_win, int P, int C, float2* d_stats, hipStream_t st);
+// stage s (0, 1, 2) of the SincNet: the input normalised with `d_stats` (and leaky_relu from stage 1 on) in the load,
+// convolution, abs (stage 0) or bias, max over 3 -> out [n_win][n_pool][co]
+hipError_t launch_seg_conv(int stage, const SegModel& m, const float* d_in, int n_win, int n_in, const float2* d_stats, float* d_out,
+                           int n_pool, hipStream_t st);
+// leaky_relu(instance norm) of the last stage's rows -> [n_win][frames][60]
+hipError_t launch_seg_norm(const SegModel& m, const float* d_in, int n_win, int frames, const float2* d_stats, float* d_out, hipStream_t st);
+// xproj [rows][1024] = x [rows][in] . w_ih^T + b
+hipError_t launch_seg_proj(const float* d_x, long rows, int in, const float* d_w, const float* d_b, float* d_xproj, hipStream_t st);
+// the recurrence of one layer, both directions of every window -> y [n_win][frames][256]
+hipError_t launch_seg_lstm(const float* d_xproj, const float* d_whh, int n_win, int frames, float* d_y, hipStream_t st);
+// linear + leaky_relu twice, classifier, log_softmax -> scores [rows][7]
+hipError_t launch_seg_head(const SegModel& m, const float* d_y, long rows, float* d_scores, hipStream_t st);
 
 }  // namespace diar
 }  // namespace crispy

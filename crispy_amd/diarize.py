@@ -4,7 +4,10 @@ caller's; there is no CPU path for the clustering.  The host functions (`chunk_p
 `format_diarized_text`) need no device.
 
 The front end (crispy_diar_fbank*, crispy_diar_speech_segments): `segmentation_windows`, `speech_segments`, `Diarizer.fbank`
-and `run_diarization`, which is the reference's run_diarization (:276-409) with its two networks as callables."""
+and `run_diarization`, which is the reference's run_diarization (:276-409) with its two networks as callables.
+
+The segmentation network (crispy_diar_seg_*): `Diarizer.load_segmentation`, `seg_forward`, `segmentation_scores[_device]`,
+`seg_frames`, `seg_windows`; with it loaded, `run_diarization(pcm, None, emb_fn, ...)` needs the embedding network alone."""
 from __future__ import annotations
 
 import ctypes as C
@@ -136,6 +139,66 @@ class Diarizer:
                     self._L)
         return (feats, rows, off) if raw else (feats, off)
 
+    # ---- the segmentation network (crispy_diar_seg_*) ----
+    def load_segmentation(self, tensors: dict):
+        """The weights of pyannote segmentation-3.0 by their state-dict keys (`sincnet.conv1d.0.filters` is the evaluated
+        [80, 1, 251] sinc bank): name -> array-like, taken as f32.  A second load replaces the first."""
+        arrs = [np.ascontiguousarray(np.asarray(v, dtype=np.float32)).reshape(-1) for v in tensors.values()]
+        n = len(arrs)
+        names = (C.c_char_p * max(n, 1))(*[str(k).encode("utf-8") for k in tensors])
+        data = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        count = np.ascontiguousarray([a.size for a in arrs], dtype=np.int64)
+        N.check(self._L.crispy_diar_seg_load(self._h, names, data, _p(count, C.c_long), n), self._L)
+
+    @property
+    def segmentation_loaded(self) -> bool:
+        return bool(self._L.crispy_diar_seg_loaded(self._h))
+
+    def seg_forward(self, windows, taps: bool = False, stream=None):
+        """The network on windows of one length: f32 [n_win, len] (numpy or CUDA tensor), 991 <= len <= 160000 ->
+        scores [n_win, frames, 7]; with `taps` also the SincNet output [n_win, frames, 60] and the last LSTM layer's
+        [n_win, frames, 256].  numpy in gives numpy out, a CUDA tensor gives CUDA tensors."""
+        import torch
+        host = not isinstance(windows, torch.Tensor)
+        x = torch.from_numpy(np.ascontiguousarray(windows, dtype=np.float32)).cuda() if host else windows.contiguous()
+        if x.dim() != 2 or x.dtype != torch.float32:
+            raise ValueError("windows must be f32 [n_win, len]")
+        n_win, ln = int(x.shape[0]), int(x.shape[1])
+        fr = seg_frames(ln)
+        scores = torch.empty((n_win, fr, N.SEG_CLASSES), dtype=torch.float32, device=x.device)
+        sinc = torch.empty((n_win, fr, 60), dtype=torch.float32, device=x.device) if taps else None
+        lstm = torch.empty((n_win, fr, 256), dtype=torch.float32, device=x.device) if taps else None
+        if stream is None:      # the handle's stream does not wait for torch's
+            torch.cuda.current_stream(x.device).synchronize()
+        N.check(self._L.crispy_diar_seg_forward_device(self._h, x.data_ptr() if x.numel() else None, n_win, ln, scores.data_ptr() if fr else None,
+                                                       sinc.data_ptr() if taps else None, lstm.data_ptr() if taps else None, stream), self._L)
+        out = (scores, sinc, lstm) if taps else (scores,)
+        if host:
+            out = tuple(o.cpu().numpy() for o in out)
+        return out if taps else out[0]
+
+    def segmentation_scores(self, pcm) -> np.ndarray:
+        """pyannote_get_segments_fixed up to the network's output (:103-145) for a whole recording.  pcm: 16 kHz mono numpy
+        int16 or float32 (f32 goes through f32_to_i16 on the device) -> f32 [n_windows, 589, 7], what speech_segments takes."""
+        pcm = np.ascontiguousarray(pcm)
+        fmt = _pcm_format(pcm.dtype)
+        scores = np.zeros((seg_windows(pcm.size), N.SEG_FRAMES, N.SEG_CLASSES), np.float32)
+        N.check(self._L.crispy_diar_seg_scores(self._h, pcm.ctypes.data if pcm.size else None, fmt, pcm.size,
+                                               scores.ctypes.data if scores.size else None), self._L)
+        return scores
+
+    def segmentation_scores_device(self, pcm, stream=None):
+        """The same on a CUDA int16 or float32 tensor -> f32 CUDA tensor [n_windows, 589, 7]."""
+        import torch
+        fmt = _pcm_format(pcm.dtype)
+        n = int(pcm.numel())
+        scores = torch.empty((seg_windows(n), N.SEG_FRAMES, N.SEG_CLASSES), dtype=torch.float32, device=pcm.device)
+        if stream is None:
+            torch.cuda.current_stream(pcm.device).synchronize()
+        N.check(self._L.crispy_diar_seg_scores_device(self._h, pcm.data_ptr() if n else None, fmt, n,
+                                                      scores.data_ptr() if scores.numel() else None, stream), self._L)
+        return scores
+
 
 def _pcm_format(dtype) -> int:
     name = str(dtype).replace("torch.", "")
@@ -197,15 +260,30 @@ def speech_segments(scores, n_samples: int, merge_gap: float, sample_rate: int =
     return [(float(os_[i]), float(oe[i]), int(of[i]), int(ol[i])) for i in range(cnt)]
 
 
+def seg_frames(n: int) -> int:
+    """Frames the segmentation network gives for a window of n samples (589 at 160000, 0 below 991)."""
+    return int(N.lib().crispy_diar_seg_frames(int(n)))
+
+
+def seg_windows(n: int) -> int:
+    """Windows of a recording of n samples: 0 for 0, else ceil(n / 160000) + 1."""
+    return int(N.lib().crispy_diar_seg_windows(int(n)))
+
+
 def run_diarization(pcm, seg_fn, emb_fn, max_speakers: int, merge_gap: float, diarizer: "Diarizer"):
-    """run_diarization (:276-409) with the two networks as callables.  pcm: 16 kHz mono, f32 in [-1, 1] (taken through
-    f32_to_i16) or int16; seg_fn(window f32 [160000]) -> [frames, classes]; emb_fn(features f32 [frames, 80]) -> [dim].
-    -> merged [(start, end, speaker number >= 1)]."""
+    """run_diarization (:276-409).  pcm: 16 kHz mono, f32 in [-1, 1] (taken through f32_to_i16) or int16;
+    seg_fn(window f32 [160000]) -> [frames, classes], or None for the network loaded into `diarizer`
+    (Diarizer.load_segmentation); emb_fn(features f32 [frames, 80]) -> [dim].  -> merged [(start, end, speaker number >= 1)]."""
     pcm = np.asarray(pcm)
     x = pcm if pcm.dtype == np.int16 else f32_to_i16(pcm)
+    if seg_fn is None and not diarizer.segmentation_loaded:
+        raise ValueError("run_diarization: seg_fn is None and no segmentation network is loaded (Diarizer.load_segmentation)")
     if x.size == 0:
         return []
-    scores = np.stack([np.asarray(seg_fn(w), np.float32) for w in segmentation_windows(x)])
+    if seg_fn is None:
+        scores = diarizer.segmentation_scores(x)
+    else:
+        scores = np.stack([np.asarray(seg_fn(w), np.float32) for w in segmentation_windows(x)])
     segments = speech_segments(scores, x.size, merge_gap)
     if not segments:
         return []

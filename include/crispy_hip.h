@@ -1139,6 +1139,62 @@ int crispy_diar_fbank_device(void *h, const void *d_pcm, int pcm_format, const l
 int crispy_diar_fbank(void *h, const void *pcm, int pcm_format, const long *first, const long *len, int n_chunks, float scale,
                       float *feats, long *frame_offset);
 
+/* ------------------------------------------------------------------------------------------
+ * Segmentation network: the first `session.run` of run_diarization (pyannote_get_segments_fixed, :103-145) on a crispy_diar
+ * handle -- pyannote segmentation-3.0 ("PyanNet": SincNet, a 4-layer bidirectional LSTM, three linear layers), 16 kHz
+ * samples in, log-probabilities [frames][7] out, f32 operands and f32 sums throughout.  New entry points only: no struct
+ * grew, the ABI version is unchanged.  The embedding network stays the host's.
+ *
+ * The network on one window x[len] (samples as i16 / 32768):
+ *   wav_norm1d   InstanceNorm1d(1, affine) over the window: mean and biased variance over len, eps 1e-5, gamma, beta.
+ *   conv1d.0     80 filters x 251 taps, stride 10, no bias, no padding (the evaluated sinc filter bank, a plain
+ *                [80][1][251] tensor), abs, MaxPool1d(3, 3) (floor), InstanceNorm1d(80, affine) over time, leaky_relu(0.01).
+ *   conv1d.1     Conv1d(80, 60, 5) with bias, pool 3, InstanceNorm1d(60, affine), leaky_relu.
+ *   conv1d.2     Conv1d(60, 60, 5) with bias, pool 3, InstanceNorm1d(60, affine), leaky_relu -> [frames][60].
+ *   lstm         4 layers, bidirectional, hidden 128 (input 60, then 256), torch layout and gate order i, f, g, o; a
+ *                layer's output is forward | reverse, [frames][256].
+ *   head         Linear(256, 128) + leaky_relu, Linear(128, 128) + leaky_relu, Linear(128, 7), log_softmax.
+ *   frames(len) = ((((len - 251) / 10 + 1) / 3 - 4) / 3 - 4) / 3 in integer division: 589 at 160000, 1 at 991.
+ *
+ * Device work: every instance norm is a two-pass reduction about the row's first value (a constant row normalises to
+ * beta exactly); each convolution is one kernel with the previous norm and leaky_relu applied in its load and abs or bias
+ * and the max over 3 in its store, so that no pre-pool value reaches memory; per LSTM layer the input projection of all
+ * frames, windows and both directions is one GEMM, and the recurrence is one workgroup of 512 threads per (window,
+ * direction) with row g of weight_hh in thread g's registers, h and the four gates of a cell in LDS and c in registers,
+ * exp and tanh in their accurate forms; the head takes 8 frame rows per workgroup.  The order of every sum depends on
+ * the window's own length alone: a window's scores are the same bytes alone and in any batch or turn.
+ * Scratch is the handle's (grow and keep): 6.6 MB per full window, windows taken in turns below 2 GB.
+ *
+ *   crispy_diar_seg_frames   the formula above; 0 below 991 samples.  No device.
+ *   crispy_diar_seg_windows  windows crispy_diar_seg_scores gives for n samples: 0 for 0, else ceil(n / 160000) + 1.
+ *   crispy_diar_seg_load     host tensors by name (pyannote's state-dict keys), data[i] holding count[i] floats:
+ *       sincnet.wav_norm1d.{weight,bias} [1]; sincnet.conv1d.0.filters [80][1][251]; sincnet.conv1d.1.{weight,bias}
+ *       [60][80][5], [60]; sincnet.conv1d.2.{weight,bias} [60][60][5], [60]; sincnet.norm1d.{0,1,2}.{weight,bias} [80],
+ *       [60], [60]; lstm.{weight_ih,weight_hh,bias_ih,bias_hh}_l{0..3}[_reverse] [512][in], [512][128], [512], [512];
+ *       linear.0.{weight,bias} [128][256], [128]; linear.1.{weight,bias} [128][128], [128]; classifier.{weight,bias}
+ *       [7][128], [7] -- 51 tensors.  A missing, repeated or unknown name, a count that is not the tensor's size, a NULL
+ *       pointer or a non-finite value is CRISPY_ERR_INVALID_ARG with the tensor's name in the message, before the device is
+ *       touched.  A second load replaces the first; the handle owns the device copy.
+ *   crispy_diar_seg_loaded   1 after a successful load, else 0 (NULL handle: 0).
+ *   crispy_diar_seg_forward_device  the network on n_win windows d_x [n_win][len] of one length 991 <= len <= 160000,
+ *       1 <= n_win <= 4096 -> d_scores [n_win][frames(len)][7]; stage outputs for tests and profiling: d_sincnet
+ *       (nullable) [n_win][frames][60], d_lstm (nullable) [n_win][frames][256], the last layer's.  Enqueued on hip_stream
+ *       (NULL: the handle's own), complete on return.  Before a load: CRISPY_ERR_INVALID_ARG.
+ *   crispy_diar_seg_scores_device / crispy_diar_seg_scores  a whole recording: d_pcm is CRISPY_PCM_I16 or CRISPY_PCM_F32
+ *       (f32_to_i16 on the device, as the fbank does); the zero padding to a multiple of 160000 plus one more window and the
+ *       / 32768 are formed on the device -> d_scores [crispy_diar_seg_windows(n_samples)][589][7], what
+ *       crispy_diar_speech_segments takes.  1 <= n_samples <= 115 200 000 (2 h); checked before any launch.  The second
+ *       form takes pcm and scores on the host.  There is no CPU path.
+ * ------------------------------------------------------------------------------------------ */
+long crispy_diar_seg_frames(long len);
+long crispy_diar_seg_windows(long n_samples);
+int crispy_diar_seg_load(void *h, const char *const *names, const float *const *data, const long *count, int n_tensors);
+int crispy_diar_seg_loaded(void *h);
+int crispy_diar_seg_forward_device(void *h, const float *d_x, int n_win, long len, float *d_scores, float *d_sincnet, float *d_lstm,
+                                   void *hip_stream);
+int crispy_diar_seg_scores_device(void *h, const void *d_pcm, int pcm_format, long n_samples, float *d_scores, void *hip_stream);
+int crispy_diar_seg_scores(void *h, const void *pcm, int pcm_format, long n_samples, float *scores);
+
 #ifdef __cplusplus
 }
 #endif
