@@ -341,6 +341,15 @@ extern "C" {
     pub fn crispy_diar_seg_forward_device(h: *mut c_void, d_x: *const c_float, n_win: c_int, len: c_long, d_scores: *mut c_float, d_sincnet: *mut c_float, d_lstm: *mut c_float, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_diar_seg_scores_device(h: *mut c_void, d_pcm: *const c_void, pcm_format: c_int, n_samples: c_long, d_scores: *mut c_float, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_diar_seg_scores(h: *mut c_void, pcm: *const c_void, pcm_format: c_int, n_samples: c_long, scores: *mut c_float) -> c_int;
+    // the embedding network (WeSpeaker CAMPPlus) on a crispy_diar handle: EmbeddingExtractor::compute for all chunks in one call
+    pub fn crispy_diar_emb_frames(rows: c_long) -> c_long;
+    pub fn crispy_diar_emb_tensor_spec(i: c_int, dim: c_int, name: *mut *const c_char, count: *mut c_long) -> c_int;
+    pub fn crispy_diar_emb_load(h: *mut c_void, names: *const *const c_char, data: *const *const c_float, count: *const c_long, n_tensors: c_int) -> c_int;
+    pub fn crispy_diar_emb_loaded(h: *mut c_void) -> c_int;
+    pub fn crispy_diar_emb_dim(h: *mut c_void) -> c_int;
+    pub fn crispy_diar_emb_forward_device(h: *mut c_void, d_feats: *const c_float, frame_offset: *const c_long, n_chunks: c_int, d_emb: *mut c_float, d_head: *mut c_float, d_xvec: *mut c_float, d_stats: *mut c_float, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_diar_embed_device(h: *mut c_void, d_pcm: *const c_void, pcm_format: c_int, first: *const c_long, len: *const c_long, n_chunks: c_int, scale: c_float, d_emb: *mut c_float, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_diar_embed(h: *mut c_void, pcm: *const c_void, pcm_format: c_int, first: *const c_long, len: *const c_long, n_chunks: c_int, scale: c_float, emb: *mut c_float) -> c_int;
 }
 
 // ------------------------------------------------------------------------------------------------------------

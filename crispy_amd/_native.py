@@ -70,7 +70,10 @@ DIAR_SYMBOLS = ("crispy_diar_create", "crispy_diar_destroy", "crispy_diar_cluste
 DIAR_FRONT_SYMBOLS = ("crispy_diar_fbank_frames", "crispy_diar_speech_segments", "crispy_diar_fbank_device", "crispy_diar_fbank")
 DIAR_SEG_SYMBOLS = ("crispy_diar_seg_frames", "crispy_diar_seg_windows", "crispy_diar_seg_load", "crispy_diar_seg_loaded",
                     "crispy_diar_seg_forward_device", "crispy_diar_seg_scores_device", "crispy_diar_seg_scores")
-ALL_SYMBOLS = RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS + DIAR_SYMBOLS + DIAR_FRONT_SYMBOLS + DIAR_SEG_SYMBOLS
+DIAR_EMB_SYMBOLS = ("crispy_diar_emb_frames", "crispy_diar_emb_tensor_spec", "crispy_diar_emb_load", "crispy_diar_emb_loaded",
+                    "crispy_diar_emb_dim", "crispy_diar_emb_forward_device", "crispy_diar_embed_device", "crispy_diar_embed")
+ALL_SYMBOLS = RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS + DIAR_SYMBOLS + DIAR_FRONT_SYMBOLS + DIAR_SEG_SYMBOLS + DIAR_EMB_SYMBOLS
+EMB_HEAD, EMB_XVEC, EMB_STATS, EMB_MIN_ROWS, EMB_MAX_ROWS, EMB_TENSORS = 320, 512, 1024, 3, 30000, 815      # crispy_amd/csrc/diar_internal.h
 SEG_WINDOW, SEG_MIN_LEN, SEG_FRAMES, SEG_CLASSES = 160000, 991, 589, 7      # crispy_amd/csrc/diar_internal.h
 SEG_MAX_SAMPLES, SEG_MAX_WINDOWS = 115200000, 4096
 FBANK_BINS, FBANK_WAVE_FRAMES, FBANK_TILE_FRAMES = 80, 8, 32      # crispy_amd/csrc/diar_internal.h
@@ -342,6 +345,15 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_diar_seg_forward_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.crispy_diar_seg_scores_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_void_p]
     L.crispy_diar_seg_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_void_p]
+    L.crispy_diar_emb_frames.argtypes = [C.c_long]
+    L.crispy_diar_emb_frames.restype = C.c_long
+    L.crispy_diar_emb_tensor_spec.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), lp]
+    L.crispy_diar_emb_load.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), lp, C.c_int]
+    L.crispy_diar_emb_loaded.argtypes = [C.c_void_p]
+    L.crispy_diar_emb_dim.argtypes = [C.c_void_p]
+    L.crispy_diar_emb_forward_device.argtypes = [C.c_void_p, C.c_void_p, lp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.crispy_diar_embed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, lp, lp, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+    L.crispy_diar_embed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, lp, lp, C.c_int, C.c_float, C.c_void_p]
     return L
 
 

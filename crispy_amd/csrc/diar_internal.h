@@ -1,6 +1,6 @@
-// diar_internal.h -- what the host side (diar_api.cpp, diar_front.cpp, diar_seg_api.cpp) and the device side (diar_kernels.hip,
-// diar_fbank.hip, diar_seg.hip) of the speaker clustering, its front end and the segmentation network share: the handle,
-// the descriptors the kernels read from device memory and the launch functions.
+// diar_internal.h -- what the host side (diar_api.cpp, diar_front.cpp, diar_seg_api.cpp, diar_emb_api.cpp) and the device side
+// (diar_kernels.hip, diar_fbank.hip, diar_seg.hip, diar_emb.hip) of the speaker clustering, its front end and the two networks
+// share: the handle, the descriptors the kernels read from device memory and the launch functions.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -21,6 +21,9 @@ struct crispy_diar {
   crispy::DevBuf<char> fbank_tab;    // FbankTables, built with the first fbank call
   crispy::DevBuf<char> fbank_descs;  // FbankChunk and FbankTile lists of a call
   crispy::DevBuf<float> seg_weights; // the segmentation network as crispy_diar_seg_load laid it out (SegModel); empty until a load
+  crispy::DevBuf<float> emb_weights; // the embedding network as crispy_diar_emb_load laid it out (EmbModel); empty until a load
+  int emb_dim = 0;                   // its embedding width; 0 until a load
+  crispy::DevBuf<char> emb_tab;      // the row, position and segment offsets of a call's chunks, turn by turn
   ~crispy_diar() {
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -164,6 +167,68 @@ hipError_t launch_seg_proj(const float* d_x, long rows, int in, const float* d_w
 hipError_t launch_seg_lstm(const float* d_xproj, const float* d_whh, int n_win, int frames, float* d_y, hipStream_t st);
 // linear + leaky_relu twice, classifier, log_softmax -> scores [rows][7]
 hipError_t launch_seg_head(const SegModel& m, const float* d_y, long rows, float* d_scores, hipStream_t st);
+
+// ---- embedding network (diar_emb.hip) -------------------------------------------------------------------------------
+// WeSpeaker CAMPPlus.  Every constant of the network on the device side is here, once.
+constexpr int kEmbFeat = kFbankBins, kEmbHeadCh = 32, kEmbHeadOut = 320, kEmbHeadConvs = 12;
+constexpr int kEmbTdnnTaps = 5, kEmbTdnnStride = 2, kEmbInit = 128, kEmbGrowth = 32, kEmbBn = 128, kEmbGate = 64 /* 128 / reduction 2 */;
+constexpr int kEmbSegLen = 100, kEmbBlocks = 3, kEmbLayers = 52, kEmbXvec = 512, kEmbStats = 2 * kEmbXvec, kEmbMaxDim = 1024;
+constexpr int kEmbBlockLayers[kEmbBlocks] = {12, 24, 16}, kEmbBlockDilation[kEmbBlocks] = {1, 2, 2};
+constexpr int kEmbBlockWidth[kEmbBlocks] = {512, 1024, 1024};      // channels of a block's buffer once its last layer has appended
+constexpr double kEmbBnEps = 1e-5;
+constexpr float kEmbPoolEps = 1e-7f;
+constexpr int kEmbMinRows = 3, kEmbMaxRows = 30000;
+
+inline long emb_frames(long rows) { return rows < 1 ? 0 : (rows - 1) / kEmbTdnnStride + 1; }
+inline long emb_segments(long t2) { return (t2 + kEmbSegLen - 1) / kEmbSegLen; }
+
+// Where each tensor sits in the handle's device copy, as the kernels read it.  Every BatchNorm is a (scale, shift) pair folded
+// at load; convolution weights have the output channel contiguous: the head's [(kf * 3 + kt) * ci_n + ci][32], the tdnn's
+// [(k * 320 + ci)][128], linear1 [ci][128], linear_local [(k * 128 + ci)][32], the gate's [128][64] and [64][32], a transit's
+// [ci][ci / 2], the last dense [1024][dim].
+struct EmbConv {
+  const float *w, *scale, *shift;
+};
+struct EmbDense {
+  const float *s1, *h1, *w1, *s2, *h2, *wl, *g1, *b1, *g2, *b2;
+  int c_in, dilation;
+};
+struct EmbTransit {
+  const float *s, *h, *w;
+  int c_in;
+};
+struct EmbModel {
+  EmbConv head[kEmbHeadConvs];      // conv1; layer1.0 conv1, conv2, shortcut; layer1.1 conv1, conv2; layer2 likewise; conv2
+  EmbConv tdnn;
+  EmbDense layer[kEmbLayers];
+  EmbTransit transit[kEmbBlocks];
+  const float *out_s, *out_h;       // out_nonlinear, applied in the last transit's store
+  EmbConv dense;
+  int dim;
+};
+// A turn's chunks: chunk c has rows row_off[c] ... row_off[c + 1] of the input, positions t2_off[c] ... after the tdnn and
+// context segments seg_off[c] ... (all relative to the turn's buffers, in device memory).
+struct EmbTables {
+  const int *row_off, *t2_off, *seg_off;
+  int n_chunks, max_rows, max_t2;
+};
+
+// head convolution `idx` (the order of EmbModel::head) on rows [rows][f_in][c_in] -> [rows][f_out][32]; `res` (nullable) is added
+// before the ReLU; the last one stores [rows][320] with channel c * 10 + f
+hipError_t launch_emb_head_conv(int idx, const EmbModel& m, const EmbTables& t, const float* d_in, const float* d_res, float* d_out, hipStream_t st);
+// [rows][320] -> columns 0 ... 127 of the first block's buffer [t2][512]
+hipError_t launch_emb_tdnn(const EmbModel& m, const EmbTables& t, const float* d_head, float* d_blk, hipStream_t st);
+// C [M][N] (row stride ldc) = epilogue(relu(A [M][K] (row stride lda) * in_s + in_h) . Bt [K][N]) on the f32 matrix instruction;
+// epilogue: relu(v * out_s + out_h), or plain with out_s NULL.  K is a multiple of 32, N of 128.
+hipError_t launch_emb_gemm(const float* d_a, int lda, int K, const float* in_s, const float* in_h, const float* d_bt, int N, const float* out_s,
+                           const float* out_h, float* d_c, int ldc, long M, hipStream_t st);
+// the gate vectors [segments][32] of every chunk from h [t2][128]; d_segsum [segments][128] is scratch
+hipError_t launch_emb_gates(const EmbDense& l, const EmbTables& t, const float* d_h, float* d_segsum, float* d_gates, hipStream_t st);
+// linear_local of h times the gate -> columns c_in ... c_in + 31 of the block's buffer (row stride ldc)
+hipError_t launch_emb_local(const EmbDense& l, const EmbTables& t, const float* d_h, const float* d_gates, float* d_blk, int ldc, hipStream_t st);
+// xvec [t2][512] -> stats [n_chunks][1024]: mean, then sqrt(unbiased variance + 1e-7)
+hipError_t launch_emb_pool(const EmbTables& t, const float* d_xvec, float* d_stats, hipStream_t st);
+hipError_t launch_emb_dense(const EmbModel& m, const EmbTables& t, const float* d_stats, float* d_emb, hipStream_t st);
 
 }  // namespace diar
 }  // namespace crispy

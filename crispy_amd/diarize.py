@@ -7,7 +7,10 @@ The front end (crispy_diar_fbank*, crispy_diar_speech_segments): `segmentation_w
 and `run_diarization`, which is the reference's run_diarization (:276-409) with its two networks as callables.
 
 The segmentation network (crispy_diar_seg_*): `Diarizer.load_segmentation`, `seg_forward`, `segmentation_scores[_device]`,
-`seg_frames`, `seg_windows`; with it loaded, `run_diarization(pcm, None, emb_fn, ...)` needs the embedding network alone."""
+`seg_frames`, `seg_windows`; with it loaded, `run_diarization(pcm, None, emb_fn, ...)` needs the embedding network alone.
+
+The embedding network (crispy_diar_emb_*, crispy_diar_embed*): `Diarizer.load_embedding`, `embed`, `embed_chunks[_device]`,
+`emb_frames`, `emb_tensor_spec`; with both loaded, `run_diarization(pcm, None, None, ...)` needs no callable at all."""
 from __future__ import annotations
 
 import ctypes as C
@@ -199,6 +202,88 @@ class Diarizer:
                                                       scores.data_ptr() if scores.numel() else None, stream), self._L)
         return scores
 
+    # ---- the embedding network (crispy_diar_emb_*) ----
+    def load_embedding(self, tensors: dict):
+        """The weights of WeSpeaker CAMPPlus by their state-dict keys: name -> array-like, taken as f32 (`*.num_batches_tracked`
+        entries are dropped, so a torch state dict goes in as it is).  A second load replaces the first."""
+        items = [(str(k), v) for k, v in tensors.items() if not str(k).endswith("num_batches_tracked")]
+        arrs = [np.ascontiguousarray(np.asarray(v, dtype=np.float32)).reshape(-1) for _k, v in items]
+        n = len(arrs)
+        names = (C.c_char_p * max(n, 1))(*[k.encode("utf-8") for k, _v in items])
+        data = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        count = np.ascontiguousarray([a.size for a in arrs], dtype=np.int64)
+        N.check(self._L.crispy_diar_emb_load(self._h, names, data, _p(count, C.c_long), n), self._L)
+
+    @property
+    def embedding_loaded(self) -> bool:
+        return bool(self._L.crispy_diar_emb_loaded(self._h))
+
+    @property
+    def embedding_dim(self) -> int:
+        return int(self._L.crispy_diar_emb_dim(self._h))
+
+    def embed(self, feats_list, taps: bool = False, stream=None):
+        """The network on a list of chunks, each f32 [rows, 80] with 3 <= rows <= 30000 (numpy arrays or CUDA tensors), in one
+        call -> embeddings [n_chunks, dim]; with `taps` also the head's output (a list of [rows, 320]), the rows in front of the
+        pooling (a list of [emb_frames(rows), 512]) and the statistics [n_chunks, 1024].  numpy in gives numpy out, CUDA tensors
+        give CUDA tensors."""
+        import torch
+        host = not (len(feats_list) and isinstance(feats_list[0], torch.Tensor))
+        if host:
+            rows = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, N.FBANK_BINS) for f in feats_list]
+            x = torch.from_numpy(np.concatenate(rows, 0) if rows else np.zeros((0, N.FBANK_BINS), np.float32)).cuda()
+        else:
+            rows = [f.reshape(-1, N.FBANK_BINS) for f in feats_list]
+            x = torch.cat(rows, 0).contiguous()
+            if x.dtype != torch.float32:
+                raise ValueError("features must be f32 [rows, 80]")
+        n = len(rows)
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum([int(r.shape[0]) for r in rows])
+        t2 = [emb_frames(int(r.shape[0])) for r in rows]
+        dim = self.embedding_dim
+        emb = torch.empty((n, dim), dtype=torch.float32, device=x.device)
+        head = torch.empty((int(off[-1]), N.EMB_HEAD), dtype=torch.float32, device=x.device) if taps else None
+        xvec = torch.empty((sum(t2), N.EMB_XVEC), dtype=torch.float32, device=x.device) if taps else None
+        stats = torch.empty((n, N.EMB_STATS), dtype=torch.float32, device=x.device) if taps else None
+        if stream is None:      # the handle's stream does not wait for torch's
+            torch.cuda.current_stream(x.device).synchronize()
+        N.check(self._L.crispy_diar_emb_forward_device(self._h, x.data_ptr() if x.numel() else None, _p(off, C.c_long), n,
+                                                       emb.data_ptr() if emb.numel() else None, head.data_ptr() if taps else None,
+                                                       xvec.data_ptr() if taps else None, stats.data_ptr() if taps else None, stream), self._L)
+        if not taps:
+            return emb.cpu().numpy() if host else emb
+        q = np.concatenate([[0], np.cumsum(t2)])
+        heads = [head[off[c]:off[c + 1]] for c in range(n)]
+        xvecs = [xvec[q[c]:q[c + 1]] for c in range(n)]
+        if host:
+            return emb.cpu().numpy(), [t.cpu().numpy() for t in heads], [t.cpu().numpy() for t in xvecs], stats.cpu().numpy()
+        return emb, heads, xvecs, stats
+
+    def embed_chunks(self, pcm, chunks, scale: float = 1.0) -> np.ndarray:
+        """EmbeddingExtractor::compute (:53-75) for all chunks of a recording in one call.  pcm: 16 kHz mono numpy int16 or float32
+        (f32 goes through f32_to_i16 on the device); chunks: (first sample, n samples) pairs, each of at least 3 feature rows
+        (fbank_frames) -> f32 [n_chunks, dim].  The feature rows stay on the device."""
+        pcm = np.ascontiguousarray(pcm)
+        fmt = _pcm_format(pcm.dtype)
+        first, ln, _off = _chunk_arrays(chunks)
+        emb = np.zeros((len(first), self.embedding_dim), np.float32)
+        N.check(self._L.crispy_diar_embed(self._h, pcm.ctypes.data if pcm.size else None, fmt, _p(first, C.c_long), _p(ln, C.c_long), len(first),
+                                          float(scale), emb.ctypes.data if emb.size else None), self._L)
+        return emb
+
+    def embed_chunks_device(self, pcm, chunks, scale: float = 1.0, stream=None):
+        """The same on a CUDA int16 or float32 tensor -> f32 CUDA tensor [n_chunks, dim]."""
+        import torch
+        fmt = _pcm_format(pcm.dtype)
+        first, ln, _off = _chunk_arrays(chunks)
+        emb = torch.empty((len(first), self.embedding_dim), dtype=torch.float32, device=pcm.device)
+        if stream is None:
+            torch.cuda.current_stream(pcm.device).synchronize()
+        N.check(self._L.crispy_diar_embed_device(self._h, pcm.data_ptr() if pcm.numel() else None, fmt, _p(first, C.c_long), _p(ln, C.c_long),
+                                                 len(first), float(scale), emb.data_ptr() if emb.numel() else None, stream), self._L)
+        return emb
+
 
 def _pcm_format(dtype) -> int:
     name = str(dtype).replace("torch.", "")
@@ -270,14 +355,36 @@ def seg_windows(n: int) -> int:
     return int(N.lib().crispy_diar_seg_windows(int(n)))
 
 
+def emb_frames(rows: int) -> int:
+    """Positions the embedding network keeps of `rows` feature rows after its stride-2 layer: (rows - 1) // 2 + 1, 0 without rows."""
+    return int(N.lib().crispy_diar_emb_frames(int(rows)))
+
+
+def emb_tensor_spec(dim: int = 512):
+    """The tensors Diarizer.load_embedding expects for an embedding width `dim`: [(state-dict key, element count)]."""
+    L = N.lib()
+    name, count = C.c_char_p(), C.c_long()
+    n = L.crispy_diar_emb_tensor_spec(0, int(dim), None, None)
+    N.check(min(n, 0), L)
+    out = []
+    for i in range(n):
+        N.check(min(L.crispy_diar_emb_tensor_spec(i, int(dim), C.byref(name), C.byref(count)), 0), L)
+        out.append((name.value.decode("utf-8"), int(count.value)))
+    return out
+
+
 def run_diarization(pcm, seg_fn, emb_fn, max_speakers: int, merge_gap: float, diarizer: "Diarizer"):
     """run_diarization (:276-409).  pcm: 16 kHz mono, f32 in [-1, 1] (taken through f32_to_i16) or int16;
     seg_fn(window f32 [160000]) -> [frames, classes], or None for the network loaded into `diarizer`
-    (Diarizer.load_segmentation); emb_fn(features f32 [frames, 80]) -> [dim].  -> merged [(start, end, speaker number >= 1)]."""
+    (Diarizer.load_segmentation); emb_fn(features f32 [frames, 80]) -> [dim], or None for the network loaded into `diarizer`
+    (Diarizer.load_embedding: all chunks in one call, the features staying on the device; a chunk of fewer than 3 feature rows
+    is dropped like one without rows).  -> merged [(start, end, speaker number >= 1)]."""
     pcm = np.asarray(pcm)
     x = pcm if pcm.dtype == np.int16 else f32_to_i16(pcm)
     if seg_fn is None and not diarizer.segmentation_loaded:
         raise ValueError("run_diarization: seg_fn is None and no segmentation network is loaded (Diarizer.load_segmentation)")
+    if emb_fn is None and not diarizer.embedding_loaded:
+        raise ValueError("run_diarization: emb_fn is None and no embedding network is loaded (Diarizer.load_embedding)")
     if x.size == 0:
         return []
     if seg_fn is None:
@@ -288,6 +395,13 @@ def run_diarization(pcm, seg_fn, emb_fn, max_speakers: int, merge_gap: float, di
     if not segments:
         return []
     plan = chunk_plan([(s, e, n) for s, e, _first, n in segments])
+    if emb_fn is None:
+        keep = [c for c in range(len(plan)) if fbank_frames(plan[c][4]) >= N.EMB_MIN_ROWS]
+        if not keep:
+            return []
+        emb = diarizer.embed_chunks(x, [(segments[plan[c][2]][2] + plan[c][3], plan[c][4]) for c in keep])
+        labels = diarizer.cluster([emb], max(int(max_speakers), 1))[0][0]
+        return speaker_segments([plan[c][0] for c in keep], [plan[c][1] for c in keep], labels, merge_gap)
     feats = diarizer.fbank(x, [(segments[seg][2] + first, n) for _s, _e, seg, first, n in plan])
     keep = [c for c in range(len(plan)) if len(feats[c])]      # `if let Ok(embedding)`: a chunk without frames is dropped
     if not keep:

@@ -1143,7 +1143,7 @@ int crispy_diar_fbank(void *h, const void *pcm, int pcm_format, const long *firs
  * Segmentation network: the first `session.run` of run_diarization (pyannote_get_segments_fixed, :103-145) on a crispy_diar
  * handle -- pyannote segmentation-3.0 ("PyanNet": SincNet, a 4-layer bidirectional LSTM, three linear layers), 16 kHz
  * samples in, log-probabilities [frames][7] out, f32 operands and f32 sums throughout.  New entry points only: no struct
- * grew, the ABI version is unchanged.  The embedding network stays the host's.
+ * grew, the ABI version is unchanged.  The embedding network follows below.
  *
  * The network on one window x[len] (samples as i16 / 32768):
  *   wav_norm1d   InstanceNorm1d(1, affine) over the window: mean and biased variance over len, eps 1e-5, gamma, beta.
@@ -1194,6 +1194,70 @@ int crispy_diar_seg_forward_device(void *h, const float *d_x, int n_win, long le
                                    void *hip_stream);
 int crispy_diar_seg_scores_device(void *h, const void *d_pcm, int pcm_format, long n_samples, float *d_scores, void *hip_stream);
 int crispy_diar_seg_scores(void *h, const void *pcm, int pcm_format, long n_samples, float *scores);
+
+/* ------------------------------------------------------------------------------------------
+ * Embedding network: the `session.run` of EmbeddingExtractor::compute (:53-75) on a crispy_diar handle -- WeSpeaker CAMPPlus
+ * ("CAM++", wespeaker_en_voxceleb_CAM++.onnx: input "feats" [1][T][80], output "embs" [dim]), the fbank rows of
+ * crispy_diar_fbank in, one embedding per chunk out, f32 operands and f32 sums throughout.  New entry points only: no
+ * struct grew, the ABI version is unchanged.  With it run_diarization needs no network from the host.
+ *
+ * The network on one chunk [T][80] (every BatchNorm at inference, eps 1e-5; "BR" = BatchNorm, ReLU):
+ *   head (FCM)   on [1][80][T], frequency strided, time never: Conv2d(1, 32, 3x3, pad 1) BR; layer1 and layer2, each two
+ *                BasicResBlocks of 32 channels (conv 3x3 stride (s, 1) BR, conv 3x3 B, + shortcut, ReLU; block .0 has s = 2
+ *                and a 1x1 stride (2, 1) convolution + B as shortcut, block .1 s = 1 and the identity): 80 -> 40 -> 20;
+ *                Conv2d(32, 32, 3x3, stride (2, 1)) BR -> [32][10][T] -> [T][320], channel c * 10 + f.
+ *   tdnn         Conv1d(320, 128, 5, stride 2, pad 2) BR -> T2 = (T - 1) / 2 + 1 positions.
+ *   blocks       12 layers at dilation 1, 24 at 2, 16 at 2, growth 32; a layer with Cin inputs: BR, Conv1d(Cin, 128, 1), BR = h;
+ *                y = Conv1d(128, 32, 3, dilation d, pad d)(h); ctx = mean over time of h + mean of h over consecutive
+ *                segments of 100 positions (the last one over its own count); out = y * sigmoid(Conv1d(64, 32, 1)(relu(
+ *                Conv1d(128, 64, 1)(ctx)))), appended.  After each block a transit: BR, Conv1d(C, C / 2, 1).  Channels
+ *                128 -> 512 -> 256 -> 1024 -> 512 -> 1024 -> 512.
+ *   pooling      BR, then mean and sqrt(unbiased variance + 1e-7) over time -> [1024]; Conv1d(1024, dim, 1); BatchNorm
+ *                without affine terms -> [dim].
+ * The unbiased variance needs T2 >= 2: a chunk of fewer than 3 rows is refused (CRISPY_ERR_INVALID_ARG) before any launch;
+ * run_diarization drops such chunks as it drops chunks without rows.
+ *
+ * Device work: every BatchNorm is folded at load into a (scale, shift) pair in double, rounded once.  Rows are time-major
+ * from the tdnn on; a block is one buffer whose layers append in place.  Every 1x1 convolution (linear1 of the 52 dense
+ * layers, the transits) is one kernel on the f32 matrix instruction (v_mfma_f32_32x32x2_f32, exact f32) with the BatchNorm
+ * and ReLU in front in its operand load and those behind in its store, k ascending in blocks of 64 that are added in order.
+ * The context sums are formed per chunk in a fixed order without atomics.  A chunk's embedding and taps are the same bytes
+ * alone, at any position of any batch and in any turn.  Scratch is the handle's (grow and keep): 33 KB per feature row,
+ * chunks taken in turns below 2 GB.
+ *
+ *   crispy_diar_emb_frames       T2 for `rows` feature rows; 0 for rows < 1.  No device.
+ *   crispy_diar_emb_tensor_spec  the i-th tensor crispy_diar_emb_load expects for an embedding width `dim`: its state-dict key
+ *       (*name, nullable; static storage) and element count (*count, nullable), in the order of wespeaker's state dict
+ *       without the num_batches_tracked entries.  Returns the number of tensors (815); CRISPY_ERR_INVALID_ARG for i out of
+ *       range or dim outside 1 ... 1024.  No device, no handle.
+ *   crispy_diar_emb_load         host tensors by name, data[i] holding count[i] floats; dim = count of
+ *       xvector.dense.linear.weight / 1024, 1 <= dim <= 1024.  A missing, repeated or unknown name, a count that is not
+ *       the tensor's size, a NULL pointer, a non-finite value or a running_var below 0 is CRISPY_ERR_INVALID_ARG with the
+ *       tensor's name in the message, before the device is touched.  A second load replaces the first; the handle owns
+ *       the device copy.
+ *   crispy_diar_emb_loaded / crispy_diar_emb_dim  1 / the width after a successful load, else 0 (NULL handle: 0).
+ *   crispy_diar_emb_forward_device  d_feats [rows][80] with host frame_offset [n_chunks + 1] (frame_offset[0] = 0), exactly
+ *       what crispy_diar_fbank_device produces -> d_emb [n_chunks][dim]; stage outputs for tests and profiling, each
+ *       nullable: d_head [rows][320], d_xvec [sum T2][512] (after the last BatchNorm and ReLU), d_stats [n_chunks][1024].
+ *       1 <= n_chunks <= 16384; 3 <= rows of a chunk <= 30000 (5 min; the fbank gives at most 29998 for its longest
+ *       chunk; one such chunk takes 1.0 GB of scratch); checked before any launch.  Enqueued on hip_stream (NULL: the
+ *       handle's own), complete on return.  Before a load: CRISPY_ERR_INVALID_ARG.
+ *   crispy_diar_embed_device / crispy_diar_embed  EmbeddingExtractor::compute for all chunks of a recording in one call:
+ *       pcm, first, len, n_chunks and scale as crispy_diar_fbank takes them -> embeddings [n_chunks][dim]; the feature rows
+ *       never leave the device.  A chunk with fewer than 3 rows is CRISPY_ERR_INVALID_ARG (filter with
+ *       crispy_diar_fbank_frames).  The result equals crispy_diar_emb_forward_device on crispy_diar_fbank_device's rows bit
+ *       for bit.  The second form takes pcm and the embeddings on the host.  There is no CPU path.
+ * ------------------------------------------------------------------------------------------ */
+long crispy_diar_emb_frames(long rows);
+int crispy_diar_emb_tensor_spec(int i, int dim, const char **name, long *count);
+int crispy_diar_emb_load(void *h, const char *const *names, const float *const *data, const long *count, int n_tensors);
+int crispy_diar_emb_loaded(void *h);
+int crispy_diar_emb_dim(void *h);
+int crispy_diar_emb_forward_device(void *h, const float *d_feats, const long *frame_offset, int n_chunks, float *d_emb, float *d_head,
+                                   float *d_xvec, float *d_stats, void *hip_stream);
+int crispy_diar_embed_device(void *h, const void *d_pcm, int pcm_format, const long *first, const long *len, int n_chunks, float scale,
+                             float *d_emb, void *hip_stream);
+int crispy_diar_embed(void *h, const void *pcm, int pcm_format, const long *first, const long *len, int n_chunks, float scale, float *emb);
 
 #ifdef __cplusplus
 }
