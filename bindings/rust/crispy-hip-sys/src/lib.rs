@@ -269,6 +269,7 @@ extern "C" {
     pub fn crispy_mel_compute_long_device(h: *mut crispy_mel, d_pcm: *const c_float, pcm_stride: c_long, n_samples: *const c_int, batch: c_int, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_mel_window_device(h: *mut crispy_mel, clip_idx: *const c_int, seek: *const c_int, n: c_int, d_out: *mut c_float, d_out_t: *mut c_float, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_mel_synchronize(h: *mut crispy_mel) -> c_int;
+    pub fn crispy_mel_stage_log10_device(h: *mut crispy_mel, d_s: *const f64, d_y: *mut c_float, n: usize, hip_stream: *mut c_void) -> c_int;
 
     pub fn crispy_asr_create(hp: *const crispy_asr_hparams, mel_filters: *const c_float, device: c_int, out: *mut *mut crispy_asr) -> c_int;
     pub fn crispy_asr_set_tensor(h: *mut crispy_asr, name: *const c_char, data: *const c_float, n_elems: usize) -> c_int;

@@ -47,7 +47,7 @@ NS_RNNOISE, NS_DUMMY, NS_NOISY = 0, 1, 2   # CRISPY_NS_*
 
 MEL_SYMBOLS = ("crispy_mel_create", "crispy_mel_destroy", "crispy_mel_compute",
                "crispy_mel_compute_device", "crispy_mel_compute_long_device", "crispy_mel_window_device",
-               "crispy_mel_synchronize")
+               "crispy_mel_synchronize", "crispy_mel_stage_log10_device")
 ASR_SYMBOLS = ("crispy_asr_create", "crispy_asr_set_tensor", "crispy_asr_finalize", "crispy_asr_free",
                "crispy_asr_hparams_get", "crispy_asr_encode", "crispy_asr_encode_device", "crispy_asr_synchronize",
                "crispy_asr_set_suppress", "crispy_asr_decode_greedy_device", "crispy_asr_transcribe_tokens",
@@ -250,6 +250,7 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_mel_compute_device.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p,
                                             C.c_void_p, C.c_void_p]
     L.crispy_mel_synchronize.argtypes = [C.c_void_p]
+    L.crispy_mel_stage_log10_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.crispy_asr_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
     L.crispy_asr_set_tensor.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]
     L.crispy_asr_finalize.argtypes = [C.c_void_p]

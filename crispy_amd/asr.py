@@ -85,6 +85,11 @@ class LogMel:
     def synchronize(self):
         self._ck(self._L.crispy_mel_synchronize(self._h))
 
+    def stage_log10_device(self, d_s: int, d_y: int, n: int, stream: int = 0):
+        """`crispy_mel_stage_log10_device` (parity tests): n float64 filter sums at d_s -> the f32 the frame kernel stores
+        for each at d_y, `s > 1e-10 ? (float) log10(s) : -10`."""
+        self._ck(self._L.crispy_mel_stage_log10_device(self._h, d_s or None, d_y or None, int(n), stream or None))
+
 
 class WhisperModel:
     """Model container + engine on the GPU (`WhisperEngine::load` + `SpeechModel::transcribe`,

@@ -31,6 +31,10 @@ struct crispy_mel {
   std::vector<int> seek_max;
 };
 
+// what mel_stage.cpp needs of a handle
+int crispy::mel_handle_device(const crispy_mel* h) { return h->device; }
+hipStream_t crispy::mel_handle_stream(const crispy_mel* h) { return h->stream; }
+
 namespace {
 
 int mel_reserve(crispy_mel* h, int batch, long stride, bool need_pcm, bool need_out) {

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct crispy_mel;      // the log-mel handle (asr_api.cpp)
+
 namespace crispy {
 
 // GELU as ggml's CPU backend computes it [UPSTREAM-RECALL: ggml_vec_gelu_f32 with GGML_GELU_FP16, ggml_gelu_f32] -- precision
@@ -71,6 +73,11 @@ struct MelArgs {
 
 hipError_t mel_launch(const MelArgs& a, int batch, hipStream_t s);
 hipError_t mel_window_launch(const MelArgs& a, int n, hipStream_t s);
+// y[i] = s[i] > 1e-10 ? the frame kernel's (float) log10(s[i]) : -10.f (stage entry of the parity tests, mel_stage.cpp,
+// which reads the handle of asr_api.cpp through the two accessors)
+hipError_t mel_log10_launch(const double* s, float* y, long n, hipStream_t st);
+int mel_handle_device(const ::crispy_mel* h);
+hipStream_t mel_handle_stream(const ::crispy_mel* h);
 
 // C[M,N] = A[M,K] . W[N,K]^T (+bias) (GELU) (+residual) (+rowtab[m % period]); all f32, row-major.
 // A may be a strided view (lda < K): rows overlap, which is how the two convolutions are expressed.

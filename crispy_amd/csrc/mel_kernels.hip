@@ -41,8 +41,9 @@ constexpr size_t MEL_LDS = MEL_LDS_BUF + 400 * sizeof(float2) + 400 * sizeof(flo
 // (float) log10(s) for a normal double s: log10(2) e + log10(e) ln m with s = m 2^e, m in [sqrt(1/2), sqrt(2)), and
 // ln m = 2 atanh z, z = (m - 1) / (m + 1) <= 0.172, as its odd series to z^13 (the z^15 term is 4e-13).  The absolute
 // error is ~1e-12 against the 4.8e-7 ulp of the float the value is rounded to: the float differs from the correctly
-// rounded one about once in 10^5 values.  ~25 double operations where the library's log10 took ~300 (it was a fifth
-// of the kernel's instruction issue).
+// rounded one about once in 10^5 values at most (tests/test_gpu_logmel_precision.py bounds both figures against float64
+// through mel_log10_kernel below: none of 6e6 values did).  ~25 double operations where the library's log10 took ~300
+// (it was a fifth of the kernel's instruction issue).
 __device__ __forceinline__ float log10_to_float(double s) {
   const long long bits = __double_as_longlong(s);
   int e = (int)((bits >> 52) & 0x7ff) - 1023;
@@ -204,7 +205,19 @@ __global__ __launch_bounds__(256) void mel_finish_kernel(MelArgs a) {
   if (a.out_t) a.out_t[((long)k * (MEL_FRAMES + 2) + t + 1) * a.n_mel + m] = r;
 }
 
+// stage entry (crispy_mel_stage_log10_device): what mel_frames_kernel applies to every filter sum, value by value
+__global__ __launch_bounds__(256) void mel_log10_kernel(const double* __restrict__ s, float* __restrict__ y, long n) {
+  const long stride = (long)gridDim.x * 256;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) y[i] = s[i] > 1e-10 ? log10_to_float(s[i]) : -10.f;
+}
+
 }  // namespace
+
+hipError_t mel_log10_launch(const double* s, float* y, long n, hipStream_t st) {
+  const long blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(mel_log10_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, s, y, n);
+  return hipGetLastError();
+}
 
 hipError_t mel_launch(const MelArgs& a, int batch, hipStream_t s) {
   constexpr size_t smem = MEL_LDS;     // 36 KB whatever the number of mel bins

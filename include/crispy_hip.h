@@ -513,6 +513,10 @@ int crispy_mel_compute_long_device(crispy_mel *h, const float *d_pcm, long pcm_s
 int crispy_mel_window_device(crispy_mel *h, const int *clip_idx, const int *seek, int n, float *d_out,
                              float *d_out_t, void *hip_stream);
 int crispy_mel_synchronize(crispy_mel *h);
+/* Stage entry point (parity tests): d_y[i] = the float the frame kernel stores for the filter sum d_s[i] (DEVICE, n
+ * values): d_s[i] > 1e-10 ? (float) log10(d_s[i]) by the kernel's own series : -10.f.  Enqueued on hip_stream (NULL =
+ * the handle's stream) without waiting. */
+int crispy_mel_stage_log10_device(crispy_mel *h, const double *d_s, float *d_y, size_t n, void *hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * Whisper engine: replaces transcribe_rs::whisper_cpp::WhisperEngine behind `SpeechModel`
