@@ -56,31 +56,39 @@ constexpr int kStagedMaxStreams = 1280;
 // has alone, so a sub-chunk may be at most ~1.5x its predecessor: behind 3, 8 the frame kernels of sub-chunks 1 and 2
 // waited 107 + 55 us for their input (tools/step_timeline.py).  CRISPY_RN_RAMP="3,4,6,9" overrides the ramp 3, 4, 5, 7, 10 (developer
 // knob; entries above the sub-chunk size are clipped).
-inline const std::vector<int>& ramp_frames() {
-  static const std::vector<int> ramp = [] {
-    std::vector<int> r;
-    if (const char* env = dev_env("CRISPY_RN_RAMP")) {
-      for (const char* p = env; *p;) {
-        char* end = nullptr;
-        const long v = std::strtol(p, &end, 10);
-        if (end == p) break;
-        if (v > 0) r.push_back(v > kSubFrames ? kSubFrames : (int)v);
-        p = *end ? end + 1 : end;
-      }
-    }
-    if (r.empty()) r = {3, 4, 5, 7, 10};
-    return r;
-  }();
-  return ramp;
+// Grain and ramp belong to the handle (crispy_rn::sub_frames, ::ramp), read once when it is created: CRISPY_RN_SUB_FRAMES
+// (1 .. kChunkFrames) overrides the grain as CRISPY_RN_RAMP does the ramp, so handles of several grains can be timed
+// side by side in one process (tools/grain_sweep.py).  Neither changes kChunkFrames or the workspace.
+inline std::vector<int> default_ramp(int grain = kSubFrames) {
+  std::vector<int> r = {3, 4, 5, 7, 10};
+  for (int& v : r) v = v > grain ? grain : v;
+  return r;
 }
-inline int sub_frames(int index, int remaining) {
-  const std::vector<int>& ramp = ramp_frames();
-  const int want = index < (int)ramp.size() ? ramp[index] : kSubFrames;
+void read_schedule(crispy_rn* h) {
+  h->sub_frames = kSubFrames;
+  if (const char* env = dev_env("CRISPY_RN_SUB_FRAMES")) {
+    const int v = std::atoi(env);
+    if (v > 0) h->sub_frames = v > kChunkFrames ? kChunkFrames : v;
+  }
+  h->ramp.clear();
+  if (const char* env = dev_env("CRISPY_RN_RAMP")) {
+    for (const char* p = env; *p;) {
+      char* end = nullptr;
+      const long v = std::strtol(p, &end, 10);
+      if (end == p) break;
+      if (v > 0) h->ramp.push_back(v > h->sub_frames ? h->sub_frames : (int)v);
+      p = *end ? end + 1 : end;
+    }
+  }
+  if (h->ramp.empty()) h->ramp = default_ramp(h->sub_frames);
+}
+inline int sub_frames(const std::vector<int>& ramp, int grain, int index, int remaining) {
+  const int want = index < (int)ramp.size() ? ramp[index] : grain;
   return remaining < want ? remaining : want;
 }
-inline int count_subs(int T) {
+inline int count_subs(const std::vector<int>& ramp, int grain, int T) {
   int n = 0;
-  for (int done = 0; done < T; ++n) done += sub_frames(n, T - done);
+  for (int done = 0; done < T; ++n) done += sub_frames(ramp, grain, n, T - done);
   return n;
 }
 
@@ -398,6 +406,9 @@ int crispy_rn_create(const int8_t* weights, size_t nbytes, int n_streams, int de
       if (sp) h->hp_split = std::atoi(sp);   // 0: one kernel per sub-chunk
       const char* ah = dev_env("CRISPY_RN_HP_AHEAD");
       h->hp_ahead = ah ? std::atoi(ah) : 0;
+      const char* hf = dev_env("CRISPY_RN_HP_FIRST");
+      if (hf) h->hp_first_deep = std::atoi(hf) != 0;   // 0: sub-chunk 0 split and capped like every other one
+      read_schedule(h);
     }
     RnTables* tab = new RnTables();
     build_tables(tab);
@@ -427,9 +438,12 @@ void crispy_rn_destroy(crispy_rn* h) { delete h; }     // ~crispy_rn (rn_handle.
 int crispy_rn_n_streams(const crispy_rn* h) { return h ? h->B : 0; }
 
 int crispy_rn_frames_per_launch(void) { return kSubFrames; }
+// what a handle created with the defaults launches
 int crispy_rn_n_launches(int n_frames) try {
   int n = 0;
-  for (int t0 = 0; t0 < n_frames; t0 += kChunkFrames) n += count_subs(n_frames - t0 < kChunkFrames ? n_frames - t0 : kChunkFrames);
+  const std::vector<int> ramp = default_ramp();
+  for (int t0 = 0; t0 < n_frames; t0 += kChunkFrames)
+    n += count_subs(ramp, kSubFrames, n_frames - t0 < kChunkFrames ? n_frames - t0 : kChunkFrames);
   return n;
 } CRISPY_CATCH_RET("crispy_rn_n_launches")
 
@@ -502,7 +516,7 @@ int process_device_impl(crispy_rn* h, const void* d_in_v, void* d_out_v, float* 
     // (producer of d_in, previous segment's frame kernels and history roll).
     HIP_TRY(hipEventRecord(h->ev_begin[0], s));
     HIP_TRY(hipStreamWaitEvent(h->hp_stream, h->ev_begin[0], 0));
-    const int n_sub = count_subs(T);
+    const int n_sub = count_subs(h->ramp, h->sub_frames, T);
     HIP_TRY(h->ev_hp.ensure((size_t)n_sub, hipEventDisableTiming));
     hipEvent_t* e = nullptr;
     if (h->timing) {
@@ -519,18 +533,29 @@ int process_device_impl(crispy_rn* h, const void* d_in_v, void* d_out_v, float* 
       for (; hp_next <= last && hp_next < n_sub; ++hp_next) {
         const int i = hp_next, ts = hp_ts;
         RnArgs sa = a;
-        sa.T = sub_frames(i, T - ts);
+        sa.T = sub_frames(h->ramp, h->sub_frames, i, T - ts);
         sa.in = in_at((long)(t0 + ts) * a.stride_t);
         sa.xhp = h->d_xhp + (long)ts * RN_FRAME;   // row pointer shifted by the frames already filtered
         hipStream_t hs = h->hp_upfront ? s : h->hp_stream;
         if (h->hp_ahead > 0 && i >= h->hp_ahead) HIP_TRY(hipStreamWaitEvent(hs, h->ev_fr[i - h->hp_ahead], 0));
-        const int per = h->hp_split > 0 ? h->hp_split : sa.T;
+        // Sub-chunk 0 of a one-wave handle: nothing overlaps it -- it is gated (ev_begin) behind everything on the caller's
+        // stream, the previous segment's or call's last frame kernel and history roll included, and the first frame kernel
+        // waits for it -- so its length is added to the call.  The split into hp_split-frame launches and the 32-register cap
+        // exist for high-pass waves that run BESIDE this handle's 120-register frame waves; none is resident here, so it
+        // is one launch of the deep kernel (32 samples requested ahead, 80 registers: the memory round trip per 8 samples
+        // is what bounds the capped form when it runs alone, NOTEBOOK 8.6).  Both kernels are rn_highpass_body: same bits.
+        // Frame waves of ANOTHER handle may be resident (four 120-register waves fill a SIMD's 512 registers but for 32): an
+        // 80-register wave then waits for a SIMD with room, where the capped one would have started at once -- measured
+        // with two 4096-stream handles on two host threads (tools/two_handle_step.py, NOTEBOOK section 34): the pair's step
+        // was 0.5 % shorter with the deep form, inside its spread, so the form is not restricted further.
+        const bool whole_deep = i == 0 && h->waves == 1 && h->hp_first_deep;
+        const int per = !whole_deep && h->hp_split > 0 ? h->hp_split : sa.T;
         for (int f0 = 0; f0 < sa.T; f0 += per) {
           RnArgs pa = sa;
           pa.T = (sa.T - f0) < per ? (sa.T - f0) : per;
           pa.in = in_at((long)(t0 + ts + f0) * a.stride_t);
           pa.xhp = sa.xhp + (long)f0 * RN_FRAME;
-          HIP_TRY(rn_launch_highpass(pa, hs, h->hp_deep));
+          HIP_TRY(rn_launch_highpass(pa, hs, whole_deep || h->hp_deep));
         }
         HIP_TRY(hipEventRecord(h->ev_hp[i], hs));
         hp_ts += sa.T;
@@ -541,7 +566,7 @@ int process_device_impl(crispy_rn* h, const void* d_in_v, void* d_out_v, float* 
     // frame kernels on the caller's stream, each gated on its own sub-chunk's high-pass
     for (int i = 0, ts = 0; i < n_sub; ++i) {
       RnArgs sa = a;
-      sa.T = sub_frames(i, T - ts);
+      sa.T = sub_frames(h->ramp, h->sub_frames, i, T - ts);
       sa.out = out_at((long)(t0 + ts) * a.stride_t);
       sa.vad = d_vad ? d_vad + (long)(t0 + ts) * h->B : nullptr;
       sa.taps = d_taps ? d_taps + (long)(t0 + ts) * h->B * RN_TAPS : nullptr;

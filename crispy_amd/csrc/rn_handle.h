@@ -188,6 +188,15 @@ struct crispy_rn {
   crispy::EventList ev_fr;   // one per sub-chunk: frame kernel done (only used with hp_ahead)
   bool hp_deep = false;      // the high-pass requests 32 samples ahead (80 registers): set where a wave of it fits beside the frame waves
   bool hp_upfront = false;   // diagnostic (CRISPY_RN_HP=upfront): every high-pass of a call segment first, on the main stream
+  // Sub-chunk 0 of a segment of a one-wave handle is filtered by ONE launch of the deep kernel instead of hp_split
+  // launches of the 32-register one (crispy_api.cpp, process_device_impl, says what that relies on).
+  // CRISPY_RN_HP_FIRST=0 (developer knob) restores the split form.
+  bool hp_first_deep = true;
+  // Pipeline grain of this handle: frames per frame-kernel launch, and the shorter sub-chunks a segment starts with
+  // (crispy_api.cpp: kSubFrames, default_ramp).  Read once at create time; CRISPY_RN_SUB_FRAMES and CRISPY_RN_RAMP
+  // (developer knobs) override them per handle, so that one process can time several grains side by side.
+  int sub_frames = 0;
+  std::vector<int> ramp;
   crispy::DevBuf<float> d_dbg;
   // Host-pointer staging, one set for every entry point that takes host arrays (process, push, pull, app_push, level, drain):
   // each of them synchronises before it returns, so a buffer is only live inside one call.  Scratch (DevBuf::grow).
