@@ -190,6 +190,21 @@ pub struct crispy_diar_info {
     pub gap: c_float,
     pub p_max: c_int,
 }
+/// `crispy_pk_config`: the Parakeet encoder's shape and flags (`cfg` of `crispy_pk_tensor_spec`, `crispy_pk_load`, `crispy_pk_config_of`).
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
+pub struct crispy_pk_config {
+    pub hidden: c_int,
+    pub layers: c_int,
+    pub heads: c_int,
+    pub ffn: c_int,
+    pub conv_kernel: c_int,
+    pub mel_bins: c_int,
+    pub sub_channels: c_int,
+    pub attention_bias: c_int,
+    pub convolution_bias: c_int,
+    pub scale_input: c_int,
+}
 #[repr(C)]
 #[derive(Debug, Clone, Copy)]
 pub struct crispy_asr_word {
@@ -351,6 +366,16 @@ extern "C" {
     pub fn crispy_diar_emb_forward_device(h: *mut c_void, d_feats: *const c_float, frame_offset: *const c_long, n_chunks: c_int, d_emb: *mut c_float, d_head: *mut c_float, d_xvec: *mut c_float, d_stats: *mut c_float, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_diar_embed_device(h: *mut c_void, d_pcm: *const c_void, pcm_format: c_int, first: *const c_long, len: *const c_long, n_chunks: c_int, scale: c_float, d_emb: *mut c_float, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_diar_embed(h: *mut c_void, pcm: *const c_void, pcm_format: c_int, first: *const c_long, len: *const c_long, n_chunks: c_int, scale: c_float, emb: *mut c_float) -> c_int;
+    // Parakeet encoder; `cfg` points at a `crispy_pk_config`
+    pub fn crispy_pk_create(device: c_int, out: *mut *mut c_void) -> c_int;
+    pub fn crispy_pk_destroy(h: *mut c_void);
+    pub fn crispy_pk_frames(rows: c_long) -> c_long;
+    pub fn crispy_pk_tensor_spec(cfg: *const c_void, i: c_int, name: *mut *const c_char, count: *mut c_long) -> c_int;
+    pub fn crispy_pk_load(h: *mut c_void, cfg: *const c_void, names: *const *const c_char, data: *const *const c_float, count: *const c_long, n_tensors: c_int) -> c_int;
+    pub fn crispy_pk_loaded(h: *mut c_void) -> c_int;
+    pub fn crispy_pk_config_of(h: *mut c_void, cfg: *mut c_void) -> c_int;
+    pub fn crispy_pk_encode_device(h: *mut c_void, d_feats: *const c_float, frame_offset: *const c_long, n_clips: c_int, d_out: *mut c_float, d_sub: *mut c_float, tap_layer: c_int, d_tap: *mut c_float, d_pos: *mut c_float, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_pk_encode(h: *mut c_void, feats: *const c_float, frame_offset: *const c_long, n_clips: c_int, out: *mut c_float, sub: *mut c_float, tap_layer: c_int, tap: *mut c_float, pos: *mut c_float) -> c_int;
 }
 
 // ------------------------------------------------------------------------------------------------------------

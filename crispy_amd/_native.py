@@ -72,13 +72,23 @@ DIAR_SEG_SYMBOLS = ("crispy_diar_seg_frames", "crispy_diar_seg_windows", "crispy
                     "crispy_diar_seg_forward_device", "crispy_diar_seg_scores_device", "crispy_diar_seg_scores")
 DIAR_EMB_SYMBOLS = ("crispy_diar_emb_frames", "crispy_diar_emb_tensor_spec", "crispy_diar_emb_load", "crispy_diar_emb_loaded",
                     "crispy_diar_emb_dim", "crispy_diar_emb_forward_device", "crispy_diar_embed_device", "crispy_diar_embed")
-ALL_SYMBOLS = RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS + DIAR_SYMBOLS + DIAR_FRONT_SYMBOLS + DIAR_SEG_SYMBOLS + DIAR_EMB_SYMBOLS
+PK_SYMBOLS = ("crispy_pk_create", "crispy_pk_destroy", "crispy_pk_frames", "crispy_pk_tensor_spec", "crispy_pk_load", "crispy_pk_loaded",
+              "crispy_pk_config_of", "crispy_pk_encode_device", "crispy_pk_encode")
+ALL_SYMBOLS = (RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS + DIAR_SYMBOLS + DIAR_FRONT_SYMBOLS + DIAR_SEG_SYMBOLS + DIAR_EMB_SYMBOLS
+               + PK_SYMBOLS)
+PK_HEAD_DIM, PK_MAX_ROWS, PK_MAX_CLIPS, PK_ATTN_Q, PK_ATTN_K = 128, 40000, 4096, 32, 32      # crispy_amd/csrc/pk_internal.h
 EMB_HEAD, EMB_XVEC, EMB_STATS, EMB_MIN_ROWS, EMB_MAX_ROWS, EMB_TENSORS = 320, 512, 1024, 3, 30000, 815      # crispy_amd/csrc/diar_internal.h
 SEG_WINDOW, SEG_MIN_LEN, SEG_FRAMES, SEG_CLASSES = 160000, 991, 589, 7      # crispy_amd/csrc/diar_internal.h
 SEG_MAX_SAMPLES, SEG_MAX_WINDOWS = 115200000, 4096
 FBANK_BINS, FBANK_WAVE_FRAMES, FBANK_TILE_FRAMES = 80, 8, 32      # crispy_amd/csrc/diar_internal.h
 FBANK_MAX_CHUNKS, FBANK_MAX_CHUNK_SAMPLES = 16384, 4800000
 DIAR_MAX_N, DIAR_MAX_DIM, DIAR_MAX_BATCH, DIAR_LDS_N = 2048, 1024, 64, 192
+
+
+class PkConfig(C.Structure):
+    """crispy_pk_config"""
+    _fields_ = [(k, C.c_int) for k in ("hidden", "layers", "heads", "ffn", "conv_kernel", "mel_bins", "sub_channels",
+                                       "attention_bias", "convolution_bias", "scale_input")]
 
 
 class DiarInfo(C.Structure):
@@ -355,6 +365,17 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_diar_emb_forward_device.argtypes = [C.c_void_p, C.c_void_p, lp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.crispy_diar_embed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, lp, lp, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
     L.crispy_diar_embed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, lp, lp, C.c_int, C.c_float, C.c_void_p]
+    L.crispy_pk_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.crispy_pk_destroy.argtypes = [C.c_void_p]
+    L.crispy_pk_destroy.restype = None
+    L.crispy_pk_frames.argtypes = [C.c_long]
+    L.crispy_pk_frames.restype = C.c_long
+    L.crispy_pk_tensor_spec.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), lp]
+    L.crispy_pk_load.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), lp, C.c_int]
+    L.crispy_pk_loaded.argtypes = [C.c_void_p]
+    L.crispy_pk_config_of.argtypes = [C.c_void_p, C.c_void_p]
+    L.crispy_pk_encode_device.argtypes = [C.c_void_p, C.c_void_p, lp, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.crispy_pk_encode.argtypes = [C.c_void_p, C.c_void_p, lp, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     return L
 
 

@@ -1,0 +1,82 @@
+// pk_internal.h -- what the host side (pk_api.cpp) and the device side (pk_sub.hip, pk_gemm.hip, pk_attn.hip) of the Parakeet
+// FastConformer encoder share: the handle, the model as the kernels read it and the launch functions.
+#pragma once
+#include <cstddef>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/crispy_hip.h"
+#include "api_util.h"
+
+struct crispy_pk {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  crispy::DevBuf<float> weights;      // the encoder as crispy_pk_load laid it out (PkModel); empty until a load
+  crispy_pk_config cfg{};             // of the load
+  crispy::DevBuf<char> scratch;       // a call's workspace, grown on demand and kept
+  crispy::DevBuf<char> io;            // host-form features, frames and taps
+  ~crispy_pk() {
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+namespace crispy {
+namespace pk {
+
+constexpr int kHeadDim = 128;
+constexpr int kMaxRows = 40000, kMaxClips = 4096;      // T' <= 5000, the model's max_position_embeddings
+constexpr int kMaxTaps = 31, kMaxSubCh = 512;
+constexpr double kEps = 1e-5;                          // LayerNorm and BatchNorm
+constexpr int kAttnQ = 32, kAttnK = 32;                // query and key tile of the attention kernel
+constexpr int kSubNF = 8;                              // frequencies of one workgroup of the fused depthwise + pointwise kernel
+
+inline long sub_len(long n) { return n < 1 ? 0 : (n - 1) / 2 + 1; }
+inline long frames(long rows) { return sub_len(sub_len(sub_len(rows))); }
+
+// Where each tensor sits in the handle's device copy, as the kernels read it.  Every linear weight is [in][out] (the output
+// contiguous); absent biases are zeros.  qkv is q, k and v side by side [H][3H]; pointwise_conv1 has its 2H outputs reordered
+// in groups of 64 columns: 32 value channels, then their 32 gate channels, so that a GEMM lane holds both halves of a GLU.
+// The depthwise weights are [tap][channel]; its bias and the BatchNorm are one (scale, shift) pair folded in double.
+struct PkLayer {
+  const float *ln_g[5], *ln_b[5];      // norm_feed_forward1, norm_self_att, norm_conv, norm_feed_forward2, norm_out
+  const float *ff_w1[2], *ff_b1[2], *ff_w2[2], *ff_b2[2];
+  const float *qkv_w, *qkv_b, *o_w, *o_b, *r_w, *bias_u, *bias_v;
+  const float *pw1_w, *pw1_b, *dw_w, *dw_scale, *dw_shift, *pw2_w, *pw2_b;
+};
+struct PkModel {
+  const float *conv0_w, *conv0_b;               // [9][C], [C]
+  const float *dw_w[2], *dw_b[2];               // [9][C], [C]
+  const float *pw_w[2], *pw_b[2];               // [C][C], [C]
+  const float *lin_w, *lin_b;                   // [C * M / 8][H], [H]
+  const float* inv_freq;                        // [H / 2]
+  std::vector<PkLayer> layer;
+};
+// A call's clips: clip c has feature rows off[0][c] ... off[0][c + 1] and off[s] likewise after s stride-2 convolutions
+// (device memory, n_clips + 1 each); max_len[s] is the longest clip's count at stage s.
+struct PkTables {
+  const int* off[4];
+  int n_clips, max_len[4];
+};
+
+// feats [rows][M] -> relu(Conv2d(1, C, 3, stride 2, pad 1)) as [T1][M / 2][C]
+hipError_t launch_sub_conv0(const PkModel& m, const PkTables& t, const float* d_feats, int M, int C, float* d_out, hipStream_t st);
+// stage s (1, 2): in [T_s][F][C] -> relu(pointwise(depthwise stride 2)) as [T_s+1][F / 2][C]; `flat`: as [T_s+1][C * (F / 2)], c * (F / 2) + f
+hipError_t launch_sub_dwpw(int s, const PkModel& m, const PkTables& t, const float* d_in, int F, int C, float* d_out, bool flat, hipStream_t st);
+// out = LayerNorm(in) * g + b over rows of H; in == out is allowed
+hipError_t launch_layernorm(const float* d_in, const float* g, const float* b, float* d_out, long rows, int H, hipStream_t st);
+// C [M][N] = epilogue(A [M][K] . Bt [K][N] + bias) on the f32 matrix instruction, k ascending in chains of 64 that are added in order.
+// kGemmScale: (v) * alpha; kGemmSilu: silu(v); kGemmResidual: res + alpha * v (res == C allowed); kGemmGlu: N outputs from 2N
+// columns in pointwise_conv1's order, value * sigmoid(gate).  K a multiple of 32, the column count of 128; bias nullable.
+enum GemmEpilogue { kGemmScale, kGemmSilu, kGemmResidual, kGemmGlu };
+hipError_t launch_gemm(GemmEpilogue e, const float* d_a, int K, const float* d_bt, const float* bias, int N, float alpha, const float* d_res,
+                       float* d_c, long M, hipStream_t st);
+// pos [2 * tmax - 1][H]: row p is d = p - (tmax - 1); sin in the even columns, cos in the odd ones
+hipError_t launch_pos_table(const float* inv_freq, int tmax, int H, float* d_pos, hipStream_t st);
+// soft-max((q + u) k^T + (q + v) r_{i - j}^T) / sqrt(128)) v per clip and head; qkv [T'][3H], r [2 * tmax - 1][H] -> out [T'][H]
+hipError_t launch_attention(const PkLayer& l, const PkTables& t, const float* d_qkv, const float* d_r, int tmax, int heads, float* d_out, hipStream_t st);
+// silu(scale * depthwise K-tap convolution + shift), zero-padded at each clip's own edges; [T'][H] -> [T'][H]
+hipError_t launch_dwconv(const PkLayer& l, const PkTables& t, const float* d_in, int H, int K, float* d_out, hipStream_t st);
+
+}  // namespace pk
+}  // namespace crispy

@@ -1263,6 +1263,76 @@ int crispy_diar_embed_device(void *h, const void *d_pcm, int pcm_format, const l
                              float *d_emb, void *hip_stream);
 int crispy_diar_embed(void *h, const void *pcm, int pcm_format, const long *first, const long *len, int n_chunks, float scale, float *emb);
 
+/* ------------------------------------------------------------------------------------------
+ * Parakeet encoder: the FastConformer encoder of parakeet-tdt-0.6b (v2 and v3), the model the reference recommends first
+ * (commands/models.rs:145, managers/model.rs:150-186) -- log-mel feature rows in, encoder frames out, f32 operands and f32
+ * sums throughout.  The log-mel front end and the TDT decoder are not part of it.  New entry points only: no struct of an
+ * existing entry point grew, the ABI version is unchanged.  State-dict keys are those of transformers' ParakeetEncoder; all
+ * of it is inference.
+ *
+ * The network on one clip [T][M] (crispy_pk_config: hidden H = 128 x heads, layers, heads, ffn, conv_kernel K (odd), mel_bins M
+ * (a multiple of 8), sub_channels C, and the flags attention_bias, convolution_bias, scale_input, each 0 or 1; a flag at 0
+ * means those bias tensors are absent from the load):
+ *   subsampling  the clip as a 1-channel image (time x mel): Conv2d(1, C, 3, stride 2, pad 1), ReLU; twice depthwise
+ *                Conv2d(C, C, 3, stride 2, pad 1, groups C), Conv2d(C, C, 1), ReLU; then [T'][C * M / 8] (index c * M / 8 + f),
+ *                Linear to H, times sqrt(H) with scale_input.  T' is L -> (L - 1) / 2 + 1 applied three times.
+ *   block        x += 0.5 FF1(LN(x)); x += Attn(LN(x)); x += Conv(LN(x)); x += 0.5 FF2(LN(x)); x = LN_out(x); LayerNorm eps 1e-5,
+ *                FF = linear2(silu(linear1(.))) (its biases follow attention_bias).
+ *   attention    q, k, v, o projections, relative_k_proj without bias, bias_u and bias_v [heads][128];
+ *                score(i, j) = ((q_i + u) . k_j + (q_i + v) . r_{i - j}) / sqrt(128) with r_d = relative_k_proj(pos(d)); soft-max
+ *                over the clip's own T' keys.  pos(d)[2k] = f32(sin(arg)), pos(d)[2k + 1] = f32(cos(arg)) in double, arg the one
+ *                f32 product f32(d) * f32(1 / 10000^(2k / H)).
+ *   convolution  pointwise_conv1 (H -> 2H), GLU over channels, depthwise Conv1d(H, H, K, pad (K - 1) / 2) zero-padded at the
+ *                clip's own edges, BatchNorm (eps 1e-5), SiLU, pointwise_conv2.
+ *
+ * Device work: clips are ragged and lie end to end, [sum T'][H] with the host's frame_offset.  The subsampling is three
+ * kernels (the first convolution; each depthwise + pointwise + ReLU pair in one, the depthwise image never stored).  Every
+ * Linear and 1x1 convolution is one GEMM kernel on the f32 matrix instruction (v_mfma_f32_32x32x2_f32, exact f32), k ascending
+ * in chains of 64 that are added in order; its store carries bias, SiLU, GLU, the residual with its factor or the input scale.
+ * LayerNorm is a row pass.  Attention is one workgroup per (clip, head, 32 queries) over key tiles of 32 with a running maximum
+ * and sum and no [T'][T'] buffer; the position term of a tile pair is one product with the 63-row band of R it needs.  The
+ * BatchNorm and the depthwise bias are folded at load into a (scale, shift) pair in double.  No atomics: a clip's frames are
+ * the same bytes alone, at any position of any batch and in any call.
+ *
+ *   crispy_pk_create / crispy_pk_destroy   a handle on `device` with its own stream; the workspace grows on demand and is kept.
+ *   crispy_pk_frames       T' for `rows` feature rows; 0 for rows < 1.  No device.
+ *   crispy_pk_tensor_spec  the i-th tensor crispy_pk_load expects for `cfg` (a const crispy_pk_config *): its state-dict key
+ *       (*name, nullable; valid until the calling thread's next call) and element count (*count, nullable), in state-dict
+ *       order without the num_batches_tracked entries.  Returns the number of tensors; CRISPY_ERR_INVALID_ARG for i out of
+ *       range or a config outside the supported set (heads 1 ... 16, hidden = 128 x heads, layers 1 ... 64, ffn a multiple of
+ *       128 up to 16384, conv_kernel odd 3 ... 31, mel_bins a multiple of 8 up to 256, sub_channels a multiple of 32 up to
+ *       512, flags 0 or 1), naming the field.  No device, no handle.
+ *   crispy_pk_load         host tensors by name, data[i] holding count[i] floats.  A missing, repeated or unknown name, a count
+ *       that is not the tensor's size, a NULL pointer, a non-finite value, a running_var below 0 or an unsupported config is
+ *       CRISPY_ERR_INVALID_ARG with the tensor's or field's name in the message, before the device is touched.  A second
+ *       load replaces the first; the handle owns the device copy.
+ *   crispy_pk_loaded / crispy_pk_config_of   1 after a successful load, else 0 (NULL handle: 0) / the loaded config into
+ *       *cfg (a crispy_pk_config *); CRISPY_ERR_INVALID_ARG before a load.
+ *   crispy_pk_encode_device  d_feats [rows][M] with host frame_offset [n_clips + 1] (frame_offset[0] = 0) -> d_out [sum T'][H].
+ *       Stage outputs, each nullable: d_sub [sum T'][H] the subsampling output after the scale, d_tap [sum T'][H] the output
+ *       of block tap_layer (0 ... layers - 1, checked when d_tap is given), d_pos [2 Tmax - 1][H] the position table, row p
+ *       for d = p - (Tmax - 1), Tmax the longest clip's T'.  1 <= rows of a clip <= 40000 (T' <= 5000), 1 <= n_clips <= 4096,
+ *       checked before any launch.  The workspace (46 KB per feature row at the catalog widths, 32 of them the first image) is sized from the call and
+ *       checked against the device's free memory before any launch: too large is CRISPY_ERR_OOM with nothing enqueued.
+ *       Enqueued on hip_stream (NULL: the handle's own), complete on return.  Before a load: CRISPY_ERR_INVALID_ARG.
+ *   crispy_pk_encode       the same call with host pointers; bit-identical results.  There is no CPU path.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct crispy_pk_config {
+  int hidden, layers, heads, ffn, conv_kernel, mel_bins, sub_channels, attention_bias, convolution_bias, scale_input;
+} crispy_pk_config;
+
+int crispy_pk_create(int device, void **out);
+void crispy_pk_destroy(void *h);
+long crispy_pk_frames(long rows);
+int crispy_pk_tensor_spec(const void *cfg, int i, const char **name, long *count);
+int crispy_pk_load(void *h, const void *cfg, const char *const *names, const float *const *data, const long *count, int n_tensors);
+int crispy_pk_loaded(void *h);
+int crispy_pk_config_of(void *h, void *cfg);
+int crispy_pk_encode_device(void *h, const float *d_feats, const long *frame_offset, int n_clips, float *d_out, float *d_sub, int tap_layer,
+                            float *d_tap, float *d_pos, void *hip_stream);
+int crispy_pk_encode(void *h, const float *feats, const long *frame_offset, int n_clips, float *out, float *sub, int tap_layer, float *tap,
+                     float *pos);
+
 #ifdef __cplusplus
 }
 #endif
