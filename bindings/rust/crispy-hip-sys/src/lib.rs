@@ -205,6 +205,20 @@ pub struct crispy_pk_config {
     pub convolution_bias: c_int,
     pub scale_input: c_int,
 }
+/// `crispy_pk_tdt_config`: the Parakeet TDT decoder's shape (`cfg` of `crispy_pk_tdt_tensor_spec`, `crispy_pk_tdt_load`,
+/// `crispy_pk_tdt_config_of`, `crispy_pk_tdt_max_steps`); `durations` holds `n_durations` values.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
+pub struct crispy_pk_tdt_config {
+    pub hidden: c_int,
+    pub decoder_hidden: c_int,
+    pub decoder_layers: c_int,
+    pub vocab: c_int,
+    pub blank: c_int,
+    pub n_durations: c_int,
+    pub durations: [c_int; 8],
+    pub max_symbols_per_step: c_int,
+}
 #[repr(C)]
 #[derive(Debug, Clone, Copy)]
 pub struct crispy_asr_word {
@@ -376,6 +390,17 @@ extern "C" {
     pub fn crispy_pk_config_of(h: *mut c_void, cfg: *mut c_void) -> c_int;
     pub fn crispy_pk_encode_device(h: *mut c_void, d_feats: *const c_float, frame_offset: *const c_long, n_clips: c_int, d_out: *mut c_float, d_sub: *mut c_float, tap_layer: c_int, d_tap: *mut c_float, d_pos: *mut c_float, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_pk_encode(h: *mut c_void, feats: *const c_float, frame_offset: *const c_long, n_clips: c_int, out: *mut c_float, sub: *mut c_float, tap_layer: c_int, tap: *mut c_float, pos: *mut c_float) -> c_int;
+    // Parakeet TDT decoder; `cfg` points at a `crispy_pk_tdt_config`
+    pub fn crispy_pk_tdt_create(device: c_int, out: *mut *mut c_void) -> c_int;
+    pub fn crispy_pk_tdt_destroy(h: *mut c_void);
+    pub fn crispy_pk_tdt_tensor_spec(cfg: *const c_void, i: c_int, name: *mut *const c_char, count: *mut c_long) -> c_int;
+    pub fn crispy_pk_tdt_load(h: *mut c_void, cfg: *const c_void, names: *const *const c_char, data: *const *const c_float, count: *const c_long, n_tensors: c_int) -> c_int;
+    pub fn crispy_pk_tdt_loaded(h: *mut c_void) -> c_int;
+    pub fn crispy_pk_tdt_config_of(h: *mut c_void, cfg: *mut c_void) -> c_int;
+    pub fn crispy_pk_tdt_max_steps(cfg: *const c_void, frames: c_long) -> c_long;
+    pub fn crispy_pk_tdt_decode_device(h: *mut c_void, d_frames: *const c_float, frame_offset: *const c_long, n_clips: c_int, d_steps: *mut c_int, d_n_steps: *mut c_int, d_proj_tap: *mut c_float, d_logits_tap: *mut c_float, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_pk_tdt_decode(h: *mut c_void, frames: *const c_float, frame_offset: *const c_long, n_clips: c_int, steps: *mut c_int, n_steps: *mut c_int, proj_tap: *mut c_float, logits_tap: *mut c_float) -> c_int;
+    pub fn crispy_pk_tdt_words(steps: *const c_int, n_steps: c_int, frames: c_int, blank: c_int, pieces: *const *const c_char, vocab: c_int, seconds_per_frame: f64, start_s: *mut c_float, end_s: *mut c_float, text_off: *mut c_long, max_words: c_int, text: *mut c_char, text_cap: c_long, text_needed: *mut c_long) -> c_long;
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -74,8 +74,11 @@ DIAR_EMB_SYMBOLS = ("crispy_diar_emb_frames", "crispy_diar_emb_tensor_spec", "cr
                     "crispy_diar_emb_dim", "crispy_diar_emb_forward_device", "crispy_diar_embed_device", "crispy_diar_embed")
 PK_SYMBOLS = ("crispy_pk_create", "crispy_pk_destroy", "crispy_pk_frames", "crispy_pk_tensor_spec", "crispy_pk_load", "crispy_pk_loaded",
               "crispy_pk_config_of", "crispy_pk_encode_device", "crispy_pk_encode")
+PK_TDT_SYMBOLS = ("crispy_pk_tdt_create", "crispy_pk_tdt_destroy", "crispy_pk_tdt_tensor_spec", "crispy_pk_tdt_load", "crispy_pk_tdt_loaded",
+                  "crispy_pk_tdt_config_of", "crispy_pk_tdt_max_steps", "crispy_pk_tdt_decode_device", "crispy_pk_tdt_decode", "crispy_pk_tdt_words")
 ALL_SYMBOLS = (RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS + DIAR_SYMBOLS + DIAR_FRONT_SYMBOLS + DIAR_SEG_SYMBOLS + DIAR_EMB_SYMBOLS
-               + PK_SYMBOLS)
+               + PK_SYMBOLS + PK_TDT_SYMBOLS)
+PK_TDT_ROWS, PK_TDT_COLS, PK_TDT_MAX_FRAMES, PK_TDT_GROUP = 16, 64, 5000, 32      # crispy_amd/csrc/pk_internal.h
 PK_HEAD_DIM, PK_MAX_ROWS, PK_MAX_CLIPS, PK_ATTN_Q, PK_ATTN_K = 128, 40000, 4096, 32, 32      # crispy_amd/csrc/pk_internal.h
 EMB_HEAD, EMB_XVEC, EMB_STATS, EMB_MIN_ROWS, EMB_MAX_ROWS, EMB_TENSORS = 320, 512, 1024, 3, 30000, 815      # crispy_amd/csrc/diar_internal.h
 SEG_WINDOW, SEG_MIN_LEN, SEG_FRAMES, SEG_CLASSES = 160000, 991, 589, 7      # crispy_amd/csrc/diar_internal.h
@@ -89,6 +92,12 @@ class PkConfig(C.Structure):
     """crispy_pk_config"""
     _fields_ = [(k, C.c_int) for k in ("hidden", "layers", "heads", "ffn", "conv_kernel", "mel_bins", "sub_channels",
                                        "attention_bias", "convolution_bias", "scale_input")]
+
+
+class PkTdtConfig(C.Structure):
+    """crispy_pk_tdt_config"""
+    _fields_ = [("hidden", C.c_int), ("decoder_hidden", C.c_int), ("decoder_layers", C.c_int), ("vocab", C.c_int), ("blank", C.c_int),
+                ("n_durations", C.c_int), ("durations", C.c_int * 8), ("max_symbols_per_step", C.c_int)]
 
 
 class DiarInfo(C.Structure):
@@ -376,6 +385,20 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_pk_config_of.argtypes = [C.c_void_p, C.c_void_p]
     L.crispy_pk_encode_device.argtypes = [C.c_void_p, C.c_void_p, lp, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.crispy_pk_encode.argtypes = [C.c_void_p, C.c_void_p, lp, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.crispy_pk_tdt_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.crispy_pk_tdt_destroy.argtypes = [C.c_void_p]
+    L.crispy_pk_tdt_destroy.restype = None
+    L.crispy_pk_tdt_tensor_spec.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), lp]
+    L.crispy_pk_tdt_load.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), lp, C.c_int]
+    L.crispy_pk_tdt_loaded.argtypes = [C.c_void_p]
+    L.crispy_pk_tdt_config_of.argtypes = [C.c_void_p, C.c_void_p]
+    L.crispy_pk_tdt_max_steps.argtypes = [C.c_void_p, C.c_long]
+    L.crispy_pk_tdt_max_steps.restype = C.c_long
+    L.crispy_pk_tdt_decode_device.argtypes = [C.c_void_p, C.c_void_p, lp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.crispy_pk_tdt_decode.argtypes = [C.c_void_p, C.c_void_p, lp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.crispy_pk_tdt_words.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int, C.c_void_p, C.c_long, lp]
+    L.crispy_pk_tdt_words.restype = C.c_long
     return L
 
 

@@ -21,6 +21,18 @@ struct crispy_pk {
   }
 };
 
+struct crispy_pk_tdt {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  crispy::DevBuf<float> weights;      // the decoder as crispy_pk_tdt_load laid it out (TdtModel); empty until a load
+  crispy_pk_tdt_config cfg{};         // of the load
+  crispy::DevBuf<char> scratch;       // a call's workspace, grown on demand and kept
+  crispy::DevBuf<char> io;            // host-form frames, steps and taps
+  ~crispy_pk_tdt() {
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
 namespace crispy {
 namespace pk {
 
@@ -77,6 +89,51 @@ hipError_t launch_pos_table(const float* inv_freq, int tmax, int H, float* d_pos
 hipError_t launch_attention(const PkLayer& l, const PkTables& t, const float* d_qkv, const float* d_r, int tmax, int heads, float* d_out, hipStream_t st);
 // silu(scale * depthwise K-tap convolution + shift), zero-padded at each clip's own edges; [T'][H] -> [T'][H]
 hipError_t launch_dwconv(const PkLayer& l, const PkTables& t, const float* d_in, int H, int K, float* d_out, hipStream_t st);
+
+// ---- the TDT decoder (pk_tdt.hip, pk_tdt_api.cpp) -----------------------------------------------------------------------
+constexpr int kTdtRows = 16;         // clips of one workgroup of the skinny products
+constexpr int kTdtCols = 64;         // output columns of one workgroup
+constexpr int kTdtKBlock = 128;      // k of one LDS block: 32 for each of the four waves; D is a multiple of it
+constexpr int kTdtMaxFrames = 5000, kTdtMaxVocab = 65536, kTdtMaxWidth = 2048, kTdtMaxLayers = 8, kTdtMaxDurations = 8, kTdtMaxSymbols = 64;
+constexpr int kTdtGroup = 32;        // steps enqueued between two reads of the finished-clips counter
+
+inline long tdt_max_steps(int max_symbols, long frames) { return frames < 1 ? 0 : (long)max_symbols * frames - 1; }
+
+// The decoder as the kernels read it.  Every matrix is [in][out].  An LSTM layer is one matrix [2D][4D]: rows 0 ... D - 1 are
+// W_ih, rows D ... 2D - 1 W_hh, and column 4 j + q is gate q (i, f, g, o) of unit j, so that one workgroup's 64 columns are 16
+// whole units; its bias is b_ih + b_hh in the same column order.  The head is padded with zero columns to a multiple of 64.
+struct TdtModel {
+  const float *proj_w, *proj_b;                              // [H][D], [D]
+  const float* emb;                                          // [V][D]
+  const float *lstm_w[kTdtMaxLayers], *lstm_b[kTdtMaxLayers];
+  const float *dp_w, *dp_b;                                  // [D][D], [D]
+  const float *head_w, *head_b;                              // [D][n_pad], [n_pad]
+  int D, L, V, n_dur, blank, n_pad, dur[kTdtMaxDurations];
+};
+// A call's clips and everything a step decides, all in device memory.
+struct TdtState {
+  int n_clips, tiles;            // tiles = n_pad / 64
+  const int* off;                // [n + 1] first frame of each clip
+  const long* step_off;          // [n + 1] first row of each clip in steps / logits_tap: the running sum of the budgets
+  int *t, *tok, *run, *budget, *done, *finished;      // per clip: frame pointer, next input token, "run the prediction network", steps left, finished; one counter
+  float *h, *c, *hn;             // [L][n][D]: the LSTM state and a layer's new h until the next launch commits it
+  float* g;                      // [n][D] decoder_projector's output
+  const float* p;                // [sum T'][D]
+  float* part_val;               // [n][tiles] the largest token logit of a column tile ...
+  int* part_idx;                 // ... and its column
+  float* dur_logit;              // [n][8]
+  int *steps, *n_steps;          // the caller's [sum budget][3] and [n]
+  float* logits_tap;             // the caller's [sum budget][V + n_dur] or NULL
+};
+
+// t = 0, token = blank, (h, c) = 0, n_steps = 0; clips without a budget are finished from the start
+hipError_t launch_tdt_init(const TdtModel& m, const TdtState& s, hipStream_t st);
+// the prediction network on the clips whose run flag is set: one launch per LSTM layer and one for decoder_projector
+hipError_t launch_tdt_predict(const TdtModel& m, const TdtState& s, hipStream_t st);
+// logits = head(relu(p[t] + g)) for the unfinished clips; the tap, the duration logits and each column tile's token winner
+hipError_t launch_tdt_joint(const TdtModel& m, const TdtState& s, hipStream_t st);
+// per clip: the arg-max in index order, the duration rule, the step log, t, the next token and the flags
+hipError_t launch_tdt_advance(const TdtModel& m, const TdtState& s, hipStream_t st);
 
 }  // namespace pk
 }  // namespace crispy

@@ -1,5 +1,6 @@
-"""The Parakeet FastConformer encoder on the GPU (crispy_pk_*, include/crispy_hip.h): log-mel feature rows in, encoder frames out.
-The log-mel front end and the TDT decoder are not part of it."""
+"""Parakeet on the GPU (include/crispy_hip.h): the FastConformer encoder (crispy_pk_*), log-mel feature rows in, encoder frames out,
+and the greedy TDT decoder (crispy_pk_tdt_*), frames in, tokens with frame times and words out.  The log-mel front end is not
+part of it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -45,11 +46,11 @@ def pk_tensor_spec(config, lib=None):
 
 def state_dict_items(state_dict):
     """(key, f32 array) of an encoder's tensors from a torch or numpy state dict as it is: a leading `encoder.` is stripped,
-    `num_batches_tracked` entries and the `decoder.*` / `joint.*` keys of a ParakeetForTDT dict are dropped"""
+    `num_batches_tracked` entries and the `encoder_projector.*` / `decoder.*` / `joint.*` keys of a ParakeetForTDT dict are dropped"""
     items = []
     for k, v in state_dict.items():
         k = str(k)
-        if k.endswith("num_batches_tracked") or k.startswith(("decoder.", "joint.")):
+        if k.endswith("num_batches_tracked") or k.startswith(("encoder_projector.", "decoder.", "joint.")):
             continue
         if k.startswith("encoder."):
             k = k[len("encoder."):]
@@ -146,3 +147,189 @@ class ParakeetEncoder:
                                          ptr(pos)), self._L)
         cut = lambda a: [a[q[c]:q[c + 1]] for c in range(n)]
         return (cut(out), cut(sub), cut(tap), pos) if taps else cut(out)
+
+
+# ---- the TDT decoder ---------------------------------------------------------------------------------------------------------
+TDT_CONFIG_FIELDS = tuple(k for k, _t in N.PkTdtConfig._fields_)
+TDT_PREFIXES = ("encoder_projector.", "decoder.", "joint.")
+
+
+def make_tdt_config(config) -> N.PkTdtConfig:
+    """a crispy_pk_tdt_config from a mapping or an object with the fields hidden, decoder_hidden, decoder_layers, vocab, blank,
+    durations (a sequence; n_durations is its length unless given) and max_symbols_per_step"""
+    if isinstance(config, N.PkTdtConfig):
+        return config
+    get = config.__getitem__ if hasattr(config, "__getitem__") else lambda k: getattr(config, k)
+    has = (lambda k: k in config) if hasattr(config, "__contains__") else (lambda k: hasattr(config, k))
+    dur = [int(d) for d in get("durations")]
+    n = int(get("n_durations")) if has("n_durations") else len(dur)
+    if len(dur) > 8:
+        raise ValueError("at most 8 durations")
+    cfg = N.PkTdtConfig(**{k: int(get(k)) for k in TDT_CONFIG_FIELDS if k not in ("durations", "n_durations")})
+    cfg.n_durations = n
+    cfg.durations = (C.c_int * 8)(*(dur + [0] * (8 - len(dur))))
+    return cfg
+
+
+def _tdt_config_dict(cfg: N.PkTdtConfig) -> dict:
+    out = {k: int(getattr(cfg, k)) for k in TDT_CONFIG_FIELDS if k != "durations"}
+    out["durations"] = [int(d) for d in cfg.durations]
+    return out
+
+
+def pk_tdt_max_steps(config, frames: int, lib=None) -> int:
+    """the step budget of one clip of `frames` frames; no device"""
+    L = lib or N.lib()
+    cfg = make_tdt_config(config)
+    n = int(L.crispy_pk_tdt_max_steps(C.byref(cfg), int(frames)))
+    N.check(0 if n >= 0 else n, L)
+    return n
+
+
+def pk_tdt_tensor_spec(config, lib=None):
+    """[(state-dict key, element count)] crispy_pk_tdt_load expects for `config`, in state-dict order; no device"""
+    L = lib or N.lib()
+    cfg = make_tdt_config(config)
+    name, count = C.c_char_p(), C.c_long()
+    n = L.crispy_pk_tdt_tensor_spec(C.byref(cfg), 0, C.byref(name), C.byref(count))
+    N.check(0 if n > 0 else n, L)
+    out = []
+    for i in range(n):
+        N.check(0 if L.crispy_pk_tdt_tensor_spec(C.byref(cfg), i, C.byref(name), C.byref(count)) == n else -1, L)
+        out.append((name.value.decode("utf-8"), int(count.value)))
+    return out
+
+
+def tdt_state_dict_items(state_dict):
+    """(key, f32 array) of the decoder's tensors from a torch or numpy ParakeetForTDT state dict as it is: the `encoder_projector.*`,
+    `decoder.*` and `joint.*` keys; the encoder's are dropped"""
+    items = []
+    for k, v in state_dict.items():
+        k = str(k)
+        if not k.startswith(TDT_PREFIXES):
+            continue
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().float().numpy()
+        items.append((k, np.ascontiguousarray(np.asarray(v, dtype=np.float32)).reshape(-1)))
+    return items
+
+
+def pk_tdt_words(steps, pieces, frames: int, blank: int, seconds_per_frame: float = 0.08, lib=None):
+    """One clip's steps [n][3] and the vocabulary's pieces -> [(start_s, end_s, text)] (crispy_pk_tdt_words); no device"""
+    L = lib or N.lib()
+    steps = np.ascontiguousarray(steps, dtype=np.int32).reshape(-1, 3)
+    raw = (C.c_char_p * max(len(pieces), 1))(*[p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in pieces])
+    need = C.c_long()
+    args = (steps.ctypes.data if len(steps) else None, len(steps), int(frames), int(blank), raw, len(pieces), float(seconds_per_frame))
+    n = int(L.crispy_pk_tdt_words(*args, None, None, None, 0, None, 0, C.byref(need)))
+    N.check(0 if n >= 0 else n, L)
+    if n == 0:
+        return []
+    start, end, off = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int64)
+    text = C.create_string_buffer(int(need.value))
+    got = int(L.crispy_pk_tdt_words(*args, start.ctypes.data, end.ctypes.data, off.ctypes.data, n, text, int(need.value), C.byref(need)))
+    N.check(0 if got == n else min(got, -1), L)
+    raw_text = text.raw
+    return [(start[i], end[i], raw_text[off[i]:raw_text.index(b"\0", off[i])].decode("utf-8")) for i in range(n)]
+
+
+class ParakeetTDT:
+    """A crispy_pk_tdt handle: its own stream, the loaded decoder and a workspace that grows on demand."""
+
+    def __init__(self, device: int = 0, lib=None):
+        self._L = lib or N.lib()
+        self._h = C.c_void_p()
+        N.check(self._L.crispy_pk_tdt_create(int(device), C.byref(self._h)), self._L)
+
+    def close(self):
+        if self._h:
+            self._L.crispy_pk_tdt_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def load(self, config, state_dict):
+        """The decoder's weights by their state-dict keys (a whole ParakeetForTDT dict is fine); a second load replaces the first."""
+        cfg = make_tdt_config(config)
+        items = tdt_state_dict_items(state_dict)
+        n = len(items)
+        names = (C.c_char_p * max(n, 1))(*[k.encode("utf-8") for k, _a in items])
+        data = (C.c_void_p * max(n, 1))(*[a.ctypes.data for _k, a in items])
+        count = np.ascontiguousarray([a.size for _k, a in items], dtype=np.int64)
+        N.check(self._L.crispy_pk_tdt_load(self._h, C.byref(cfg), names, data, _p(count, C.c_long), n), self._L)
+
+    @property
+    def loaded(self) -> bool:
+        return bool(self._L.crispy_pk_tdt_loaded(self._h))
+
+    @property
+    def config(self) -> dict:
+        cfg = N.PkTdtConfig()
+        N.check(self._L.crispy_pk_tdt_config_of(self._h, C.byref(cfg)), self._L)
+        return _tdt_config_dict(cfg)
+
+    def _shape(self):
+        """(H, D, V + n_d, [budget(T') for a clip]) of the loaded decoder; before a load the library refuses the call itself"""
+        if not self.loaded:
+            return 1, 1, 1, lambda t: 0
+        cfg = N.PkTdtConfig()
+        N.check(self._L.crispy_pk_tdt_config_of(self._h, C.byref(cfg)), self._L)
+        m = int(cfg.max_symbols_per_step)
+        return int(cfg.hidden), int(cfg.decoder_hidden), int(cfg.vocab) + int(cfg.n_durations), lambda t: max(0, m * t - 1) if 0 < t <= 5000 else 0
+
+    @staticmethod
+    def _offsets(lengths, budget):
+        off = np.zeros(len(lengths) + 1, np.int64)
+        off[1:] = np.cumsum(lengths)
+        q = np.zeros(len(lengths) + 1, np.int64)
+        q[1:] = np.cumsum([budget(int(t)) for t in lengths])
+        return off, q
+
+    def decode_device(self, frames_list, taps: bool = False, stream=None):
+        """Clips as CUDA f32 tensors [T', H] in one ragged call -> a list of CUDA int32 tensors [n_steps, 3] (token, frame, duration);
+        with `taps` a tuple (steps, projected frames [T', D] per clip, logits [n_steps, V + n_d] per clip)."""
+        import torch
+        H, D, W, budget = self._shape()
+        rows = [f.reshape(-1, H) for f in frames_list]
+        dev = rows[0].device if rows else torch.device("cuda")
+        x = torch.cat(rows, 0).contiguous() if rows else torch.zeros((0, H), dtype=torch.float32, device=dev)
+        if x.dtype != torch.float32:
+            raise ValueError("frames must be f32 [T', hidden]")
+        n = len(rows)
+        off, q = self._offsets([int(r.shape[0]) for r in rows], budget)
+        steps = torch.zeros((int(q[-1]), 3), dtype=torch.int32, device=dev)
+        n_steps = torch.zeros((max(n, 1),), dtype=torch.int32, device=dev)
+        proj = torch.zeros((int(off[-1]), D), dtype=torch.float32, device=dev) if taps else None
+        logits = torch.zeros((int(q[-1]), W), dtype=torch.float32, device=dev) if taps else None
+        if stream is None:      # the handle's stream does not wait for torch's
+            torch.cuda.current_stream(dev).synchronize()
+        ptr = lambda a: a.data_ptr() if a is not None and a.numel() else None
+        N.check(self._L.crispy_pk_tdt_decode_device(self._h, ptr(x), _p(off, C.c_long) if n else None, n, ptr(steps), n_steps.data_ptr(), ptr(proj),
+                                                    ptr(logits), stream), self._L)
+        cnt = n_steps.cpu().numpy()
+        cut = lambda a, at, length: [a[at[c]:at[c] + length[c]] for c in range(n)]
+        out = cut(steps, q, cnt)
+        return (out, cut(proj, off, np.diff(off)), cut(logits, q, cnt)) if taps else out
+
+    def decode(self, frames_list, taps: bool = False):
+        """The same on numpy arrays through the library's host form (crispy_pk_tdt_decode) -> numpy arrays."""
+        H, D, W, budget = self._shape()
+        rows = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, H) for f in frames_list]
+        x = np.ascontiguousarray(np.concatenate(rows, 0)) if rows else np.zeros((0, H), np.float32)
+        n = len(rows)
+        off, q = self._offsets([r.shape[0] for r in rows], budget)
+        steps = np.zeros((int(q[-1]), 3), np.int32)
+        n_steps = np.zeros(max(n, 1), np.int32)
+        proj = np.zeros((int(off[-1]), D), np.float32) if taps else None
+        logits = np.zeros((int(q[-1]), W), np.float32) if taps else None
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        N.check(self._L.crispy_pk_tdt_decode(self._h, ptr(x), _p(off, C.c_long) if n else None, n, ptr(steps), n_steps.ctypes.data, ptr(proj),
+                                             ptr(logits)), self._L)
+        cut = lambda a, at, length: [a[at[c]:at[c] + length[c]] for c in range(n)]
+        out = cut(steps, q, n_steps)
+        return (out, cut(proj, off, np.diff(off)), cut(logits, q, n_steps)) if taps else out
+
+    @staticmethod
+    def words(steps, pieces, frames: int, blank: int, seconds_per_frame: float = 0.08):
+        """[(start_s, end_s, text)] of one clip's steps (pk_tdt_words)"""
+        return pk_tdt_words(steps, pieces, frames, blank, seconds_per_frame)

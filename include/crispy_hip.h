@@ -1333,6 +1333,73 @@ int crispy_pk_encode_device(void *h, const float *d_feats, const long *frame_off
 int crispy_pk_encode(void *h, const float *feats, const long *frame_offset, int n_clips, float *out, float *sub, int tap_layer, float *tap,
                      float *pos);
 
+/* ------------------------------------------------------------------------------------------
+ * Parakeet TDT decoder: greedy token-and-duration transducer decoding of the encoder's frames -- tokens with frame times, and
+ * from them the (start_s, end_s, word) records of the reference's transcribe_with_timestamps
+ * (managers/transcription.rs:196-237).  f32 operands and f32 sums throughout; the whole loop runs on the device.  New entry
+ * points only, the ABI version is unchanged.  State-dict keys are those of transformers' ParakeetForTDT behind its encoder.
+ *
+ * crispy_pk_tdt_config: hidden H (the encoder's, a multiple of 32), decoder_hidden D (a multiple of 128 up to 2048),
+ * decoder_layers L (1 ... 8), vocab V (2 ... 65536, the blank included), blank (< V), n_durations (1 ... 8) of durations[8]
+ * (non-negative, strictly ascending), max_symbols_per_step (1 ... 64).  Tensors: encoder_projector.{weight [D][H], bias},
+ * decoder.embedding.weight [V][D], decoder.lstm.{weight_ih_l*, weight_hh_l* [4D][D], bias_ih_l*, bias_hh_l*} (gates i, f, g, o),
+ * decoder.decoder_projector.{weight [D][D], bias}, joint.head.{weight [V + n_d][D], bias}.
+ *
+ * The loop on one clip's frames e[0 .. T'):  p = encoder_projector(e);  t = 0, (h, c) = 0,
+ * g = decoder_projector(lstm(embedding[blank])) (which updates the state);  at each step logits = head(relu(p[t] + g)),
+ * k = arg-max of the first V logits, d = durations[arg-max of the last n_d], ties to the lowest index; a blank with d == 0
+ * takes d = 1; the step (k, t, d) is recorded and t += d; a non-blank k runs the LSTM and the projector on embedding[k] and
+ * replaces (h, c, g), a blank leaves them.  The clip ends with t >= T' or after max_symbols_per_step * T' - 1 steps
+ * (crispy_pk_tdt_max_steps).  The emitted tokens are the steps with k != blank; a token starts at frame t and ends at
+ * min(t + d, T').
+ *
+ * Device work: all clips of a call step together.  A step is five launches at L = 2: the joint product with each column
+ * tile's arg-max, the per-clip advance (arg-max in index order, duration rule, step log, frame pointer, next token, flags, the
+ * finished-clips counter), one launch per LSTM layer and decoder_projector on the clips that emitted a token.  Every sum
+ * runs in an order fixed by its length alone and no workgroup reads another clip's state: a clip's steps and tapped logits
+ * are the same bytes alone, at any position of any batch and in any call.  The host enqueues steps in groups of 32 and reads
+ * one counter between groups; a call enqueues at most max_symbols_per_step * Tmax - 1 steps.
+ *
+ *   crispy_pk_tdt_create / _destroy / _tensor_spec / _load / _loaded / _config_of   as their crispy_pk_* namesakes, `cfg` a
+ *       (const) crispy_pk_tdt_config *.  A load takes exactly the tensors above: a ParakeetForTDT state dict without its
+ *       encoder.* keys.
+ *   crispy_pk_tdt_max_steps  the step budget of one clip of `frames` frames (0 for frames < 1); CRISPY_ERR_INVALID_ARG for a
+ *       config outside the supported set or frames > 5000.  No device.
+ *   crispy_pk_tdt_decode_device  d_frames [sum T'][H] with host frame_offset [n_clips + 1] (frame_offset[0] = 0) ->
+ *       d_steps [sum budget][3] int32 (token, frame, duration), clip c's rows starting at the sum of the budgets before it
+ *       and d_n_steps[c] of them written, the rest untouched.  1 <= n_clips <= 4096, 0 <= T' <= 5000; a clip with T' = 0
+ *       gives zero steps.  Taps, each nullable: d_proj_tap [sum T'][D] the projected frames, d_logits_tap
+ *       [sum budget][V + n_d] each step's logits in the rows of d_steps.  The logits tap is test equipment: at the catalog
+ *       widths it is 33 KB per step of budget, 123 MB for one 30 s clip.  The workspace is sized from the call and checked
+ *       against the device's free memory before any launch: too large is CRISPY_ERR_OOM with nothing enqueued.  Enqueued on
+ *       hip_stream (NULL: the handle's own), complete on return.  Before a load: CRISPY_ERR_INVALID_ARG.
+ *   crispy_pk_tdt_decode   the same call with host pointers; bit-identical results; rows behind n_steps[c] are zeros.
+ *   crispy_pk_tdt_words    host only, no device, no handle: one clip's steps -> words.  pieces: the vocabulary as `vocab`
+ *       NUL-terminated UTF-8 pieces.  A piece that begins with U+2581 starts a word, and so does the first token; the marker
+ *       is removed and pieces are concatenated; blanks never appear.  Word i starts at start_s[i] = its first token's frame
+ *       and ends at end_s[i] = its last token's min(frame + duration, frames), both times seconds_per_frame (0.08 for the
+ *       catalog models: hop 10 ms times the 8-fold subsampling); its text is the NUL-terminated string at text + text_off[i].
+ *       Returns the number of words and sets *text_needed (nullable) to the bytes the texts take with their NULs.  When
+ *       max_words or text_cap is too small (or a buffer is NULL) nothing is written: call again with what was returned.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct crispy_pk_tdt_config {
+  int hidden, decoder_hidden, decoder_layers, vocab, blank, n_durations, durations[8], max_symbols_per_step;
+} crispy_pk_tdt_config;
+
+int crispy_pk_tdt_create(int device, void **out);
+void crispy_pk_tdt_destroy(void *h);
+int crispy_pk_tdt_tensor_spec(const void *cfg, int i, const char **name, long *count);
+int crispy_pk_tdt_load(void *h, const void *cfg, const char *const *names, const float *const *data, const long *count, int n_tensors);
+int crispy_pk_tdt_loaded(void *h);
+int crispy_pk_tdt_config_of(void *h, void *cfg);
+long crispy_pk_tdt_max_steps(const void *cfg, long frames);
+int crispy_pk_tdt_decode_device(void *h, const float *d_frames, const long *frame_offset, int n_clips, int *d_steps, int *d_n_steps,
+                                float *d_proj_tap, float *d_logits_tap, void *hip_stream);
+int crispy_pk_tdt_decode(void *h, const float *frames, const long *frame_offset, int n_clips, int *steps, int *n_steps, float *proj_tap,
+                         float *logits_tap);
+long crispy_pk_tdt_words(const int *steps, int n_steps, int frames, int blank, const char *const *pieces, int vocab, double seconds_per_frame,
+                         float *start_s, float *end_s, long *text_off, int max_words, char *text, long text_cap, long *text_needed);
+
 #ifdef __cplusplus
 }
 #endif
