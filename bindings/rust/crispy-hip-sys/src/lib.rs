@@ -401,6 +401,15 @@ extern "C" {
     pub fn crispy_pk_tdt_decode_device(h: *mut c_void, d_frames: *const c_float, frame_offset: *const c_long, n_clips: c_int, d_steps: *mut c_int, d_n_steps: *mut c_int, d_proj_tap: *mut c_float, d_logits_tap: *mut c_float, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_pk_tdt_decode(h: *mut c_void, frames: *const c_float, frame_offset: *const c_long, n_clips: c_int, steps: *mut c_int, n_steps: *mut c_int, proj_tap: *mut c_float, logits_tap: *mut c_float) -> c_int;
     pub fn crispy_pk_tdt_words(steps: *const c_int, n_steps: c_int, frames: c_int, blank: c_int, pieces: *const *const c_char, vocab: c_int, seconds_per_frame: f64, start_s: *mut c_float, end_s: *mut c_float, text_off: *mut c_long, max_words: c_int, text: *mut c_char, text_cap: c_long, text_needed: *mut c_long) -> c_long;
+
+    // Parakeet front end; `h` / `h_enc` is a `crispy_pk_create` handle, `h_tdt` a `crispy_pk_tdt_create` handle
+    pub fn crispy_pk_feature_rows(samples: c_long) -> c_long;
+    pub fn crispy_pk_mel_filters(mel_bins: c_int, fb: *mut c_float) -> c_int;
+    pub fn crispy_pk_set_mel_filters(h: *mut c_void, mel_bins: c_int, fb: *const c_float) -> c_int;
+    pub fn crispy_pk_features_device(h: *mut c_void, mel_bins: c_int, d_pcm: *const c_float, sample_offset: *const c_long, n_clips: c_int, d_feats: *mut c_float, d_raw_tap: *mut c_float, d_stats_tap: *mut c_float, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_pk_features(h: *mut c_void, mel_bins: c_int, pcm: *const c_float, sample_offset: *const c_long, n_clips: c_int, feats: *mut c_float, raw_tap: *mut c_float, stats_tap: *mut c_float) -> c_int;
+    pub fn crispy_pk_transcribe_device(h_enc: *mut c_void, h_tdt: *mut c_void, d_pcm: *const c_float, sample_offset: *const c_long, n_clips: c_int, d_steps: *mut c_int, d_n_steps: *mut c_int, hip_stream: *mut c_void) -> c_int;
+    pub fn crispy_pk_transcribe(h_enc: *mut c_void, h_tdt: *mut c_void, pcm: *const c_float, sample_offset: *const c_long, n_clips: c_int, steps: *mut c_int, n_steps: *mut c_int) -> c_int;
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -76,8 +76,11 @@ PK_SYMBOLS = ("crispy_pk_create", "crispy_pk_destroy", "crispy_pk_frames", "cris
               "crispy_pk_config_of", "crispy_pk_encode_device", "crispy_pk_encode")
 PK_TDT_SYMBOLS = ("crispy_pk_tdt_create", "crispy_pk_tdt_destroy", "crispy_pk_tdt_tensor_spec", "crispy_pk_tdt_load", "crispy_pk_tdt_loaded",
                   "crispy_pk_tdt_config_of", "crispy_pk_tdt_max_steps", "crispy_pk_tdt_decode_device", "crispy_pk_tdt_decode", "crispy_pk_tdt_words")
+PK_MEL_SYMBOLS = ("crispy_pk_feature_rows", "crispy_pk_mel_filters", "crispy_pk_set_mel_filters", "crispy_pk_features_device", "crispy_pk_features",
+                  "crispy_pk_transcribe_device", "crispy_pk_transcribe")
 ALL_SYMBOLS = (RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS + DIAR_SYMBOLS + DIAR_FRONT_SYMBOLS + DIAR_SEG_SYMBOLS + DIAR_EMB_SYMBOLS
-               + PK_SYMBOLS + PK_TDT_SYMBOLS)
+               + PK_SYMBOLS + PK_TDT_SYMBOLS + PK_MEL_SYMBOLS)
+PK_MEL_SPEC, PK_MEL_MAX_BINS, PK_MEL_MAX_TAPS, PK_MEL_MIN_SAMPLES, PK_MEL_TILE_FRAMES = 257, 128, 4096, 320, 32      # crispy_amd/csrc/pk_internal.h
 PK_TDT_ROWS, PK_TDT_COLS, PK_TDT_MAX_FRAMES, PK_TDT_GROUP = 16, 64, 5000, 32      # crispy_amd/csrc/pk_internal.h
 PK_HEAD_DIM, PK_MAX_ROWS, PK_MAX_CLIPS, PK_ATTN_Q, PK_ATTN_K = 128, 40000, 4096, 32, 32      # crispy_amd/csrc/pk_internal.h
 EMB_HEAD, EMB_XVEC, EMB_STATS, EMB_MIN_ROWS, EMB_MAX_ROWS, EMB_TENSORS = 320, 512, 1024, 3, 30000, 815      # crispy_amd/csrc/diar_internal.h
@@ -399,6 +402,14 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_pk_tdt_words.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int, C.c_void_p, C.c_long, lp]
     L.crispy_pk_tdt_words.restype = C.c_long
+    L.crispy_pk_feature_rows.argtypes = [C.c_long]
+    L.crispy_pk_feature_rows.restype = C.c_long
+    L.crispy_pk_mel_filters.argtypes = [C.c_int, C.c_void_p]
+    L.crispy_pk_set_mel_filters.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.crispy_pk_features_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, lp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.crispy_pk_features.argtypes = [C.c_void_p, C.c_int, C.c_void_p, lp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.crispy_pk_transcribe_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, lp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.crispy_pk_transcribe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, lp, C.c_int, C.c_void_p, C.c_void_p]
     return L
 
 

@@ -1,6 +1,7 @@
 // pk_api.cpp -- host side of the Parakeet FastConformer encoder (include/crispy_hip.h, "Parakeet encoder"; kernels in pk_sub.hip,
 // pk_gemm.hip and pk_attn.hip): the tensor table of crispy_pk_tensor_spec and crispy_pk_load, the folds and the layout of the
-// handle's device copy, the workspace and the launches of a call.
+// handle's device copy, the workspace and the launches of a call; and crispy_pk_transcribe ("Parakeet front end"), which joins the
+// front end (pk_mel_api.cpp), the encoder and the decoder (pk_tdt_api.cpp) in one call.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -227,9 +228,10 @@ int check_call(const char* who, const crispy_pk* h, const long* frame_offset, in
   return CRISPY_OK;
 }
 
-// The encoder on n_clips clips of feature rows; the arguments have been checked.
+// The encoder on n_clips clips of feature rows; the arguments have been checked.  With `wait` the call is complete on return;
+// without, it is enqueued (crispy_pk_transcribe: the decoder's stream waits for an event instead).
 int pk_run(crispy_pk* h, const float* d_feats, const long* frame_offset, int n_clips, float* d_out, float* d_sub, int tap_layer, float* d_tap,
-           float* d_pos, hipStream_t st) {
+           float* d_pos, hipStream_t st, bool wait = true) {
   const crispy_pk_config& cfg = h->cfg;
   const int H = cfg.hidden, C = cfg.sub_channels, M = cfg.mel_bins;
   std::vector<int> tab((size_t)4 * (n_clips + 1), 0);
@@ -312,9 +314,67 @@ int pk_run(crispy_pk* h, const float* d_feats, const long* frame_offset, int n_c
     if (d_tap && li == tap_layer)
       HIP_TRY(hipMemcpyAsync(d_tap, last ? d_out : w.x, (size_t)T * H * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
-  HIP_TRY(hipStreamSynchronize(st));
+  if (wait || tl.on) HIP_TRY(hipStreamSynchronize(st));
   tl.report();
   return CRISPY_OK;
+}
+
+// ---- crispy_pk_transcribe: features, encoder and decoder in one call ------------------------------------------------------
+struct Chain {
+  std::vector<long> row_off, frame_off;      // [n_clips + 1] each
+  long budget = 0;                           // rows of the step log
+};
+
+// Everything that refuses a call, before anything is enqueued.
+int check_transcribe(const char* who, const crispy_pk* e, const crispy_pk_tdt* d, const long* sample_offset, int n_clips, Chain& ch) {
+  if (!e || !d) return fail(CRISPY_ERR_INVALID_ARG, "%s: NULL handle", who);
+  if (!e->weights.p) return fail(CRISPY_ERR_INVALID_ARG, "%s: no encoder is loaded (crispy_pk_load comes first)", who);
+  if (!d->weights.p) return fail(CRISPY_ERR_INVALID_ARG, "%s: no decoder is loaded (crispy_pk_tdt_load comes first)", who);
+  if (e->cfg.hidden != d->cfg.hidden)
+    return fail(CRISPY_ERR_INVALID_ARG, "%s: the encoder's hidden %d is not the decoder's (%d)", who, e->cfg.hidden, d->cfg.hidden);
+  if (e->device != d->device) return fail(CRISPY_ERR_INVALID_ARG, "%s: the encoder is on device %d, the decoder on device %d", who, e->device, d->device);
+  if (e->cfg.mel_bins > kMelMaxBins) return fail(CRISPY_ERR_INVALID_ARG, "%s: the front end has at most %d mel bins, the encoder %d", who, kMelMaxBins, e->cfg.mel_bins);
+  if (!e->mel_fb.empty() && e->mel_fb_bins != e->cfg.mel_bins)
+    return fail(CRISPY_ERR_INVALID_ARG, "%s: the filters set with crispy_pk_set_mel_filters have %d bins, the encoder %d", who, e->mel_fb_bins, e->cfg.mel_bins);
+  const int rc = mel_check_offsets(who, sample_offset, n_clips);
+  if (rc != CRISPY_OK) return rc;
+  ch.row_off.assign((size_t)n_clips + 1, 0);
+  ch.frame_off.assign((size_t)n_clips + 1, 0);
+  for (int c = 0; c < n_clips; ++c) {
+    const long rows = mel_rows(sample_offset[c + 1] - sample_offset[c]), t = frames(rows);
+    ch.row_off[(size_t)c + 1] = ch.row_off[(size_t)c] + rows;
+    ch.frame_off[(size_t)c + 1] = ch.frame_off[(size_t)c] + t;
+    ch.budget += tdt_max_steps(d->cfg.max_symbols_per_step, t);
+  }
+  return CRISPY_OK;
+}
+
+// The three stages; the arguments have been checked.  st == NULL: each handle's own stream, ordered by an event.
+int transcribe_run(crispy_pk* e, crispy_pk_tdt* d, const char* who, const float* d_pcm, const long* sample_offset, int n_clips, const Chain& ch,
+                   int* d_steps, int* d_n_steps, hipStream_t st) {
+  const size_t M = (size_t)e->cfg.mel_bins, H = (size_t)e->cfg.hidden;
+  auto round = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t rows_b = round((size_t)ch.row_off[(size_t)n_clips] * M * sizeof(float)), frames_b = round((size_t)ch.frame_off[(size_t)n_clips] * H * sizeof(float));
+  if (rows_b + frames_b > e->chain.bytes) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (rows_b + frames_b > free_b + e->chain.bytes)
+      return fail(CRISPY_ERR_OOM, "%s: the rows and frames need %zu bytes, the device has %zu free", who, rows_b + frames_b, free_b + e->chain.bytes);
+    HIP_TRY(e->chain.grow(rows_b + frames_b));
+  }
+  float* d_rows = reinterpret_cast<float*>(e->chain.p);
+  float* d_frames = reinterpret_cast<float*>(e->chain.p + rows_b);
+  hipStream_t se = st ? st : e->stream, sd = st ? st : d->stream;
+  int rc = mel_enqueue(e, who, (int)M, d_pcm, sample_offset, n_clips, d_rows, nullptr, nullptr, se);
+  if (rc != CRISPY_OK) return rc;
+  rc = pk_run(e, d_rows, ch.row_off.data(), n_clips, d_frames, nullptr, 0, nullptr, nullptr, se, false);
+  if (rc != CRISPY_OK) return rc;
+  if (se != sd) {
+    HIP_TRY(e->chain_ev.ensure(1, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(e->chain_ev[0], se));
+    HIP_TRY(hipStreamWaitEvent(sd, e->chain_ev[0], 0));
+  }
+  return crispy_pk_tdt_decode_device(d, d_frames, ch.frame_off.data(), n_clips, d_steps, d_n_steps, nullptr, nullptr, sd);      // complete on return
 }
 
 }  // namespace
@@ -540,5 +600,54 @@ int crispy_pk_encode(void* hv, const float* feats, const long* frame_offset, int
   return CRISPY_OK;
 }
 CRISPY_CATCH_RET("crispy_pk_encode")
+
+int crispy_pk_transcribe_device(void* h_enc, void* h_tdt, const float* d_pcm, const long* sample_offset, int n_clips, int* d_steps, int* d_n_steps,
+                                void* hip_stream) try {
+  const char* who = "crispy_pk_transcribe_device";
+  crispy_pk* e = static_cast<crispy_pk*>(h_enc);
+  crispy_pk_tdt* d = static_cast<crispy_pk_tdt*>(h_tdt);
+  Chain ch;
+  const int rc = check_transcribe(who, e, d, sample_offset, n_clips, ch);
+  if (rc != CRISPY_OK) return rc;
+  if (!d_pcm || !d_n_steps) return fail(CRISPY_ERR_INVALID_ARG, "%s: d_pcm or d_n_steps is NULL", who);
+  if (ch.budget > 0 && !d_steps) return fail(CRISPY_ERR_INVALID_ARG, "%s: d_steps is NULL", who);
+  HIP_TRY(hipSetDevice(e->device));
+  return transcribe_run(e, d, who, d_pcm, sample_offset, n_clips, ch, d_steps, d_n_steps, static_cast<hipStream_t>(hip_stream));
+}
+CRISPY_CATCH_RET("crispy_pk_transcribe_device")
+
+int crispy_pk_transcribe(void* h_enc, void* h_tdt, const float* pcm, const long* sample_offset, int n_clips, int* steps, int* n_steps) try {
+  const char* who = "crispy_pk_transcribe";
+  crispy_pk* e = static_cast<crispy_pk*>(h_enc);
+  crispy_pk_tdt* d = static_cast<crispy_pk_tdt*>(h_tdt);
+  Chain ch;
+  const int rc0 = check_transcribe(who, e, d, sample_offset, n_clips, ch);
+  if (rc0 != CRISPY_OK) return rc0;
+  if (!pcm || !n_steps) return fail(CRISPY_ERR_INVALID_ARG, "%s: pcm or n_steps is NULL", who);
+  const size_t B = (size_t)ch.budget, n = (size_t)sample_offset[n_clips];
+  if (B > 0 && !steps) return fail(CRISPY_ERR_INVALID_ARG, "%s: steps is NULL", who);
+  auto round = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t pcm_b = round(n * sizeof(float)), steps_b = round(B * 3 * sizeof(int)), n_b = round((size_t)n_clips * sizeof(int));
+  const size_t need = pcm_b + steps_b + n_b;
+  HIP_TRY(hipSetDevice(e->device));
+  if (need > e->io.bytes) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b + e->io.bytes) return fail(CRISPY_ERR_OOM, "%s: the call's buffers need %zu bytes, the device has %zu free", who, need, free_b + e->io.bytes);
+    HIP_TRY(e->io.grow(need));
+  }
+  float* d_pcm = reinterpret_cast<float*>(e->io.p);
+  int* d_steps = reinterpret_cast<int*>(e->io.p + pcm_b);
+  int* d_n = reinterpret_cast<int*>(e->io.p + pcm_b + steps_b);
+  HIP_TRY(hipMemcpyAsync(d_pcm, pcm, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  if (B > 0) HIP_TRY(hipMemsetAsync(d_steps, 0, B * 3 * sizeof(int), e->stream));      // rows behind a clip's n_steps read as zeros
+  const int rc = transcribe_run(e, d, who, d_pcm, sample_offset, n_clips, ch, d_steps, d_n, nullptr);
+  if (rc != CRISPY_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(n_steps, d_n, (size_t)n_clips * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (B > 0) HIP_TRY(hipMemcpyAsync(steps, d_steps, B * 3 * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return CRISPY_OK;
+}
+CRISPY_CATCH_RET("crispy_pk_transcribe")
 
 }  // extern "C"

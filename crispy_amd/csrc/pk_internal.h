@@ -1,5 +1,6 @@
 // pk_internal.h -- what the host side (pk_api.cpp) and the device side (pk_sub.hip, pk_gemm.hip, pk_attn.hip) of the Parakeet
-// FastConformer encoder share: the handle, the model as the kernels read it and the launch functions.
+// FastConformer encoder share: the handle, the model as the kernels read it and the launch functions; the same for the TDT
+// decoder (pk_tdt_api.cpp, pk_tdt.hip) and the log-mel front end (pk_mel_api.cpp, pk_mel.hip).
 #pragma once
 #include <cstddef>
 #include <vector>
@@ -16,6 +17,15 @@ struct crispy_pk {
   crispy_pk_config cfg{};             // of the load
   crispy::DevBuf<char> scratch;       // a call's workspace, grown on demand and kept
   crispy::DevBuf<char> io;            // host-form features, frames and taps
+  // the log-mel front end (pk_mel_api.cpp); usable before a load
+  std::vector<float> mel_fb;          // the caller's filter matrix [mel_fb_bins][257] (crispy_pk_set_mel_filters); empty: the built-in filters
+  int mel_fb_bins = 0;
+  crispy::DevBuf<char> mel_tab;       // MelTables for mel_tab_bins bins; 0: to be built by the next call
+  int mel_tab_bins = 0;
+  crispy::DevBuf<char> mel_work;      // a features call's clip and tile lists, raw rows, partial sums and statistics
+  std::vector<char> mel_host;         // what the call copies to the device: it outlives the call's enqueued copies
+  crispy::DevBuf<char> chain;         // crispy_pk_transcribe: the feature rows and the encoder's frames
+  crispy::EventList chain_ev;         // "the frames are written", for the decoder's stream
   ~crispy_pk() {
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -134,6 +144,55 @@ hipError_t launch_tdt_predict(const TdtModel& m, const TdtState& s, hipStream_t 
 hipError_t launch_tdt_joint(const TdtModel& m, const TdtState& s, hipStream_t st);
 // per clip: the arg-max in index order, the duration rule, the step log, t, the next token and the flags
 hipError_t launch_tdt_advance(const TdtModel& m, const TdtState& s, hipStream_t st);
+
+// ---- the log-mel front end (pk_mel.hip, pk_mel_api.cpp) ------------------------------------------------------------------
+constexpr int kMelFft = 512, kMelWin = 400, kMelHop = 160, kMelSpec = kMelFft / 2 + 1;
+constexpr int kMelMaxBins = 128, kMelMaxTaps = 4096;
+constexpr long kMelMinSamples = 2 * kMelHop;      // two rows: the standard deviation divides by rows - 1
+constexpr int kMelWaveFrames = 8;                 // consecutive frames one wave transforms
+constexpr int kMelTileFrames = 32;                // frames of one workgroup (4 waves)
+
+inline long mel_rows(long samples) { return samples < 0 ? 0 : samples / kMelHop; }
+
+// What the frame kernel copies into LDS once per workgroup (the first n_taps of taps only).  Filter m is one run of weights
+// over the power bins [k0, k0 + len): meta[m] = k0 | len << 9 | (offset into taps) << 18.
+struct MelTables {
+  float2 w512[kMelFft];            // exp(-2 pi i k / 512)
+  float window[kMelWin];           // symmetric Hann
+  unsigned meta[kMelMaxBins];
+  int n_taps, pad[3];
+  float taps[kMelMaxTaps];
+};
+// Clip c of a call: where its samples start in the PCM buffer and how many, where its rows start and how many, its tiles.
+struct MelClip {
+  long first, row0;
+  int n, rows, tile0, n_tiles;
+};
+// One workgroup's frames: up to kMelTileFrames from frame0 of clip.
+struct MelTile {
+  int clip, frame0;
+};
+
+// host, no device: window and twiddles in double rounded once; `fb` [M][257] cut to runs.  CRISPY_OK, or CRISPY_ERR_INVALID_ARG
+// (with the message set) for a non-finite weight or more than kMelMaxTaps taps in all.
+int mel_tables(const char* who, int M, const float* fb, MelTables& t);
+// host, no device: the built-in Slaney filters [M][257] (Slaney scale and norm, 0 ... 8000 Hz), in double rounded once
+void mel_slaney(int M, float* fb);
+// checks a call's sample_offset: CRISPY_OK, or CRISPY_ERR_INVALID_ARG naming the clip
+int mel_check_offsets(const char* who, const long* sample_offset, int n_clips);
+// The front end on n_clips clips; the arguments have been checked.  Enqueues on st and does not wait.
+int mel_enqueue(crispy_pk* h, const char* who, int M, const float* d_pcm, const long* sample_offset, int n_clips, float* d_feats, float* d_raw_tap,
+                float* d_stats_tap, hipStream_t st);
+
+// raw rows [rows][M] of every tile's frames and, per (tile, bin), part [tile][3][M]: the tile's first value p, the sums of
+// (v - p) and (v - p)^2 over its frames in frame order, in double
+hipError_t launch_mel_frames(const MelTables* d_tab, int M, const float* d_pcm, const MelClip* d_clips, const MelTile* d_tiles, int n_tiles,
+                             float* d_raw, double* d_part, hipStream_t st);
+// stats [clip][2][M]: mean and standard deviation (divisor rows - 1) from the clip's tiles in tile order, rounded once to f32
+hipError_t launch_mel_stats(const MelClip* d_clips, int n_clips, int M, const double* d_part, float* d_stats, hipStream_t st);
+// feats = (raw - mean) / (std + 1e-5f)
+hipError_t launch_mel_normalise(const MelClip* d_clips, const MelTile* d_tiles, int n_tiles, int M, const float* d_raw, const float* d_stats,
+                                float* d_feats, hipStream_t st);
 
 }  // namespace pk
 }  // namespace crispy

@@ -1,6 +1,7 @@
-"""Parakeet on the GPU (include/crispy_hip.h): the FastConformer encoder (crispy_pk_*), log-mel feature rows in, encoder frames out,
-and the greedy TDT decoder (crispy_pk_tdt_*), frames in, tokens with frame times and words out.  The log-mel front end is not
-part of it."""
+"""Parakeet on the GPU (include/crispy_hip.h): the log-mel front end (crispy_pk_features*), 16 kHz mono f32 samples in, feature rows out;
+the FastConformer encoder (crispy_pk_*), feature rows in, encoder frames out; the greedy TDT decoder (crispy_pk_tdt_*), frames in,
+tokens with frame times and words out; and `Parakeet`, which owns both handles and goes from samples to words in one call
+(crispy_pk_transcribe)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -19,6 +20,25 @@ def _p(a, ty):
 def pk_frames(rows: int) -> int:
     """T' for `rows` feature rows (0 for rows < 1); no device"""
     return int(N.lib().crispy_pk_frames(int(rows)))
+
+
+def pk_feature_rows(samples: int) -> int:
+    """feature rows for `samples` samples at 16 kHz (samples // 160); no device"""
+    return int(N.lib().crispy_pk_feature_rows(int(samples)))
+
+
+def pk_mel_filters(mel_bins: int, lib=None) -> np.ndarray:
+    """the built-in Slaney filters [mel_bins, 257] (crispy_pk_mel_filters); no device"""
+    L = lib or N.lib()
+    fb = np.zeros((max(int(mel_bins), 0), N.PK_MEL_SPEC), np.float32)
+    N.check(L.crispy_pk_mel_filters(int(mel_bins), fb.ctypes.data if fb.size else None), L)
+    return fb
+
+
+def _sample_offsets(lengths):
+    off = np.zeros(len(lengths) + 1, np.int64)
+    off[1:] = np.cumsum(lengths)
+    return off
 
 
 def make_config(config) -> N.PkConfig:
@@ -100,6 +120,69 @@ class ParakeetEncoder:
             return 1, 1
         c = self.config
         return c["hidden"], c["mel_bins"]
+
+    def set_mel_filters(self, fb=None):
+        """Replaces the front end's built-in Slaney filters with `fb` [mel_bins, 257] (a checkpoint's own featurizer.fb); None restores
+        them."""
+        if fb is None:
+            N.check(self._L.crispy_pk_set_mel_filters(self._h, 0, None), self._L)
+            return
+        if hasattr(fb, "detach"):
+            fb = fb.detach().cpu().float().numpy()
+        fb = np.ascontiguousarray(fb, dtype=np.float32)
+        if fb.ndim != 2 or fb.shape[1] != N.PK_MEL_SPEC:
+            raise ValueError("filters must be [mel_bins, 257]")
+        N.check(self._L.crispy_pk_set_mel_filters(self._h, int(fb.shape[0]), fb.ctypes.data), self._L)
+
+    def _mel_bins(self, mel_bins):
+        if mel_bins is not None:
+            return int(mel_bins)
+        if not self.loaded:
+            raise ValueError("mel_bins is needed before a load")
+        return self.config["mel_bins"]
+
+    def features_device(self, pcm_list, mel_bins=None, taps: bool = False, stream=None):
+        """Clips as CUDA f32 tensors of 16 kHz mono samples in one ragged call -> a list of CUDA tensors [rows, mel_bins], what
+        encode_device takes; with `taps` a tuple (rows, rows before normalisation, (mean, std) [2, mel_bins] per clip).  `mel_bins`
+        defaults to the loaded encoder's."""
+        import torch
+        M = self._mel_bins(mel_bins)
+        clips = [p.reshape(-1) for p in pcm_list]
+        dev = clips[0].device if clips else torch.device("cuda")
+        x = torch.cat(clips, 0).contiguous() if clips else torch.zeros((0,), dtype=torch.float32, device=dev)
+        if x.dtype != torch.float32:
+            raise ValueError("samples must be f32")
+        n = len(clips)
+        off = _sample_offsets([int(c.shape[0]) for c in clips])
+        q = _sample_offsets([pk_feature_rows(int(c.shape[0])) for c in clips])
+        width = max(M, 0)
+        out = torch.empty((int(q[-1]), width), dtype=torch.float32, device=dev)
+        raw = torch.empty((int(q[-1]), width), dtype=torch.float32, device=dev) if taps else None
+        stats = torch.empty((n, 2, width), dtype=torch.float32, device=dev) if taps else None
+        if stream is None:      # the handle's stream does not wait for torch's
+            torch.cuda.current_stream(dev).synchronize()
+        ptr = lambda a: a.data_ptr() if a is not None and a.numel() else None
+        N.check(self._L.crispy_pk_features_device(self._h, M, ptr(x), _p(off, C.c_long) if n else None, n, ptr(out), ptr(raw), ptr(stats), stream),
+                self._L)
+        cut = lambda a: [a[q[c]:q[c + 1]] for c in range(n)]
+        return (cut(out), cut(raw), [stats[c] for c in range(n)]) if taps else cut(out)
+
+    def features(self, pcm_list, mel_bins=None, taps: bool = False):
+        """The same on numpy arrays through the library's host form (crispy_pk_features) -> numpy arrays."""
+        M = self._mel_bins(mel_bins)
+        clips = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1) for p in pcm_list]
+        x = np.ascontiguousarray(np.concatenate(clips)) if clips else np.zeros(0, np.float32)
+        n = len(clips)
+        off = _sample_offsets([c.shape[0] for c in clips])
+        q = _sample_offsets([pk_feature_rows(int(c.shape[0])) for c in clips])
+        width = max(M, 0)
+        out = np.zeros((int(q[-1]), width), np.float32)
+        raw = np.zeros((int(q[-1]), width), np.float32) if taps else None
+        stats = np.zeros((n, 2, width), np.float32) if taps else None
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        N.check(self._L.crispy_pk_features(self._h, M, ptr(x), _p(off, C.c_long) if n else None, n, ptr(out), ptr(raw), ptr(stats)), self._L)
+        cut = lambda a: [a[q[c]:q[c + 1]] for c in range(n)]
+        return (cut(out), cut(raw), [stats[c] for c in range(n)]) if taps else cut(out)
 
     def encode_device(self, feats_list, taps: bool = False, tap_layer: int = 0, stream=None):
         """Clips as CUDA f32 tensors [rows, M] in one ragged call -> a list of CUDA tensors [T', H]; with `taps` a tuple (frames,
@@ -333,3 +416,79 @@ class ParakeetTDT:
     def words(steps, pieces, frames: int, blank: int, seconds_per_frame: float = 0.08):
         """[(start_s, end_s, text)] of one clip's steps (pk_tdt_words)"""
         return pk_tdt_words(steps, pieces, frames, blank, seconds_per_frame)
+
+
+# ---- samples to words ---------------------------------------------------------------------------------------------------------
+class Parakeet:
+    """The whole arm: a ParakeetEncoder (with its log-mel front end) and a ParakeetTDT on one device, and crispy_pk_transcribe over both."""
+
+    def __init__(self, device: int = 0, lib=None):
+        self._L = lib or N.lib()
+        self.encoder = ParakeetEncoder(device, self._L)
+        self.decoder = ParakeetTDT(device, self._L)
+
+    def close(self):
+        self.encoder.close()
+        self.decoder.close()
+
+    def load(self, config, tdt_config, state_dict):
+        """One ParakeetForTDT state dict: the `encoder.*` keys go to the encoder, the rest to the decoder."""
+        self.encoder.load(config, state_dict)
+        self.decoder.load(tdt_config, state_dict)
+
+    def _layout(self, lengths):
+        """sample offsets, the frames of each clip and the first row of each clip in the step log"""
+        _h, _d, _w, budget = self.decoder._shape()
+        off = _sample_offsets(lengths)
+        frames = [pk_frames(pk_feature_rows(int(n))) for n in lengths]
+        q = _sample_offsets([budget(t) for t in frames])
+        return off, frames, q
+
+    def _result(self, steps, frames, pieces):
+        out = []
+        blank = self.decoder.config["blank"] if pieces is not None else 0
+        for s, t in zip(steps, frames):
+            r = {"steps": s}
+            if pieces is not None:
+                r["words"] = pk_tdt_words(s, pieces, t, blank, lib=self._L)
+                r["text"] = " ".join(w for _a, _b, w in r["words"]).strip()
+            out.append(r)
+        return out
+
+    def transcribe(self, pcm_list, pieces=None):
+        """Clips of 16 kHz mono f32 samples (numpy) in one ragged call (crispy_pk_transcribe) -> per clip a dict with `steps`
+        [n_steps, 3] (token, frame, duration); with the vocabulary's `pieces` also `words` [(start_s, end_s, text)] and `text`, the
+        words joined by one space."""
+        clips = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1) for p in pcm_list]
+        x = np.ascontiguousarray(np.concatenate(clips)) if clips else np.zeros(0, np.float32)
+        n = len(clips)
+        off, frames, q = self._layout([c.shape[0] for c in clips])
+        steps = np.zeros((int(q[-1]), 3), np.int32)
+        n_steps = np.zeros(max(n, 1), np.int32)
+        ptr = lambda a: a.ctypes.data if a.size else None
+        N.check(self._L.crispy_pk_transcribe(self.encoder._h, self.decoder._h, ptr(x), _p(off, C.c_long) if n else None, n, ptr(steps),
+                                             n_steps.ctypes.data), self._L)
+        return self._result([steps[q[c]:q[c] + n_steps[c]] for c in range(n)], frames, pieces)
+
+    def transcribe_device(self, pcm_list, pieces=None, stream=None):
+        """The same on CUDA f32 tensors (crispy_pk_transcribe_device); `steps` are CUDA int32 tensors."""
+        import torch
+        clips = [p.reshape(-1) for p in pcm_list]
+        dev = clips[0].device if clips else torch.device("cuda")
+        x = torch.cat(clips, 0).contiguous() if clips else torch.zeros((0,), dtype=torch.float32, device=dev)
+        if x.dtype != torch.float32:
+            raise ValueError("samples must be f32")
+        n = len(clips)
+        off, frames, q = self._layout([int(c.shape[0]) for c in clips])
+        steps = torch.zeros((int(q[-1]), 3), dtype=torch.int32, device=dev)
+        n_steps = torch.zeros((max(n, 1),), dtype=torch.int32, device=dev)
+        if stream is None:      # the handles' streams do not wait for torch's
+            torch.cuda.current_stream(dev).synchronize()
+        ptr = lambda a: a.data_ptr() if a.numel() else None
+        N.check(self._L.crispy_pk_transcribe_device(self.encoder._h, self.decoder._h, ptr(x), _p(off, C.c_long) if n else None, n, ptr(steps),
+                                                    n_steps.data_ptr(), stream), self._L)
+        cnt = n_steps.cpu().numpy()
+        cut = [steps[q[c]:q[c] + cnt[c]] for c in range(n)]
+        if pieces is None:
+            return self._result(cut, frames, None)
+        return self._result([s.cpu().numpy() for s in cut], frames, pieces)

@@ -1266,7 +1266,7 @@ int crispy_diar_embed(void *h, const void *pcm, int pcm_format, const long *firs
 /* ------------------------------------------------------------------------------------------
  * Parakeet encoder: the FastConformer encoder of parakeet-tdt-0.6b (v2 and v3), the model the reference recommends first
  * (commands/models.rs:145, managers/model.rs:150-186) -- log-mel feature rows in, encoder frames out, f32 operands and f32
- * sums throughout.  The log-mel front end and the TDT decoder are not part of it.  New entry points only: no struct of an
+ * sums throughout.  The log-mel front end and the TDT decoder have sections of their own below.  New entry points only: no struct of an
  * existing entry point grew, the ABI version is unchanged.  State-dict keys are those of transformers' ParakeetEncoder; all
  * of it is inference.
  *
@@ -1399,6 +1399,62 @@ int crispy_pk_tdt_decode(void *h, const float *frames, const long *frame_offset,
                          float *logits_tap);
 long crispy_pk_tdt_words(const int *steps, int n_steps, int frames, int blank, const char *const *pieces, int vocab, double seconds_per_frame,
                          float *start_s, float *end_s, long *text_off, int max_words, char *text, long text_cap, long *text_needed);
+
+/* ------------------------------------------------------------------------------------------
+ * Parakeet front end: the log-mel features of transformers' ParakeetFeatureExtractor from 16 kHz mono f32 samples, and the
+ * whole arm in one call -- samples in, steps (tokens with frame times) out, as the reference calls the model
+ * (engine.transcribe(&audio), managers/transcription.rs:174-249).  Exact f32 operands.  New entry points only, the ABI version
+ * is unchanged.  The entry points take the encoder's handle (crispy_pk_create); the features need no load.
+ *
+ * A clip of n samples gives rows = n / 160 (rounded down) rows of M values:
+ *   pre-emphasis   y[0] = x[0], y[i] = x[i] - f32(0.97 x[i - 1]), 0 outside the clip's own [0, n).
+ *   frames         frame t is centred at sample 160 t: a symmetric 400-point Hann window from sample 160 t - 200, zero-padded to
+ *                  512, a real 512-point transform, re^2 + im^2 over bins 0 ... 256.
+ *   mel            M filters over the 257 bins, then logf(e + 2^-24).  Built in: Slaney triangles (Slaney scale and norm,
+ *                  0 ... 8000 Hz) for any M in 1 ... 128, worked out in double and rounded once.
+ *   normalisation  per clip and bin over the clip's own rows: (v - mean) / (std + 1e-5f), std with the divisor rows - 1.
+ *
+ * Device work: three launches for all clips of a call.  The frame kernel (a workgroup per 32 consecutive frames of one clip)
+ * reads samples straight from the clip, keeps twiddles, window and filters in LDS, sums each filter's run of weights in f32 in
+ * tap order and stores the rows before normalisation and, per (tile, bin), partial sums in double about the tile's first
+ * value; a second kernel adds a clip's partial sums in tile order in double and rounds mean and std once to f32 (a constant
+ * column gives std = 0 and rows of exactly 0); a third normalises.  No atomics: a clip's rows are the same bytes alone, at any
+ * position of any batch and in any call.
+ *
+ *   crispy_pk_feature_rows   rows for `samples` samples (0 below 160).  No device.
+ *   crispy_pk_mel_filters    the built-in filters for mel_bins (1 ... 128) into fb [mel_bins][257].  No device, no handle.
+ *   crispy_pk_set_mel_filters  replaces the built-in filters of handle h with fb [mel_bins][257], for example a checkpoint's own
+ *       featurizer.fb; fb = NULL restores the built-in ones (mel_bins is then ignored).  Each filter is stored as the one run
+ *       of bins that covers its non-zero weights; a non-finite weight or more than 4096 weights in all runs is
+ *       CRISPY_ERR_INVALID_ARG and leaves the handle as it was.
+ *   crispy_pk_features_device  d_pcm [sum n] f32 with host sample_offset [n_clips + 1] (sample_offset[0] = 0) -> d_feats
+ *       [sum rows][mel_bins], what crispy_pk_encode_device takes.  Taps, each nullable: d_raw_tap [sum rows][mel_bins] the rows
+ *       before normalisation, d_stats_tap [n_clips][2][mel_bins] each clip's mean and std.  1 <= n_clips <= 4096; a clip with
+ *       fewer than 320 samples (std would divide by 0) or more than 40000 rows is CRISPY_ERR_INVALID_ARG naming the clip, and
+ *       so is a mel_bins outside 1 ... 128, other than the loaded encoder's (after a load) or other than that of the filters
+ *       set -- all before anything is enqueued.  The workspace (rows before normalisation, 24 bytes per bin and 32 rows of
+ *       partial sums) is sized from the call and checked against the device's free memory before any launch: too large is
+ *       CRISPY_ERR_OOM.  Enqueued on hip_stream (NULL: the handle's own), complete on return.
+ *   crispy_pk_features       the same call with host pointers; bit-identical results.  There is no CPU path.
+ *   crispy_pk_transcribe_device  features, crispy_pk_encode_device and crispy_pk_tdt_decode_device in one call: d_pcm and
+ *       sample_offset as above -> d_steps and d_n_steps as crispy_pk_tdt_decode_device lays them out, clip c's rows starting
+ *       at the sum of crispy_pk_tdt_max_steps(cfg, crispy_pk_frames(rows)) before it.  Rows and frames stay in h_enc's
+ *       workspace.  With hip_stream = NULL the features and the encoder run on h_enc's stream and the decoder on h_tdt's,
+ *       which waits for an event, not the host; otherwise everything runs on hip_stream.  Refused with
+ *       CRISPY_ERR_INVALID_ARG and nothing enqueued: either handle without a load, a `hidden` that differs between the two
+ *       configs, handles on different devices, and what crispy_pk_features_device refuses.  Complete on return.
+ *   crispy_pk_transcribe     the same call with host pointers; bit-identical results; rows behind n_steps[c] are zeros.
+ * ------------------------------------------------------------------------------------------ */
+long crispy_pk_feature_rows(long samples);
+int crispy_pk_mel_filters(int mel_bins, float *fb);
+int crispy_pk_set_mel_filters(void *h, int mel_bins, const float *fb);
+int crispy_pk_features_device(void *h, int mel_bins, const float *d_pcm, const long *sample_offset, int n_clips, float *d_feats,
+                              float *d_raw_tap, float *d_stats_tap, void *hip_stream);
+int crispy_pk_features(void *h, int mel_bins, const float *pcm, const long *sample_offset, int n_clips, float *feats, float *raw_tap,
+                       float *stats_tap);
+int crispy_pk_transcribe_device(void *h_enc, void *h_tdt, const float *d_pcm, const long *sample_offset, int n_clips, int *d_steps,
+                                int *d_n_steps, void *hip_stream);
+int crispy_pk_transcribe(void *h_enc, void *h_tdt, const float *pcm, const long *sample_offset, int n_clips, int *steps, int *n_steps);
 
 #ifdef __cplusplus
 }
