@@ -390,6 +390,10 @@ extern "C" {
     pub fn crispy_pk_config_of(h: *mut c_void, cfg: *mut c_void) -> c_int;
     pub fn crispy_pk_encode_device(h: *mut c_void, d_feats: *const c_float, frame_offset: *const c_long, n_clips: c_int, d_out: *mut c_float, d_sub: *mut c_float, tap_layer: c_int, d_tap: *mut c_float, d_pos: *mut c_float, hip_stream: *mut c_void) -> c_int;
     pub fn crispy_pk_encode(h: *mut c_void, feats: *const c_float, frame_offset: *const c_long, n_clips: c_int, out: *mut c_float, sub: *mut c_float, tap_layer: c_int, tap: *mut c_float, pos: *mut c_float) -> c_int;
+    // Parakeet encoder, precision mode 1 (f16 operands, f32 sums); `epilogue` is CRISPY_PK_GEMM_SCALE 0, _SILU 1, _RESIDUAL 2, _GLU 3
+    pub fn crispy_pk_set_precision(h: *mut c_void, mode: c_int) -> c_int;
+    pub fn crispy_pk_precision(h: *mut c_void) -> c_int;
+    pub fn crispy_pk_stage_gemm_device(h: *mut c_void, mode: c_int, epilogue: c_int, d_a: *const c_float, m: c_long, k: c_int, d_w: *const c_float, d_bias: *const c_float, n: c_int, alpha: c_float, d_res: *const c_float, d_c: *mut c_float) -> c_int;
     // Parakeet TDT decoder; `cfg` points at a `crispy_pk_tdt_config`
     pub fn crispy_pk_tdt_create(device: c_int, out: *mut *mut c_void) -> c_int;
     pub fn crispy_pk_tdt_destroy(h: *mut c_void);

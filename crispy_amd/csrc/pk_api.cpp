@@ -1,6 +1,6 @@
 // pk_api.cpp -- host side of the Parakeet FastConformer encoder (include/crispy_hip.h, "Parakeet encoder"; kernels in pk_sub.hip,
-// pk_gemm.hip and pk_attn.hip): the tensor table of crispy_pk_tensor_spec and crispy_pk_load, the folds and the layout of the
-// handle's device copy, the workspace and the launches of a call; and crispy_pk_transcribe ("Parakeet front end"), which joins the
+// pk_gemm.hip, pk_gemm_f16.hip and pk_attn.hip): the tensor table of crispy_pk_tensor_spec and crispy_pk_load, the folds and the layout of the
+// handle's device copy, precision mode 1's f16 copies of the GEMM weights, the workspace and the launches of a call; and crispy_pk_transcribe ("Parakeet front end"), which joins the
 // front end (pk_mel_api.cpp), the encoder and the decoder (pk_tdt_api.cpp) in one call.
 #include <cmath>
 #include <cstdio>
@@ -150,11 +150,66 @@ void put_transposed(const float* src, size_t out_n, size_t in_n, size_t taps, co
       for (size_t k = 0; k < taps; ++k) wr(dst)[(k * in_n + i) * ld + col0 + o] = src[(o * in_n + i) * taps + k];
 }
 
-// pointwise_conv1's column of output channel o (0 ... 2H - 1): groups of 64 columns hold 32 value channels, then their gates
-size_t glu_column(size_t o, size_t H) {
-  const bool gate = o >= H;
-  const size_t ch = gate ? o - H : o;
-  return (ch / 32) * 64 + (gate ? 32 : 0) + ch % 32;
+// ---- mode 1's f16 copies of the GEMM weights ------------------------------------------------------------------------------
+// Visits every matrix that launch_gemm multiplies by in a call, in a fixed order, with its f16 slot and its [K][cols] shape.
+template <class V>
+void walk_half(const PkModel& m, PkHalfModel& hm, const crispy_pk_config& c, V&& v) {
+  const size_t H = (size_t)c.hidden, F = (size_t)c.ffn;
+  v(m.lin_w, hm.lin_w, (size_t)c.sub_channels * (size_t)(c.mel_bins / 8), H);
+  hm.layer.resize((size_t)c.layers);
+  for (size_t li = 0; li < hm.layer.size(); ++li) {
+    const PkLayer& l = m.layer[li];
+    PkHalfLayer& h = hm.layer[li];
+    for (int i = 0; i < 2; ++i) {
+      v(l.ff_w1[i], h.ff_w1[i], H, F);
+      v(l.ff_w2[i], h.ff_w2[i], F, H);
+    }
+    v(l.qkv_w, h.qkv_w, H, 3 * H);
+    v(l.o_w, h.o_w, H, H);
+    v(l.r_w, h.r_w, H, H);
+    v(l.pw1_w, h.pw1_w, H, 2 * H);
+    v(l.pw2_w, h.pw2_w, H, H);
+  }
+}
+
+size_t half_bytes(const crispy_pk_config& c) {
+  PkModel m{};      // only the shapes are visited
+  m.layer.resize((size_t)c.layers);
+  PkHalfModel hm;
+  size_t at = 0;
+  walk_half(m, hm, c, [&at](const float*, const void*&, size_t K, size_t N) { at += (K * N * 2 + 255) & ~(size_t)255; });
+  return at;
+}
+
+PkHalfModel half_of(const char* base, const PkModel& m, const crispy_pk_config& c) {      // base == NULL (mode 0): every slot NULL
+  PkHalfModel hm;
+  size_t at = 0;
+  walk_half(m, hm, c, [&at, base](const float*, const void*& p, size_t K, size_t N) {
+    p = base ? base + at : nullptr;
+    at += (K * N * 2 + 255) & ~(size_t)255;
+  });
+  return hm;
+}
+
+// Packs the f16 copies of the model at `weights` into a fresh allocation, on the device, and waits.  The size is checked against
+// the device's free memory first: CRISPY_ERR_OOM leaves `out` as it was with nothing enqueued.
+int pack_half(const char* who, const float* weights, const crispy_pk_config& cfg, hipStream_t st, crispy::DevBuf<char>& out) {
+  const size_t need = half_bytes(cfg);
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (need > free_b) return fail(CRISPY_ERR_OOM, "%s: the f16 copies of the weights need %zu bytes, the device has %zu free", who, need, free_b);
+  crispy::DevBuf<char> fresh;
+  HIP_TRY(fresh.alloc(need));
+  const PkModel m = model_of(weights, cfg);
+  PkHalfModel hm = half_of(fresh.p, m, cfg);
+  hipError_t err = hipSuccess;
+  walk_half(m, hm, cfg, [&](const float* src, const void*& dst, size_t K, size_t N) {
+    if (err == hipSuccess) err = launch_pack_f16(src, (int)K, (int)N, const_cast<void*>(dst), st);
+  });
+  HIP_TRY(err);
+  HIP_TRY(hipStreamSynchronize(st));
+  out = std::move(fresh);
+  return CRISPY_OK;
 }
 
 // ---- a call's workspace ---------------------------------------------------------------------------------------------
@@ -263,6 +318,8 @@ int pk_run(crispy_pk* h, const float* d_feats, const long* frame_offset, int n_c
   carve(place, w, cfg, len, (size_t)n_clips, (size_t)tmax);
   for (int s = 0; s < 4; ++s) tb.off[s] = w.tab + (size_t)s * (n_clips + 1);
   const PkModel m = model_of(h->weights.p, cfg);
+  const int mode = h->precision;      // 1: crispy_pk_set_precision or crispy_pk_load packed the f16 copies
+  const PkHalfModel hm = half_of(mode == 1 ? h->weights16.p : nullptr, m, cfg);
   const long T = (long)len[3];
   Timeline tl;
   tl.on = crispy::dev_env("CRISPY_PK_TIMELINE") != nullptr;
@@ -272,18 +329,19 @@ int pk_run(crispy_pk* h, const float* d_feats, const long* frame_offset, int n_c
   HIP_TRY(launch_sub_dwpw(1, m, tb, w.img1, M / 2, C, w.img2, false, st));
   HIP_TRY(launch_sub_dwpw(2, m, tb, w.img2, M / 4, C, w.flat, true, st));
   HIP_TRY(tl.mark(kStSub, st));
-  HIP_TRY(launch_gemm(kGemmScale, w.flat, C * (M / 8), m.lin_w, m.lin_b, H, cfg.scale_input ? std::sqrt((float)H) : 1.0f, nullptr, w.x, T, st));
+  HIP_TRY(launch_gemm(mode, kGemmScale, w.flat, C * (M / 8), m.lin_w, hm.lin_w, m.lin_b, H, cfg.scale_input ? std::sqrt((float)H) : 1.0f, nullptr, w.x, T, st));
   float* pos = d_pos ? d_pos : w.pos;
   HIP_TRY(launch_pos_table(m.inv_freq, tmax, H, pos, st));
   HIP_TRY(tl.mark(kStGemm, st));
   if (d_sub) HIP_TRY(hipMemcpyAsync(d_sub, w.x, (size_t)T * H * sizeof(float), hipMemcpyDeviceToDevice, st));
   for (int li = 0; li < cfg.layers; ++li) {
     const PkLayer& l = m.layer[(size_t)li];
+    const PkHalfLayer& lh = hm.layer[(size_t)li];
     auto ff = [&](int i) -> int {
       HIP_TRY(launch_layernorm(w.x, l.ln_g[i ? 3 : 0], l.ln_b[i ? 3 : 0], w.ln, T, H, st));
       HIP_TRY(tl.mark(kStNorm, st));
-      HIP_TRY(launch_gemm(kGemmSilu, w.ln, H, l.ff_w1[i], l.ff_b1[i], cfg.ffn, 1.0f, nullptr, w.big, T, st));
-      HIP_TRY(launch_gemm(kGemmResidual, w.big, cfg.ffn, l.ff_w2[i], l.ff_b2[i], H, 0.5f, w.x, w.x, T, st));
+      HIP_TRY(launch_gemm(mode, kGemmSilu, w.ln, H, l.ff_w1[i], lh.ff_w1[i], l.ff_b1[i], cfg.ffn, 1.0f, nullptr, w.big, T, st));
+      HIP_TRY(launch_gemm(mode, kGemmResidual, w.big, cfg.ffn, l.ff_w2[i], lh.ff_w2[i], l.ff_b2[i], H, 0.5f, w.x, w.x, T, st));
       HIP_TRY(tl.mark(kStGemm, st));
       return CRISPY_OK;
     };
@@ -291,20 +349,20 @@ int pk_run(crispy_pk* h, const float* d_feats, const long* frame_offset, int n_c
     if (rc != CRISPY_OK) return rc;
     HIP_TRY(launch_layernorm(w.x, l.ln_g[1], l.ln_b[1], w.ln, T, H, st));
     HIP_TRY(tl.mark(kStNorm, st));
-    HIP_TRY(launch_gemm(kGemmScale, w.ln, H, l.qkv_w, l.qkv_b, 3 * H, 1.0f, nullptr, w.big, T, st));
-    HIP_TRY(launch_gemm(kGemmScale, pos, H, l.r_w, nullptr, H, 1.0f, nullptr, w.r, 2L * tmax - 1, st));
+    HIP_TRY(launch_gemm(mode, kGemmScale, w.ln, H, l.qkv_w, lh.qkv_w, l.qkv_b, 3 * H, 1.0f, nullptr, w.big, T, st));
+    HIP_TRY(launch_gemm(mode, kGemmScale, pos, H, l.r_w, lh.r_w, nullptr, H, 1.0f, nullptr, w.r, 2L * tmax - 1, st));
     HIP_TRY(tl.mark(kStGemm, st));
     HIP_TRY(launch_attention(l, tb, w.big, w.r, tmax, cfg.heads, w.mid, st));
     HIP_TRY(tl.mark(kStAttn, st));
-    HIP_TRY(launch_gemm(kGemmResidual, w.mid, H, l.o_w, l.o_b, H, 1.0f, w.x, w.x, T, st));
+    HIP_TRY(launch_gemm(mode, kGemmResidual, w.mid, H, l.o_w, lh.o_w, l.o_b, H, 1.0f, w.x, w.x, T, st));
     HIP_TRY(tl.mark(kStGemm, st));
     HIP_TRY(launch_layernorm(w.x, l.ln_g[2], l.ln_b[2], w.ln, T, H, st));
     HIP_TRY(tl.mark(kStNorm, st));
-    HIP_TRY(launch_gemm(kGemmGlu, w.ln, H, l.pw1_w, l.pw1_b, H, 1.0f, nullptr, w.mid, T, st));
+    HIP_TRY(launch_gemm(mode, kGemmGlu, w.ln, H, l.pw1_w, lh.pw1_w, l.pw1_b, H, 1.0f, nullptr, w.mid, T, st));
     HIP_TRY(tl.mark(kStGemm, st));
     HIP_TRY(launch_dwconv(l, tb, w.mid, H, cfg.conv_kernel, w.ln, st));
     HIP_TRY(tl.mark(kStConv, st));
-    HIP_TRY(launch_gemm(kGemmResidual, w.ln, H, l.pw2_w, l.pw2_b, H, 1.0f, w.x, w.x, T, st));
+    HIP_TRY(launch_gemm(mode, kGemmResidual, w.ln, H, l.pw2_w, lh.pw2_w, l.pw2_b, H, 1.0f, w.x, w.x, T, st));
     HIP_TRY(tl.mark(kStGemm, st));
     rc = ff(1);
     if (rc != CRISPY_OK) return rc;
@@ -530,7 +588,13 @@ int crispy_pk_load(void* hv, const void* cfgv, const char* const* names, const f
   crispy::DevBuf<float> fresh;
   HIP_TRY(fresh.alloc(total * sizeof(float)));
   HIP_TRY(hipMemcpy(fresh.p, blob.data(), total * sizeof(float), hipMemcpyHostToDevice));
+  crispy::DevBuf<char> fresh16;      // the f16 copies of an earlier load go with it, in either mode
+  if (h->precision == 1) {           // the mode survives the load: what does not fit refuses it, and the handle keeps what it had
+    const int rc16 = pack_half(who, fresh.p, cfg, h->stream, fresh16);
+    if (rc16 != CRISPY_OK) return rc16;
+  }
   h->weights = std::move(fresh);      // the copy of an earlier load goes with `fresh`
+  h->weights16 = std::move(fresh16);
   h->cfg = cfg;
   return CRISPY_OK;
 }
@@ -551,6 +615,69 @@ int crispy_pk_config_of(void* hv, void* cfg) try {
   return CRISPY_OK;
 }
 CRISPY_CATCH_RET("crispy_pk_config_of")
+
+int crispy_pk_set_precision(void* hv, int mode) try {
+  const char* who = "crispy_pk_set_precision";
+  crispy_pk* h = static_cast<crispy_pk*>(hv);
+  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "%s: NULL handle", who);
+  if (mode != 0 && mode != 1) return fail(CRISPY_ERR_INVALID_ARG, "%s: mode %d is neither 0 nor 1", who, mode);
+  if (mode == 1 && h->weights.p && !h->weights16.p) {      // the first time a loaded handle is in mode 1
+    HIP_TRY(hipSetDevice(h->device));
+    const int rc = pack_half(who, h->weights.p, h->cfg, h->stream, h->weights16);
+    if (rc != CRISPY_OK) return rc;      // the handle stays in the mode it had
+  }
+  h->precision = mode;
+  return CRISPY_OK;
+}
+CRISPY_CATCH_RET("crispy_pk_set_precision")
+
+int crispy_pk_precision(void* hv) try {
+  const crispy_pk* h = static_cast<const crispy_pk*>(hv);
+  return h ? h->precision : 0;
+}
+CRISPY_CATCH_RET("crispy_pk_precision")
+
+int crispy_pk_stage_gemm_device(void* hv, int mode, int epilogue, const float* d_a, long M, int K, const float* d_w, const float* d_bias, int N,
+                                float alpha, const float* d_res, float* d_c) try {
+  const char* who = "crispy_pk_stage_gemm_device";
+  crispy_pk* h = static_cast<crispy_pk*>(hv);
+  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "%s: NULL handle", who);
+  if (mode != 0 && mode != 1) return fail(CRISPY_ERR_INVALID_ARG, "%s: mode %d is neither 0 nor 1", who, mode);
+  if (epilogue < kGemmScale || epilogue > kGemmGlu) return fail(CRISPY_ERR_INVALID_ARG, "%s: epilogue %d outside 0 ... 3", who, epilogue);
+  const GemmEpilogue e = static_cast<GemmEpilogue>(epilogue);
+  if (!d_a || !d_w || !d_c) return fail(CRISPY_ERR_INVALID_ARG, "%s: d_a, d_w or d_c is NULL", who);
+  if (M < 1 || M > 0x7fffffffL) return fail(CRISPY_ERR_INVALID_ARG, "%s: M %ld outside 1 ... 2^31 - 1", who, M);
+  if (K < 32 || K > 65536 || K % 32 != 0) return fail(CRISPY_ERR_INVALID_ARG, "%s: K %d is not a multiple of 32 in 32 ... 65536", who, K);
+  if (N < 64 || N > 32768) return fail(CRISPY_ERR_INVALID_ARG, "%s: N %d outside 64 ... 32768", who, N);
+  const int cols = e == kGemmGlu ? 2 * N : N;
+  if (cols % 128 != 0) return fail(CRISPY_ERR_INVALID_ARG, "%s: N %d gives %d columns, not a multiple of 128", who, N, cols);
+  if (e == kGemmResidual && !d_res) return fail(CRISPY_ERR_INVALID_ARG, "%s: d_res is NULL with the residual epilogue", who);
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t bt_b = (size_t)K * cols * sizeof(float), bp_b = mode == 1 ? (size_t)K * cols * 2 : 0;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (bt_b + bp_b > free_b) return fail(CRISPY_ERR_OOM, "%s: the weight images need %zu bytes, the device has %zu free", who, bt_b + bp_b, free_b);
+  crispy::DevBuf<float> bt;      // [K][cols], as crispy_pk_load lays a weight out
+  crispy::DevBuf<char> bp;       // mode 1: its packed f16 image, as pack_half makes it
+  crispy::DevBuf<float> bias;    // the GLU: the bias in the weight's column order, as crispy_pk_load puts it
+  HIP_TRY(bt.alloc(bt_b));
+  HIP_TRY(launch_weight_transpose(d_w, K, cols, e == kGemmGlu, bt.p, h->stream));
+  if (e == kGemmGlu && d_bias) {
+    HIP_TRY(bias.alloc((size_t)cols * sizeof(float)));
+    HIP_TRY(launch_weight_transpose(d_bias, 1, cols, true, bias.p, h->stream));      // a [cols][1] matrix
+    d_bias = bias.p;
+  }
+  if (mode == 1) {
+    HIP_TRY(bp.alloc(bp_b));
+    HIP_TRY(launch_pack_f16(bt.p, K, cols, bp.p, h->stream));
+  }
+  const hipError_t err = launch_gemm(mode, e, d_a, K, bt.p, bp.p, d_bias, N, alpha, d_res, d_c, M, h->stream);
+  if (err == hipErrorInvalidValue) return fail(CRISPY_ERR_INVALID_ARG, "%s: launch_gemm refuses M %ld, K %d, N %d", who, M, K, N);
+  HIP_TRY(err);
+  HIP_TRY(hipStreamSynchronize(h->stream));      // bt and bp go with the call
+  return CRISPY_OK;
+}
+CRISPY_CATCH_RET("crispy_pk_stage_gemm_device")
 
 int crispy_pk_encode_device(void* hv, const float* d_feats, const long* frame_offset, int n_clips, float* d_out, float* d_sub, int tap_layer,
                             float* d_tap, float* d_pos, void* hip_stream) try {

@@ -108,5 +108,13 @@ hipError_t launch_gemm(GemmEpilogue e, const float* d_a, int K, const float* d_b
   return hipGetLastError();
 }
 
+// The encoder's form: the handle's precision mode picks the f32 kernel above or the f16-operand one of pk_gemm_f16.hip.
+hipError_t launch_gemm(int mode, GemmEpilogue e, const float* d_a, int K, const float* d_bt, const void* d_bp, const float* bias, int N, float alpha,
+                       const float* d_res, float* d_c, long M, hipStream_t st) {
+  if (mode == 1) return launch_gemm_f16(e, d_a, K, d_bp, bias, N, alpha, d_res, d_c, M, st);
+  if (mode != 0) return hipErrorInvalidValue;
+  return launch_gemm(e, d_a, K, d_bt, bias, N, alpha, d_res, d_c, M, st);
+}
+
 }  // namespace pk
 }  // namespace crispy

@@ -1,4 +1,4 @@
-// pk_internal.h -- what the host side (pk_api.cpp) and the device side (pk_sub.hip, pk_gemm.hip, pk_attn.hip) of the Parakeet
+// pk_internal.h -- what the host side (pk_api.cpp) and the device side (pk_sub.hip, pk_gemm.hip, pk_gemm_f16.hip, pk_attn.hip) of the Parakeet
 // FastConformer encoder share: the handle, the model as the kernels read it and the launch functions; the same for the TDT
 // decoder (pk_tdt_api.cpp, pk_tdt.hip) and the log-mel front end (pk_mel_api.cpp, pk_mel.hip).
 #pragma once
@@ -15,6 +15,8 @@ struct crispy_pk {
   hipStream_t stream = nullptr;
   crispy::DevBuf<float> weights;      // the encoder as crispy_pk_load laid it out (PkModel); empty until a load
   crispy_pk_config cfg{};             // of the load
+  int precision = 0;                  // crispy_pk_set_precision: 0 f32 operands, 1 f16 operands in every GEMM
+  crispy::DevBuf<char> weights16;     // mode 1: the GEMM weights packed as f16 (PkHalfModel); empty until the loaded handle is first in mode 1
   crispy::DevBuf<char> scratch;       // a call's workspace, grown on demand and kept
   crispy::DevBuf<char> io;            // host-form features, frames and taps
   // the log-mel front end (pk_mel_api.cpp); usable before a load
@@ -74,6 +76,21 @@ struct PkModel {
   const float* inv_freq;                        // [H / 2]
   std::vector<PkLayer> layer;
 };
+// Mode 1's copies of the GEMM weights: each the f32 matrix of the same name rounded to f16 in the operand order of
+// pk_gemm_f16.hip ([N / 32][K / 16][64 lanes][8]); all NULL in mode 0.
+struct PkHalfLayer {
+  const void *ff_w1[2], *ff_w2[2], *qkv_w, *o_w, *r_w, *pw1_w, *pw2_w;
+};
+struct PkHalfModel {
+  const void* lin_w = nullptr;
+  std::vector<PkHalfLayer> layer;
+};
+// pointwise_conv1's column of output channel o (0 ... 2H - 1): groups of 64 columns hold 32 value channels, then their gates
+__host__ __device__ inline size_t glu_column(size_t o, size_t H) {
+  const bool gate = o >= H;
+  const size_t ch = gate ? o - H : o;
+  return (ch / 32) * 64 + (gate ? 32 : 0) + ch % 32;
+}
 // A call's clips: clip c has feature rows off[0][c] ... off[0][c + 1] and off[s] likewise after s stride-2 convolutions
 // (device memory, n_clips + 1 each); max_len[s] is the longest clip's count at stage s.
 struct PkTables {
@@ -93,6 +110,17 @@ hipError_t launch_layernorm(const float* d_in, const float* g, const float* b, f
 enum GemmEpilogue { kGemmScale, kGemmSilu, kGemmResidual, kGemmGlu };
 hipError_t launch_gemm(GemmEpilogue e, const float* d_a, int K, const float* d_bt, const float* bias, int N, float alpha, const float* d_res,
                        float* d_c, long M, hipStream_t st);
+// The encoder's form, by the handle's precision mode (crispy_pk_set_precision).  0: the call above.  1: the same product with both
+// operands rounded once to f16, from the packed image d_bp of Bt (launch_pack_f16) on the f16 matrix instruction: one f32
+// accumulator per element over k ascending in steps of 16.
+hipError_t launch_gemm(int mode, GemmEpilogue e, const float* d_a, int K, const float* d_bt, const void* d_bp, const float* bias, int N, float alpha,
+                       const float* d_res, float* d_c, long M, hipStream_t st);
+// pk_gemm_f16.hip: mode 1's kernel behind launch_gemm; Bt [K][cols] f32 -> its packed f16 image of K * cols * 2 bytes; and the
+// state dict's [cols][K] -> Bt [K][cols] (glu: in pointwise_conv1's column order) for crispy_pk_stage_gemm_device
+hipError_t launch_gemm_f16(GemmEpilogue e, const float* d_a, int K, const void* d_bp, const float* bias, int N, float alpha, const float* d_res,
+                           float* d_c, long M, hipStream_t st);
+hipError_t launch_pack_f16(const float* d_bt, int K, int cols, void* d_out, hipStream_t st);
+hipError_t launch_weight_transpose(const float* d_w, int K, int cols, bool glu, float* d_bt, hipStream_t st);
 // pos [2 * tmax - 1][H]: row p is d = p - (tmax - 1); sin in the even columns, cos in the odd ones
 hipError_t launch_pos_table(const float* inv_freq, int tmax, int H, float* d_pos, hipStream_t st);
 // soft-max((q + u) k^T + (q + v) r_{i - j}^T) / sqrt(128)) v per clip and head; qkv [T'][3H], r [2 * tmax - 1][H] -> out [T'][H]

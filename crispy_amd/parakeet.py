@@ -115,6 +115,41 @@ class ParakeetEncoder:
         N.check(self._L.crispy_pk_config_of(self._h, C.byref(cfg)), self._L)
         return {k: int(getattr(cfg, k)) for k in CONFIG_FIELDS}
 
+    def set_precision(self, mode: int):
+        """0: f32 operands (the default).  1: f16 operands with f32 sums in every GEMM of the encoder (crispy_pk_set_precision); before
+        or after a load, and kept across loads."""
+        N.check(self._L.crispy_pk_set_precision(self._h, int(mode)), self._L)
+
+    @property
+    def precision(self) -> int:
+        return int(self._L.crispy_pk_precision(self._h))
+
+    def stage_gemm_device(self, mode: int, epilogue: int, a, w, bias=None, alpha: float = 1.0, res=None):
+        """One GEMM of the encoder as a stage (crispy_pk_stage_gemm_device; needs no load): CUDA f32 tensors a [M, K], w in the
+        state-dict layout [cols, K] (cols = 2 N with N.PK_GEMM_GLU), bias [cols] or None, res [M, N] for N.PK_GEMM_RESIDUAL ->
+        a CUDA tensor [M, N]."""
+        import torch
+        a, w = a.contiguous(), w.contiguous()
+        if a.dtype != torch.float32 or w.dtype != torch.float32 or a.dim() != 2 or w.dim() != 2:
+            raise ValueError("a and w must be f32 matrices")
+        M, K = int(a.shape[0]), int(a.shape[1])
+        cols = int(w.shape[0])
+        n = cols // 2 if int(epilogue) == N.PK_GEMM_GLU else cols
+        bias = bias.contiguous() if bias is not None else None
+        res = res.contiguous() if res is not None else None
+        out = torch.empty((M, n), dtype=torch.float32, device=a.device)
+        torch.cuda.current_stream(a.device).synchronize()      # the handle's stream does not wait for torch's
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        N.check(self._L.crispy_pk_stage_gemm_device(self._h, int(mode), int(epilogue), ptr(a), M, K, ptr(w), ptr(bias), n, float(alpha), ptr(res),
+                                                    ptr(out)), self._L)
+        return out
+
+    def stage_gemm(self, mode: int, epilogue: int, a, w, bias=None, alpha: float = 1.0, res=None, device="cuda"):
+        """The same on numpy arrays -> a numpy array (the copies go through torch; the library has the device form only)."""
+        import torch
+        up = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(device)
+        return self.stage_gemm_device(mode, epilogue, up(a), up(w), up(bias), alpha, up(res)).cpu().numpy()
+
     def _shape(self):
         if not self.loaded:      # the library refuses the call with its own message; the buffers need no width for that
             return 1, 1
@@ -430,6 +465,10 @@ class Parakeet:
     def close(self):
         self.encoder.close()
         self.decoder.close()
+
+    def set_precision(self, mode: int):
+        """The encoder's precision mode (ParakeetEncoder.set_precision); the front end and the decoder stay f32."""
+        self.encoder.set_precision(mode)
 
     def load(self, config, tdt_config, state_dict):
         """One ParakeetForTDT state dict: the `encoder.*` keys go to the encoder, the rest to the decoder."""

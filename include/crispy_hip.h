@@ -1334,6 +1334,44 @@ int crispy_pk_encode(void *h, const float *feats, const long *frame_offset, int 
                      float *pos);
 
 /* ------------------------------------------------------------------------------------------
+ * Parakeet encoder, precision mode 1: f16 operands on the dense matrix cores, f32 sums.  New entry points only: no struct
+ * grew, the ABI version is unchanged.  Mode 0 (the default) is the section above, bit for bit.
+ *
+ * Definition.  Every product that the GEMM performs inside crispy_pk_encode -- subsampling.linear, the four feed-forward
+ * linears, the fused q | k | v projection, relative_k_proj on the position table, o_proj, pointwise_conv1 and pointwise_conv2 --
+ * takes BOTH operands rounded once to IEEE binary16: round to nearest even, subnormals kept (not flushed), overflow to
+ * infinity, exactly torch.Tensor.to(torch.float16).  The products are exact and the sums are f32: one accumulator per output
+ * element on v_mfma_f32_32x32x16_f16, k ascending in steps of 16 from zero, a chain of K / 16 instructions, so an element's
+ * sum depends on K alone -- not on the row's place in a tile, the clip count or its neighbours.  Everything else is mode 0's
+ * f32 arithmetic, untouched: the subsampling convolutions, LayerNorm, the attention products and soft-max, the depthwise
+ * convolution with its BatchNorm, the bias, the epilogues (scale, SiLU, GLU, residual) and the residual stream.  The features,
+ * the TDT handle and its encoder_projector stay f32.  An activation beyond 65504 in magnitude rounds to infinity and makes its
+ * own row non-finite; no other row changes.
+ *
+ *   crispy_pk_set_precision  mode 0 or 1; anything else is CRISPY_ERR_INVALID_ARG naming `mode`.  May be set before or after
+ *       crispy_pk_load and survives a reload.  The first time a loaded handle is in mode 1 the f16 copies of the GEMM weights
+ *       are packed on the device from the resident f32 matrices (2 bytes per GEMM weight: about 1.2 GB at the catalog widths),
+ *       after a check against the device's free memory: CRISPY_ERR_OOM leaves the handle in the mode it had with nothing
+ *       enqueued.  The copies live until crispy_pk_destroy or the next load; a load in mode 1 packs its own and is refused as
+ *       a whole when they do not fit.  crispy_pk_encode[_device] and crispy_pk_transcribe[_device] honour the encoder handle's mode.
+ *   crispy_pk_precision      the mode (NULL handle: 0).
+ *   crispy_pk_stage_gemm_device  one GEMM of the encoder as a stage, for tests; needs no load.  d_a [M][K] f32, d_w f32 in the
+ *       state-dict layout [cols][K] (cols = N, or 2 N with the GLU, in pointwise_conv1's own row order), d_bias [cols] or NULL,
+ *       d_res [M][N] (the residual epilogue only; may be d_c), d_c [M][N].  epilogue: CRISPY_PK_GEMM_SCALE (v * alpha), _SILU,
+ *       _RESIDUAL (res + alpha * v), _GLU (value * sigmoid(gate)).  The weight goes through the transposition of the load's
+ *       layout, mode 1's pack kernel and the encoder's own GEMM dispatch.  K a multiple of 32, cols of 128, M >= 1; otherwise
+ *       CRISPY_ERR_INVALID_ARG.  On the handle's stream, complete on return.
+ * ------------------------------------------------------------------------------------------ */
+#define CRISPY_PK_GEMM_SCALE 0
+#define CRISPY_PK_GEMM_SILU 1
+#define CRISPY_PK_GEMM_RESIDUAL 2
+#define CRISPY_PK_GEMM_GLU 3
+int crispy_pk_set_precision(void *h, int mode);
+int crispy_pk_precision(void *h);
+int crispy_pk_stage_gemm_device(void *h, int mode, int epilogue, const float *d_a, long M, int K, const float *d_w, const float *d_bias, int N,
+                                float alpha, const float *d_res, float *d_c);
+
+/* ------------------------------------------------------------------------------------------
  * Parakeet TDT decoder: greedy token-and-duration transducer decoding of the encoder's frames -- tokens with frame times, and
  * from them the (start_s, end_s, word) records of the reference's transcribe_with_timestamps
  * (managers/transcription.rs:196-237).  f32 operands and f32 sums throughout; the whole loop runs on the device.  New entry

@@ -10,7 +10,11 @@ the catalog config (H 1024, 24 blocks, 8 heads, ffn 4096, K 9, C 256, M 128) wit
     scaled up -- a STAND-IN for ONNX Runtime on the CPU, which is not installed;
   * as a sanity check of the run, the largest distance between the device's frames and that oracle's on those clips.
 
-    python tools/pk_encoder_timing.py [--clips 64] [--rows 3000] [--layers 24] [--threads 16] [--host-clips 1] [--json OUT]
+  * with --precision 1 the same in precision mode 1 (f16 operands in the GEMMs, against the 2.5 PF f16 roof), with --alternate both
+    modes call by call in one session; the bytes of A and C the GEMM stage moves per second; the memory mode 1's copies take.
+
+    python tools/pk_encoder_timing.py [--clips 64] [--rows 3000] [--layers 24] [--threads 16] [--host-clips 1] [--precision {0,1}]
+                                      [--alternate] [--json OUT]
 """
 import argparse
 import json
@@ -29,6 +33,7 @@ from tests import pk_oracle as PO      # noqa: E402
 
 STAGES = ("subsampling", "gemms", "attention", "convolution", "layernorm")
 PEAK_TFLOPS = 157.3
+PEAK_F16_TFLOPS = 2500.0      # the dense f16 matrix roof, mode 1's GEMMs
 
 
 def flop(cfg, t, n_clips):
@@ -71,6 +76,8 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--host-clips", type=int, default=1, help="clips the host stand-in computes (its time is scaled up)")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--precision", type=int, choices=(0, 1), default=0, help="crispy_pk_set_precision: 0 f32 operands, 1 f16 operands in the GEMMs")
+    ap.add_argument("--alternate", action="store_true", help="both precision modes, alternating call by call in this one session")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
 
@@ -85,49 +92,77 @@ def main():
     t = PO.frames(a.rows)
     gemm_flop, attn_flop = flop(cfg, t, a.clips)
 
+    modes = [0, 1] if a.alternate else [a.precision]
+    peak = {0: PEAK_TFLOPS, 1: PEAK_F16_TFLOPS}
+
     os.environ["CRISPY_PK_TIMELINE"] = "1"      # read by the developer build only
     dev = ParakeetEncoder(0, lib=N.load_variant("dev"))
     dev.load(cfg.as_dict(), w)
-    dev.encode_device(feats[:1])
-    timeline(dev, feats)                        # the workspace at its full size
-    stage = timeline(dev, feats)
+    stage = {}
+    for _ in range(2):                          # the first round sizes the workspace and packs mode 1's copies; the second is reported
+        for mode in modes:
+            dev.set_precision(mode)
+            dev.encode_device(feats[:1])
+            stage[mode] = timeline(dev, feats)
     dev.close()
 
     enc = ParakeetEncoder(0)
     enc.load(cfg.as_dict(), w)
-    enc.encode_device(feats[:1])      # warm-up: code objects
-    out = enc.encode_device(feats)    # ... and the workspace at its full size
-    dev_ms = []
+    added = 0
+    dev_ms, out = {m: [] for m in modes}, {}
+    for mode in modes:
+        free0 = torch.cuda.mem_get_info()[0]
+        enc.set_precision(mode)
+        if mode == 1:
+            added = free0 - torch.cuda.mem_get_info()[0]      # the f16 copies of the GEMM weights, packed by this call
+        enc.encode_device(feats[:1])      # warm-up: code objects
+        enc.encode_device(feats)          # ... and the workspace at its full size
     for _ in range(a.reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        out = enc.encode_device(feats, stream=torch.cuda.current_stream().cuda_stream)
-        e1.record()
-        torch.cuda.synchronize()
-        dev_ms.append(e0.elapsed_time(e1))
+        for mode in modes:                # the modes alternate inside one session
+            enc.set_precision(mode)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            out[mode] = enc.encode_device(feats, stream=torch.cuda.current_stream().cuda_stream)
+            e1.record()
+            torch.cuda.synchronize()
+            dev_ms[mode].append(e0.elapsed_time(e1))
     sub = min(a.host_clips, a.clips)
-    got = [o.cpu().numpy() for o in out[:sub]]
+    got = {m: [o.cpu().numpy() for o in out[m][:sub]] for m in modes}
     enc.close()
 
-    torch.set_num_threads(a.threads)
-    net = PO.Encoder(cfg, w, torch.float32)
-    net.forward([clips[0][:64]])
-    t0 = time.perf_counter()
-    ref = net.forward(clips[:sub])
-    torch_ms = 1e3 * (time.perf_counter() - t0) * a.clips / sub
-    worst = max(float(np.abs(g - r[0]).max()) for g, r in zip(got, ref))
-    best = min(dev_ms)
+    torch_ms, worst = None, {}
+    if sub > 0:
+        torch.set_num_threads(a.threads)
+        net = PO.Encoder(cfg, w, torch.float32)
+        net.forward([clips[0][:64]])
+        t0 = time.perf_counter()
+        ref = net.forward(clips[:sub])
+        torch_ms = 1e3 * (time.perf_counter() - t0) * a.clips / sub
+        worst = {m: max(float(np.abs(g - r[0]).max()) for g, r in zip(got[m], ref)) for m in modes}
+    # bytes of A read and C written by the GEMMs of a call, each once: what the stage moves at the least besides the weights
+    H, F = cfg.hidden, cfg.ffn
+    frames = t * a.clips
+    ac_bytes = 4 * frames * (cfg.sub_channels * (cfg.mel_bins // 8) + H + cfg.layers * (2 * (H + F) + 2 * (F + 2 * H) + (H + 3 * H) + 3 * H + (H + H) + 3 * H))
     res = {"device": torch.cuda.get_device_name(0), "config": cfg.as_dict(), "clips": a.clips, "rows": a.rows, "frames_per_clip": t,
-           "device_call_ms": dev_ms, "stage_ms_dev_build": stage, "gemm_tflop": gemm_flop / 1e12, "attention_tflop": attn_flop / 1e12,
-           "gemm_stage_tflops": gemm_flop / (stage["gemms"] * 1e-3) / 1e12, "attention_stage_tflops": attn_flop / (stage["attention"] * 1e-3) / 1e12,
-           "call_tflops": (gemm_flop + attn_flop) / (best * 1e-3) / 1e12, "f32_matrix_peak_tflops": PEAK_TFLOPS,
-           "torch_f32_ms_scaled": torch_ms, "torch_threads": a.threads, "torch_clips_run": sub, "worst_frame_diff_to_torch_f32": worst}
-    print(f"{a.clips} clips x {a.rows} rows ({t} frames each, {a.layers} blocks): crispy_pk_encode_device {min(dev_ms):.1f} - {max(dev_ms):.1f} ms by "
-          f"events; developer build by stage: " + ", ".join(f"{k} {stage[k]:.1f}" for k in STAGES) + f" ms; GEMM stage "
-          f"{res['gemm_stage_tflops']:.1f} TFLOP/s, attention {res['attention_stage_tflops']:.1f}, whole call {res['call_tflops']:.1f} of "
-          f"{PEAK_TFLOPS} peak ({100 * res['call_tflops'] / PEAK_TFLOPS:.0f} %); float32 torch stand-in for ONNX Runtime on {a.threads} threads "
-          f"{torch_ms:.0f} ms (from {sub} clips); worst |device - torch f32| frame value {worst:.2e}", flush=True)
+           "gemm_tflop": gemm_flop / 1e12, "attention_tflop": attn_flop / 1e12, "gemm_a_and_c_gbytes": ac_bytes / 1e9,
+           "f16_weight_copies_bytes": int(added), "torch_f32_ms_scaled": torch_ms, "torch_threads": a.threads, "torch_clips_run": sub, "modes": {}}
+    for m in modes:
+        best = min(dev_ms[m])
+        r = {"device_call_ms": dev_ms[m], "stage_ms_dev_build": stage[m], "gemm_stage_tflops": gemm_flop / (stage[m]["gemms"] * 1e-3) / 1e12,
+             "attention_stage_tflops": attn_flop / (stage[m]["attention"] * 1e-3) / 1e12, "call_tflops": (gemm_flop + attn_flop) / (best * 1e-3) / 1e12,
+             "matrix_peak_tflops": peak[m], "gemm_a_and_c_tbytes_per_s": ac_bytes / (stage[m]["gemms"] * 1e-3) / 1e12,
+             "worst_frame_diff_to_torch_f32": worst.get(m)}
+        res["modes"][str(m)] = r
+        print(f"precision {m}: {a.clips} clips x {a.rows} rows ({t} frames each, {a.layers} blocks): crispy_pk_encode_device {min(dev_ms[m]):.1f} - "
+              f"{max(dev_ms[m]):.1f} ms by events; developer build by stage: " + ", ".join(f"{k} {stage[m][k]:.1f}" for k in STAGES) + f" ms; GEMM stage "
+              f"{r['gemm_stage_tflops']:.1f} TFLOP/s of {peak[m]:g} peak ({100 * r['gemm_stage_tflops'] / peak[m]:.0f} %), its A and C at "
+              f"{r['gemm_a_and_c_tbytes_per_s']:.2f} TB/s; attention {r['attention_stage_tflops']:.1f} TFLOP/s"
+              + (f"; worst |device - torch f32| frame value {worst[m]:.2e}" if m in worst else ""), flush=True)
+    if torch_ms is not None:
+        print(f"float32 torch stand-in for ONNX Runtime on {a.threads} threads {torch_ms:.0f} ms (from {sub} clips)")
+    if added:
+        print(f"mode 1's f16 copies of the GEMM weights: {added / 1e9:.2f} GB of device memory")
     print(json.dumps(res))
     if a.json:
         with open(a.json, "w") as f:
