@@ -394,6 +394,10 @@ extern "C" {
     pub fn crispy_pk_set_precision(h: *mut c_void, mode: c_int) -> c_int;
     pub fn crispy_pk_precision(h: *mut c_void) -> c_int;
     pub fn crispy_pk_stage_gemm_device(h: *mut c_void, mode: c_int, epilogue: c_int, d_a: *const c_float, m: c_long, k: c_int, d_w: *const c_float, d_bias: *const c_float, n: c_int, alpha: c_float, d_res: *const c_float, d_c: *mut c_float) -> c_int;
+    // Parakeet encoder, attention mode 1 (f16 operands in the attention's three products, f32 sums; key tile CRISPY_PK_ATTN_KEY_TILE 32)
+    pub fn crispy_pk_set_attention_precision(h: *mut c_void, mode: c_int) -> c_int;
+    pub fn crispy_pk_attention_precision(h: *mut c_void) -> c_int;
+    pub fn crispy_pk_stage_attention_device(h: *mut c_void, mode: c_int, d_qkv: *const c_float, d_r: *const c_float, d_bias_u: *const c_float, d_bias_v: *const c_float, frame_offset: *const c_long, n_clips: c_int, heads: c_int, tmax: c_int, d_out: *mut c_float) -> c_int;
     // Parakeet TDT decoder; `cfg` points at a `crispy_pk_tdt_config`
     pub fn crispy_pk_tdt_create(device: c_int, out: *mut *mut c_void) -> c_int;
     pub fn crispy_pk_tdt_destroy(h: *mut c_void);

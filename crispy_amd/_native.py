@@ -79,10 +79,13 @@ PK_TDT_SYMBOLS = ("crispy_pk_tdt_create", "crispy_pk_tdt_destroy", "crispy_pk_td
 PK_MEL_SYMBOLS = ("crispy_pk_feature_rows", "crispy_pk_mel_filters", "crispy_pk_set_mel_filters", "crispy_pk_features_device", "crispy_pk_features",
                   "crispy_pk_transcribe_device", "crispy_pk_transcribe")
 PK_F16_SYMBOLS = ("crispy_pk_set_precision", "crispy_pk_precision", "crispy_pk_stage_gemm_device")
+PK_ATTN_F16_SYMBOLS = ("crispy_pk_set_attention_precision", "crispy_pk_attention_precision", "crispy_pk_stage_attention_device")
 ALL_SYMBOLS = (RN_SYMBOLS + MEL_SYMBOLS + ASR_SYMBOLS + RS_SYMBOLS + DIAR_SYMBOLS + DIAR_FRONT_SYMBOLS + DIAR_SEG_SYMBOLS + DIAR_EMB_SYMBOLS
-               + PK_SYMBOLS + PK_TDT_SYMBOLS + PK_MEL_SYMBOLS + PK_F16_SYMBOLS)
+               + PK_SYMBOLS + PK_TDT_SYMBOLS + PK_MEL_SYMBOLS + PK_F16_SYMBOLS + PK_ATTN_F16_SYMBOLS)
 PK_GEMM_SCALE, PK_GEMM_SILU, PK_GEMM_RESIDUAL, PK_GEMM_GLU = 0, 1, 2, 3      # include/crispy_hip.h: CRISPY_PK_GEMM_*
 PK_F16_TILE_M, PK_F16_TILE_N = 128, 128      # crispy_amd/csrc/pk_gemm_f16.hip
+PK_ATTN_KEY_TILE = 32      # include/crispy_hip.h: CRISPY_PK_ATTN_KEY_TILE, the key tile of attention mode 1's soft-max
+PK_ATTN_F16_Q = 128        # crispy_amd/csrc/pk_internal.h: kAttnF16Q, the queries of one workgroup of pk_attn_f16.hip
 PK_MEL_SPEC, PK_MEL_MAX_BINS, PK_MEL_MAX_TAPS, PK_MEL_MIN_SAMPLES, PK_MEL_TILE_FRAMES = 257, 128, 4096, 320, 32      # crispy_amd/csrc/pk_internal.h
 PK_TDT_ROWS, PK_TDT_COLS, PK_TDT_MAX_FRAMES, PK_TDT_GROUP = 16, 64, 5000, 32      # crispy_amd/csrc/pk_internal.h
 PK_HEAD_DIM, PK_MAX_ROWS, PK_MAX_CLIPS, PK_ATTN_Q, PK_ATTN_K = 128, 40000, 4096, 32, 32      # crispy_amd/csrc/pk_internal.h
@@ -395,6 +398,10 @@ def load_library(path: str) -> C.CDLL:
     L.crispy_pk_precision.argtypes = [C.c_void_p]
     L.crispy_pk_stage_gemm_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
                                               C.c_void_p, C.c_void_p]
+    L.crispy_pk_set_attention_precision.argtypes = [C.c_void_p, C.c_int]
+    L.crispy_pk_attention_precision.argtypes = [C.c_void_p]
+    L.crispy_pk_stage_attention_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_long), C.c_int,
+                                                   C.c_int, C.c_int, C.c_void_p]
     L.crispy_pk_tdt_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.crispy_pk_tdt_destroy.argtypes = [C.c_void_p]
     L.crispy_pk_tdt_destroy.restype = None

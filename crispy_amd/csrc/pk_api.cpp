@@ -1,5 +1,5 @@
 // pk_api.cpp -- host side of the Parakeet FastConformer encoder (include/crispy_hip.h, "Parakeet encoder"; kernels in pk_sub.hip,
-// pk_gemm.hip, pk_gemm_f16.hip and pk_attn.hip): the tensor table of crispy_pk_tensor_spec and crispy_pk_load, the folds and the layout of the
+// pk_gemm.hip, pk_gemm_f16.hip, pk_attn.hip and pk_attn_f16.hip): the tensor table of crispy_pk_tensor_spec and crispy_pk_load, the folds and the layout of the
 // handle's device copy, precision mode 1's f16 copies of the GEMM weights, the workspace and the launches of a call; and crispy_pk_transcribe ("Parakeet front end"), which joins the
 // front end (pk_mel_api.cpp), the encoder and the decoder (pk_tdt_api.cpp) in one call.
 #include <cmath>
@@ -352,7 +352,7 @@ int pk_run(crispy_pk* h, const float* d_feats, const long* frame_offset, int n_c
     HIP_TRY(launch_gemm(mode, kGemmScale, w.ln, H, l.qkv_w, lh.qkv_w, l.qkv_b, 3 * H, 1.0f, nullptr, w.big, T, st));
     HIP_TRY(launch_gemm(mode, kGemmScale, pos, H, l.r_w, lh.r_w, nullptr, H, 1.0f, nullptr, w.r, 2L * tmax - 1, st));
     HIP_TRY(tl.mark(kStGemm, st));
-    HIP_TRY(launch_attention(l, tb, w.big, w.r, tmax, cfg.heads, w.mid, st));
+    HIP_TRY(launch_attention(h->attn_precision, l, tb, w.big, w.r, tmax, cfg.heads, w.mid, st));
     HIP_TRY(tl.mark(kStAttn, st));
     HIP_TRY(launch_gemm(mode, kGemmResidual, w.mid, H, l.o_w, lh.o_w, l.o_b, H, 1.0f, w.x, w.x, T, st));
     HIP_TRY(tl.mark(kStGemm, st));
@@ -678,6 +678,62 @@ int crispy_pk_stage_gemm_device(void* hv, int mode, int epilogue, const float* d
   return CRISPY_OK;
 }
 CRISPY_CATCH_RET("crispy_pk_stage_gemm_device")
+
+int crispy_pk_set_attention_precision(void* hv, int mode) try {
+  const char* who = "crispy_pk_set_attention_precision";
+  crispy_pk* h = static_cast<crispy_pk*>(hv);
+  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "%s: NULL handle", who);
+  if (mode != 0 && mode != 1) return fail(CRISPY_ERR_INVALID_ARG, "%s: mode %d is neither 0 nor 1", who, mode);
+  h->attn_precision = mode;      // the operands are activations: nothing to pack
+  return CRISPY_OK;
+}
+CRISPY_CATCH_RET("crispy_pk_set_attention_precision")
+
+int crispy_pk_attention_precision(void* hv) try {
+  const crispy_pk* h = static_cast<const crispy_pk*>(hv);
+  return h ? h->attn_precision : 0;
+}
+CRISPY_CATCH_RET("crispy_pk_attention_precision")
+
+int crispy_pk_stage_attention_device(void* hv, int mode, const float* d_qkv, const float* d_r, const float* d_bias_u, const float* d_bias_v,
+                                     const long* frame_offset, int n_clips, int heads, int tmax, float* d_out) try {
+  const char* who = "crispy_pk_stage_attention_device";
+  crispy_pk* h = static_cast<crispy_pk*>(hv);
+  if (!h) return fail(CRISPY_ERR_INVALID_ARG, "%s: NULL handle", who);
+  if (mode != 0 && mode != 1) return fail(CRISPY_ERR_INVALID_ARG, "%s: mode %d is neither 0 nor 1", who, mode);
+  const struct { const char* name; const void* p; } ptrs[] = {{"d_qkv", d_qkv}, {"d_r", d_r}, {"d_bias_u", d_bias_u}, {"d_bias_v", d_bias_v}, {"d_out", d_out}};
+  for (const auto& a : ptrs) {
+    if (!a.p) return fail(CRISPY_ERR_INVALID_ARG, "%s: %s is NULL", who, a.name);
+    if (reinterpret_cast<size_t>(a.p) % 16 != 0) return fail(CRISPY_ERR_INVALID_ARG, "%s: %s is not 16-byte aligned", who, a.name);
+  }
+  if (!frame_offset) return fail(CRISPY_ERR_INVALID_ARG, "%s: frame_offset is NULL", who);
+  if (n_clips < 1 || n_clips > kMaxClips) return fail(CRISPY_ERR_INVALID_ARG, "%s: n_clips %d outside 1 ... %d", who, n_clips, kMaxClips);
+  if (heads < 1 || heads > 16) return fail(CRISPY_ERR_INVALID_ARG, "%s: heads %d outside 1 ... 16", who, heads);
+  if (tmax < 1 || tmax > kMaxFrames) return fail(CRISPY_ERR_INVALID_ARG, "%s: tmax %d outside 1 ... %d", who, tmax, kMaxFrames);
+  if (frame_offset[0] != 0) return fail(CRISPY_ERR_INVALID_ARG, "%s: frame_offset[0] is %ld, not 0", who, frame_offset[0]);
+  std::vector<int> off((size_t)n_clips + 1, 0);
+  PkTables tb{};
+  tb.n_clips = n_clips;
+  for (int c = 0; c < n_clips; ++c) {
+    const long n = frame_offset[c + 1] - frame_offset[c];
+    if (n < 1 || n > tmax) return fail(CRISPY_ERR_INVALID_ARG, "%s: frame_offset: clip %d has %ld frames, outside 1 ... tmax (%d)", who, c, n, tmax);
+    off[(size_t)c + 1] = (int)frame_offset[c + 1];
+    tb.max_len[3] = std::max(tb.max_len[3], (int)n);
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  crispy::DevBuf<int> d_off;
+  HIP_TRY(d_off.alloc(off.size() * sizeof(int)));
+  HIP_TRY(hipMemcpyAsync(d_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  tb.off[3] = d_off.p;
+  PkLayer l{};
+  l.bias_u = d_bias_u;
+  l.bias_v = d_bias_v;
+  const hipError_t err = launch_attention(mode, l, tb, d_qkv, d_r, tmax, heads, d_out, h->stream);
+  HIP_TRY(hipStreamSynchronize(h->stream));      // off and d_off go with the call
+  HIP_TRY(err);
+  return CRISPY_OK;
+}
+CRISPY_CATCH_RET("crispy_pk_stage_attention_device")
 
 int crispy_pk_encode_device(void* hv, const float* d_feats, const long* frame_offset, int n_clips, float* d_out, float* d_sub, int tap_layer,
                             float* d_tap, float* d_pos, void* hip_stream) try {

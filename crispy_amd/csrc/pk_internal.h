@@ -1,4 +1,4 @@
-// pk_internal.h -- what the host side (pk_api.cpp) and the device side (pk_sub.hip, pk_gemm.hip, pk_gemm_f16.hip, pk_attn.hip) of the Parakeet
+// pk_internal.h -- what the host side (pk_api.cpp) and the device side (pk_sub.hip, pk_gemm.hip, pk_gemm_f16.hip, pk_attn.hip, pk_attn_f16.hip) of the Parakeet
 // FastConformer encoder share: the handle, the model as the kernels read it and the launch functions; the same for the TDT
 // decoder (pk_tdt_api.cpp, pk_tdt.hip) and the log-mel front end (pk_mel_api.cpp, pk_mel.hip).
 #pragma once
@@ -16,6 +16,7 @@ struct crispy_pk {
   crispy::DevBuf<float> weights;      // the encoder as crispy_pk_load laid it out (PkModel); empty until a load
   crispy_pk_config cfg{};             // of the load
   int precision = 0;                  // crispy_pk_set_precision: 0 f32 operands, 1 f16 operands in every GEMM
+  int attn_precision = 0;             // crispy_pk_set_attention_precision: 0 f32 operands, 1 f16 operands in the attention's three products
   crispy::DevBuf<char> weights16;     // mode 1: the GEMM weights packed as f16 (PkHalfModel); empty until the loaded handle is first in mode 1
   crispy::DevBuf<char> scratch;       // a call's workspace, grown on demand and kept
   crispy::DevBuf<char> io;            // host-form features, frames and taps
@@ -49,10 +50,12 @@ namespace crispy {
 namespace pk {
 
 constexpr int kHeadDim = 128;
+constexpr int kMaxFrames = 5000;                       // T' of kMaxRows rows: the longest clip an attention pass takes
 constexpr int kMaxRows = 40000, kMaxClips = 4096;      // T' <= 5000, the model's max_position_embeddings
 constexpr int kMaxTaps = 31, kMaxSubCh = 512;
 constexpr double kEps = 1e-5;                          // LayerNorm and BatchNorm
 constexpr int kAttnQ = 32, kAttnK = 32;                // query and key tile of the attention kernel
+constexpr int kAttnF16Q = 128, kAttnF16K = CRISPY_PK_ATTN_KEY_TILE;      // the same of attention mode 1 (pk_attn_f16.hip)
 constexpr int kSubNF = 8;                              // frequencies of one workgroup of the fused depthwise + pointwise kernel
 
 inline long sub_len(long n) { return n < 1 ? 0 : (n - 1) / 2 + 1; }
@@ -125,6 +128,12 @@ hipError_t launch_weight_transpose(const float* d_w, int K, int cols, bool glu, 
 hipError_t launch_pos_table(const float* inv_freq, int tmax, int H, float* d_pos, hipStream_t st);
 // soft-max((q + u) k^T + (q + v) r_{i - j}^T) / sqrt(128)) v per clip and head; qkv [T'][3H], r [2 * tmax - 1][H] -> out [T'][H]
 hipError_t launch_attention(const PkLayer& l, const PkTables& t, const float* d_qkv, const float* d_r, int tmax, int heads, float* d_out, hipStream_t st);
+// The encoder's form, by the handle's attention mode (crispy_pk_set_attention_precision).  0: the call above.  1: the same with q + u,
+// q + v, k, r, v and the soft-max weights rounded once to f16 on the f16 matrix instruction, f32 sums, the soft-max in key tiles of
+// CRISPY_PK_ATTN_KEY_TILE (pk_attn_f16.hip: launch_attention_f16).
+hipError_t launch_attention(int mode, const PkLayer& l, const PkTables& t, const float* d_qkv, const float* d_r, int tmax, int heads, float* d_out,
+                            hipStream_t st);
+hipError_t launch_attention_f16(const PkLayer& l, const PkTables& t, const float* d_qkv, const float* d_r, int tmax, int heads, float* d_out, hipStream_t st);
 // silu(scale * depthwise K-tap convolution + shift), zero-padded at each clip's own edges; [T'][H] -> [T'][H]
 hipError_t launch_dwconv(const PkLayer& l, const PkTables& t, const float* d_in, int H, int K, float* d_out, hipStream_t st);
 

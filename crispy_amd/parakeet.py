@@ -150,6 +150,42 @@ class ParakeetEncoder:
         up = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(device)
         return self.stage_gemm_device(mode, epilogue, up(a), up(w), up(bias), alpha, up(res)).cpu().numpy()
 
+    def set_attention_precision(self, mode: int):
+        """0: f32 operands in the attention's three products (the default).  1: q + u, q + v, k, r, v and the soft-max weights rounded
+        once to f16, f32 sums, the soft-max in key tiles of N.PK_ATTN_KEY_TILE (crispy_pk_set_attention_precision).  Independent of
+        set_precision; before or after a load, and kept across loads."""
+        N.check(self._L.crispy_pk_set_attention_precision(self._h, int(mode)), self._L)
+
+    @property
+    def attention_precision(self) -> int:
+        return int(self._L.crispy_pk_attention_precision(self._h))
+
+    def stage_attention_device(self, mode: int, qkv, r, bias_u, bias_v, lengths, heads: int, tmax: int):
+        """One attention pass as a stage (crispy_pk_stage_attention_device; needs no load): CUDA f32 tensors qkv [sum n, 3 * heads * 128]
+        (q | k | v side by side), r [2 tmax - 1, heads * 128] (row p for the distance p - (tmax - 1)), bias_u and bias_v
+        [heads * 128]; `lengths` the clips' frame counts -> a CUDA tensor [sum n, heads * 128]."""
+        import torch
+        def prep(t):      # contiguous f32 on a 16-byte boundary
+            if t.dtype != torch.float32:
+                raise ValueError("the operands must be f32")
+            t = t.contiguous()
+            return t.clone() if t.data_ptr() % 16 else t
+        qkv, r, bias_u, bias_v = prep(qkv), prep(r), prep(bias_u), prep(bias_v)
+        off = _sample_offsets([int(n) for n in lengths])
+        n = len(lengths)
+        out = torch.empty((max(int(off[-1]), 1), max(int(heads), 1) * N.PK_HEAD_DIM), dtype=torch.float32, device=qkv.device)      # never empty: the library refuses heads itself
+        torch.cuda.current_stream(qkv.device).synchronize()      # the handle's stream does not wait for torch's
+        ptr = lambda t: t.data_ptr() if t.numel() else None
+        N.check(self._L.crispy_pk_stage_attention_device(self._h, int(mode), ptr(qkv), ptr(r), ptr(bias_u), ptr(bias_v), _p(off, C.c_long) if n else None,
+                                                         n, int(heads), int(tmax), ptr(out)), self._L)
+        return out[:int(off[-1])] if int(heads) >= 1 else out[:0]
+
+    def stage_attention(self, mode: int, qkv, r, bias_u, bias_v, lengths, heads: int, tmax: int, device="cuda"):
+        """The same on numpy arrays -> a numpy array (the copies go through torch; the library has the device form only)."""
+        import torch
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(device)
+        return self.stage_attention_device(mode, up(qkv), up(r), up(bias_u), up(bias_v), lengths, heads, tmax).cpu().numpy()
+
     def _shape(self):
         if not self.loaded:      # the library refuses the call with its own message; the buffers need no width for that
             return 1, 1
@@ -469,6 +505,10 @@ class Parakeet:
     def set_precision(self, mode: int):
         """The encoder's precision mode (ParakeetEncoder.set_precision); the front end and the decoder stay f32."""
         self.encoder.set_precision(mode)
+
+    def set_attention_precision(self, mode: int):
+        """The encoder's attention mode (ParakeetEncoder.set_attention_precision), independent of set_precision."""
+        self.encoder.set_attention_precision(mode)
 
     def load(self, config, tdt_config, state_dict):
         """One ParakeetForTDT state dict: the `encoder.*` keys go to the encoder, the rest to the decoder."""

@@ -1372,6 +1372,49 @@ int crispy_pk_stage_gemm_device(void *h, int mode, int epilogue, const float *d_
                                 float alpha, const float *d_res, float *d_c);
 
 /* ------------------------------------------------------------------------------------------
+ * Parakeet encoder, attention mode 1: f16 operands in the three products of the relative-position attention, f32 sums.  A second
+ * switch on the encoder handle, independent of crispy_pk_set_precision: all four combinations are valid.  New entry points only:
+ * no struct grew, the ABI version is unchanged.  Attention mode 0 (the default) is today's attention bit for bit under both GEMM
+ * modes.
+ *
+ * Definition, per (clip, head), over the clip's own n frames.  q, k and v are the f32 outputs of the fused projection, r the f32
+ * output of relative_k_proj on the position table, u and v_b the head's bias_u and bias_v.
+ *   1. Operands.  Five operands are each rounded once to IEEE binary16: q + u and q + v_b (the sums formed in f32, then rounded),
+ *      k, r and v -- round to nearest even, subnormals kept, overflow to infinity, exactly torch.Tensor.to(torch.float16).
+ *      Products are exact in f32 and sums are f32.
+ *   2. Score.  ac(i, j) = f16(q_i + u) . f16(k_j), bd(i, d) = f16(q_i + v_b) . f16(r_d), and
+ *      score(i, j) = (ac(i, j) + bd(i, i - j)) * 128^-1/2: the addition and the scale are f32 and come after the sums (the scale
+ *      is not folded into an operand: 2^-3.5 is not exact).
+ *   3. Soft-max.  Over the keys in tiles of CRISPY_PK_ATTN_KEY_TILE keys, ascending from the clip's first key, with a running
+ *      maximum m and sum l in f32 (m = -inf, l = 0, o = 0 at the start):  m_new = max(m, the tile's largest score);
+ *      alpha = expf(m - m_new);  p_j = expf(score_j - m_new);  l = l * alpha + the sum of the unrounded f32 p_j;
+ *      o = o * alpha + sum_j f16(p_j) * f16(v_j) (f32 sums);  at the end out = o / l.  Keys behind the clip's end contribute
+ *      nothing.  The tile length is part of the definition: f16(p_j) is rounded relative to the running maximum, so another
+ *      tiling gives other f16 neighbours.  The order of the additions inside one sum is the implementation's, fixed, and depends
+ *      on the clip's own length alone: a clip's bytes are the same alone, at any position of any batch and in any call.
+ *   4. Overflow.  An operand beyond 65504 in magnitude makes rows of its own clip non-finite; no other clip's bytes change.
+ *
+ *   crispy_pk_set_attention_precision  mode 0 or 1; anything else is CRISPY_ERR_INVALID_ARG naming `mode` and leaves the handle
+ *       as it was.  May be set before or after crispy_pk_load and survives a reload.  Allocates nothing (the operands are
+ *       activations; no weights are packed) and cannot fail on memory.  crispy_pk_encode[_device] and
+ *       crispy_pk_transcribe[_device] honour the encoder handle's mode.  crispy_pk_precision is unaffected, and the reverse.
+ *   crispy_pk_attention_precision      the mode (NULL handle: 0).
+ *   crispy_pk_stage_attention_device   one attention pass as a stage, for tests; needs no load.  d_qkv [sum n][3 * heads * 128]
+ *       as the fused projection stores it (q | k | v side by side, each head's 128 columns together); d_r [2 tmax - 1][heads * 128],
+ *       row p for the distance d = p - (tmax - 1); d_bias_u, d_bias_v [heads * 128]; frame_offset a host array [n_clips + 1] of
+ *       the clips' first frames, frame_offset[0] = 0; d_out [sum n][heads * 128].  The device pointers are 16-byte aligned.  Goes
+ *       through the encoder's own attention dispatch with `mode`, whatever the handle's mode is.  Refused with
+ *       CRISPY_ERR_INVALID_ARG naming the field, with nothing enqueued: a NULL pointer, n_clips outside 1 ... 4096, heads outside
+ *       1 ... 16, tmax outside 1 ... 5000, a clip of 0 frames or longer than tmax, mode outside 0 / 1.  On the handle's stream,
+ *       complete on return.
+ * ------------------------------------------------------------------------------------------ */
+#define CRISPY_PK_ATTN_KEY_TILE 32
+int crispy_pk_set_attention_precision(void *h, int mode);
+int crispy_pk_attention_precision(void *h);
+int crispy_pk_stage_attention_device(void *h, int mode, const float *d_qkv, const float *d_r, const float *d_bias_u, const float *d_bias_v,
+                                     const long *frame_offset, int n_clips, int heads, int tmax, float *d_out);
+
+/* ------------------------------------------------------------------------------------------
  * Parakeet TDT decoder: greedy token-and-duration transducer decoding of the encoder's frames -- tokens with frame times, and
  * from them the (start_s, end_s, word) records of the reference's transcribe_with_timestamps
  * (managers/transcription.rs:196-237).  f32 operands and f32 sums throughout; the whole loop runs on the device.  New entry

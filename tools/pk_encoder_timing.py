@@ -11,10 +11,12 @@ the catalog config (H 1024, 24 blocks, 8 heads, ffn 4096, K 9, C 256, M 128) wit
   * as a sanity check of the run, the largest distance between the device's frames and that oracle's on those clips.
 
   * with --precision 1 the same in precision mode 1 (f16 operands in the GEMMs, against the 2.5 PF f16 roof), with --alternate both
-    modes call by call in one session; the bytes of A and C the GEMM stage moves per second; the memory mode 1's copies take.
+    modes call by call in one session; the bytes of A and C the GEMM stage moves per second; the memory mode 1's copies take;
+  * with --attention-precision 1 the attention's three products on f16 operands (crispy_pk_set_attention_precision), and with
+    --alternate attention both attention modes call by call in one session, the GEMMs fixed in precision mode 1.
 
     python tools/pk_encoder_timing.py [--clips 64] [--rows 3000] [--layers 24] [--threads 16] [--host-clips 1] [--precision {0,1}]
-                                      [--alternate] [--json OUT]
+                                      [--attention-precision {0,1}] [--alternate [precision|attention]] [--json OUT]
 """
 import argparse
 import json
@@ -77,7 +79,11 @@ def main():
     ap.add_argument("--host-clips", type=int, default=1, help="clips the host stand-in computes (its time is scaled up)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--precision", type=int, choices=(0, 1), default=0, help="crispy_pk_set_precision: 0 f32 operands, 1 f16 operands in the GEMMs")
-    ap.add_argument("--alternate", action="store_true", help="both precision modes, alternating call by call in this one session")
+    ap.add_argument("--attention-precision", type=int, choices=(0, 1), default=0,
+                    help="crispy_pk_set_attention_precision: 0 f32 operands, 1 f16 operands in the attention's three products")
+    ap.add_argument("--alternate", nargs="?", const="precision", default=None, choices=("precision", "attention"),
+                    help="alternate call by call in this one session: both precision modes (the default), or with `attention` both attention "
+                         "modes with the GEMMs in precision mode 1")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
 
@@ -92,8 +98,17 @@ def main():
     t = PO.frames(a.rows)
     gemm_flop, attn_flop = flop(cfg, t, a.clips)
 
-    modes = [0, 1] if a.alternate else [a.precision]
+    # a mode is (precision, attention precision); its label is the precision alone unless the attention is in mode 1 or alternates
+    if a.alternate == "attention":
+        modes = [(1, 0), (1, 1)]
+    else:
+        modes = [(g, a.attention_precision) for g in ([0, 1] if a.alternate else [a.precision])]
+    label = lambda m: str(m[0]) if a.alternate != "attention" and not a.attention_precision else f"{m[0]}, attention {m[1]}"
     peak = {0: PEAK_TFLOPS, 1: PEAK_F16_TFLOPS}
+
+    def select(e, m):
+        e.set_precision(m[0])
+        e.set_attention_precision(m[1])
 
     os.environ["CRISPY_PK_TIMELINE"] = "1"      # read by the developer build only
     dev = ParakeetEncoder(0, lib=N.load_variant("dev"))
@@ -101,7 +116,7 @@ def main():
     stage = {}
     for _ in range(2):                          # the first round sizes the workspace and packs mode 1's copies; the second is reported
         for mode in modes:
-            dev.set_precision(mode)
+            select(dev, mode)
             dev.encode_device(feats[:1])
             stage[mode] = timeline(dev, feats)
     dev.close()
@@ -112,14 +127,14 @@ def main():
     dev_ms, out = {m: [] for m in modes}, {}
     for mode in modes:
         free0 = torch.cuda.mem_get_info()[0]
-        enc.set_precision(mode)
-        if mode == 1:
+        select(enc, mode)
+        if mode[0] == 1 and not added:
             added = free0 - torch.cuda.mem_get_info()[0]      # the f16 copies of the GEMM weights, packed by this call
         enc.encode_device(feats[:1])      # warm-up: code objects
         enc.encode_device(feats)          # ... and the workspace at its full size
     for _ in range(a.reps):
         for mode in modes:                # the modes alternate inside one session
-            enc.set_precision(mode)
+            select(enc, mode)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
             e0.record()
@@ -151,12 +166,12 @@ def main():
         best = min(dev_ms[m])
         r = {"device_call_ms": dev_ms[m], "stage_ms_dev_build": stage[m], "gemm_stage_tflops": gemm_flop / (stage[m]["gemms"] * 1e-3) / 1e12,
              "attention_stage_tflops": attn_flop / (stage[m]["attention"] * 1e-3) / 1e12, "call_tflops": (gemm_flop + attn_flop) / (best * 1e-3) / 1e12,
-             "matrix_peak_tflops": peak[m], "gemm_a_and_c_tbytes_per_s": ac_bytes / (stage[m]["gemms"] * 1e-3) / 1e12,
+             "matrix_peak_tflops": peak[m[0]], "precision": m[0], "attention_precision": m[1], "gemm_a_and_c_tbytes_per_s": ac_bytes / (stage[m]["gemms"] * 1e-3) / 1e12,
              "worst_frame_diff_to_torch_f32": worst.get(m)}
-        res["modes"][str(m)] = r
-        print(f"precision {m}: {a.clips} clips x {a.rows} rows ({t} frames each, {a.layers} blocks): crispy_pk_encode_device {min(dev_ms[m]):.1f} - "
+        res["modes"][label(m)] = r
+        print(f"precision {label(m)}: {a.clips} clips x {a.rows} rows ({t} frames each, {a.layers} blocks): crispy_pk_encode_device {min(dev_ms[m]):.1f} - "
               f"{max(dev_ms[m]):.1f} ms by events; developer build by stage: " + ", ".join(f"{k} {stage[m][k]:.1f}" for k in STAGES) + f" ms; GEMM stage "
-              f"{r['gemm_stage_tflops']:.1f} TFLOP/s of {peak[m]:g} peak ({100 * r['gemm_stage_tflops'] / peak[m]:.0f} %), its A and C at "
+              f"{r['gemm_stage_tflops']:.1f} TFLOP/s of {peak[m[0]]:g} peak ({100 * r['gemm_stage_tflops'] / peak[m[0]]:.0f} %), its A and C at "
               f"{r['gemm_a_and_c_tbytes_per_s']:.2f} TB/s; attention {r['attention_stage_tflops']:.1f} TFLOP/s"
               + (f"; worst |device - torch f32| frame value {worst[m]:.2e}" if m in worst else ""), flush=True)
     if torch_ms is not None:
